@@ -7,7 +7,13 @@ barrier + device synchronisation; the metric is K / wall (max over ranks).  A "s
 the whole grid.  Inputs are synthetic (deterministic baroclinic-instability IC + seeded velocity noise) and are
 resident in HBM before the timed region starts.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--size Nx Ny Nz] [--weak] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--size Nx Ny Nz] [--weak] [--full] [--dump-outputs DIR]
+A plain run does only what the headline line needs: set-up, warm-up, the K timed steps, the outputs if --dump-outputs is
+given, the JSON line.  --full adds what takes time of its own: the per-kernel HIP-event timers and the roofline built on
+them (--no-profile leaves them out), and the CPU baselines of the oracle on this host (--no-cpu-baseline leaves them out).
+--dump-outputs DIR writes the state the timed loop leaves (Oceananigans.fields(model): u, v, w, eta, T, S and e where CATKE
+runs, interior points) as DIR/<name>.npy in the model's float type; a field of more than 8 MB is a fixed, seeded sample of
+its points (dump_outputs), so two builds can be compared output for output.
 N > 1 is launched by the driver with torch.distributed.run, one rank per GPU: the SAME Nx x Ny x Nz grid (BASELINE.json:
 1440x720x48 at 1/2/4/8 GPUs) cut into N x-slabs, i.e. strong scaling; --weak gives every rank its own Nx x Ny x Nz slab of
 an (N Nx) x Ny x Nz grid instead (the reference's own scaling protocol, sharding/sharded_..._run.jl:82-88).  Started
@@ -112,6 +118,22 @@ def counter_rng(shape, seed, salt):
     return ((x >> np.uint64(11)).astype(np.float64) / float(1 << 53)).reshape(shape, order="F")
 
 
+DUMP_BYTES_PER_FIELD = 8 << 20      # at most 7 fields (u, v, w, eta, T, S, e): 56 MB per run at most, under 64 MB
+
+
+def dump_outputs(model, directory, suffix="", bytes_per_field=DUMP_BYTES_PER_FIELD):
+    """Oceananigans.fields(model) at the interior points -> <directory>/<name><suffix>.npy in the model's float type.  A field
+    of more than `bytes_per_field` is sampled: the same seeded positions of its column-major (i fastest) order in every run
+    and every build, sorted, saved as a 1-D array."""
+    os.makedirs(directory, exist_ok=True)
+    for name, field in model.fields().items():
+        a = field.interior
+        k = bytes_per_field // a.itemsize
+        if a.size > k:
+            a = a.ravel(order="F")[np.sort(np.random.default_rng(20250).choice(a.size, k, replace=False))]
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), a)
+
+
 GRID_NAMES = {"simple_lat_lon": "LatitudeLongitudeGrid", "gaussian_islands_lat_lon": "LatitudeLongitudeGrid + GridFittedBottom(gaussian_islands)",
               "lat_lon_as_curvilinear": "LatitudeLongitudeGrid (curvilinear kernels)", "tripolar": "TripolarGrid",
               "gaussian_islands": "TripolarGrid + GridFittedBottom(gaussian_islands)"}
@@ -173,13 +195,21 @@ def main():
                          "x slabs where the reference decomposes in 2-D.  Not the headline line")
     ap.add_argument("--burn", type=int, default=0,
                     help="single GPU: run this many steps of a throw-away model first (GPU clocks at load before the timed model starts)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="skip the per-kernel HIP-event timers")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel timers with the roofline, and the CPU baselines (single GPU); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: the model's fields as DIR/<name>.npy (a seeded sample of a field over 8 MB; "
+                         "N > 1: <name>_rank<R>.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-profile", action="store_true", help="--full without the per-kernel HIP-event timers")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 100
     if args.warmup is None:
         args.warmup = 5
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    profile = args.full and not args.no_profile
     if args.data_free:
         args.grid_type, args.closure, args.dt = "gaussian_islands", "catke", 30.0
     if args.dt is None:
@@ -314,13 +344,13 @@ def main():
         gb.loop(scratch, args.burn)
         scratch.backend.synchronize()      # (closed after the timed region: freeing its fields would idle the GPU again)
     warm_kernels, dominant = {}, None
-    if not args.no_profile and args.warmup > 0:
+    if profile and args.warmup > 0:
         b.profile_enable(True)
         b.profile_reset()
     for _ in range(args.warmup):
         gb.time_step(model)
     b.synchronize()
-    if not args.no_profile:
+    if profile:
         if args.warmup > 0:
             warm_kernels = collect()
             timed_w = {k: v for k, v in warm_kernels.items() if k in ALGORITHMIC_BYTES_PER_CELL or k == "gu"}
@@ -347,10 +377,12 @@ def main():
 
     finite = bool(np.isfinite(model.free_surface.eta.interior).all())
     kernels = {}
-    if not args.no_profile:
+    if profile:
         kernels = collect()                       # timed region: the dominant kernel alone (or all, without warm-up)
         for k, v in warm_kernels.items():         # the others: per-kernel means of the warm-up steps
             kernels.setdefault(k, v)
+    if args.dump_outputs:                         # (after the timers are read: fetching a field may launch kernels)
+        dump_outputs(model, args.dump_outputs, "" if world == 1 else f"_rank{rank}", DUMP_BYTES_PER_FIELD // world)
 
     if rank == 0:
         cells = locNx * locNy * Nz                 # per GPU (= per launch of a kernel)
@@ -444,7 +476,7 @@ def main():
             out["kernels_ms_per_launch"] = {k: v["avg_ms"] for k, v in kernels.items()}
             out["kernel_times_from"] = (f"timed region: {dom}; others: warm-up steps" if warm_kernels
                                         else "timed region")
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(Nx, Ny, Nz, args.dt, grid_type=args.grid_type)
             # BASELINE.json configs[0] (the reference's own CPU-runnable case: 128x64x8, 100 AB2 steps) beside it
             c1 = cpu_baseline(128, 64, 8, 1200.0, budget_s=10.0, max_steps=99)

@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <condition_variable>
 #include <memory>
@@ -916,6 +917,9 @@ gb25_status alloc_field(gb25_model* m, Field& F, int nx, int ny, int nz) {
 }
 
 inline int mom_kchunks(const gb25_model* m) { return std::max(1, m->g.Nz / m->mom_chunk_levels); }
+inline int trc_kchunks(const gb25_model* m) { return std::max(1, m->g.Nz / m->trc_chunk_levels); }   // (>= 12 levels: z-carry start-up ~3 %)
+// w on the fly: the chunkings of the two tendency kernels must be the one the look-ahead's chunk sums were made with
+inline bool chunkings_match(const gb25_model* m) { return trc_kchunks(m) == mom_kchunks(m); }
 inline dim3 grid2(int nx, int ny, dim3 b) { return dim3((nx + b.x - 1) / b.x, (ny + b.y - 1) / b.y); }
 
 // sel: 3 = u, v, T, S;  1 = u, v;  2 = T, S
@@ -1145,6 +1149,76 @@ inline bool tendencies_split(const gb25_model* m) {
          interior_tile_columns_end(m->g) > 1 && !m->g.cv.north_fold && m->Ry == 1;   // (the rows beyond a fold / of a neighbour in y arrive last)
 }
 
+// ---- which template instance of a tendency kernel runs.  A family's flags are in the order of the kernel's template
+// parameters; pick_instance turns their values into the instance and instantiates only the variants the family's rule admits
+// (the rule is also the kernel's static_assert: tendency_kernels.hpp).  A state no variant exists for is an error.
+template <class Fam, bool... B>
+typename Fam::kernel_t pick_instance(const std::array<bool, Fam::n>& f) {
+  if constexpr (sizeof...(B) < Fam::n)
+    return f[sizeof...(B)] ? pick_instance<Fam, B..., true>(f) : pick_instance<Fam, B..., false>(f);
+  else if constexpr (Fam::admits(B...))
+    return Fam::template instance<B...>();
+  else
+    return nullptr;
+}
+template <class Fam>
+gb25_status tendency_instance(gb25_model* m, const std::array<bool, Fam::n>& f, typename Fam::kernel_t* k) {
+  if ((*k = pick_instance<Fam>(f))) return GB25_OK;
+  std::string bits;
+  for (bool b : f) bits += b ? '1' : '0';
+  return fail(m, GB25_ERR_STATE, "the %s kernel has no variant for the flags %s", Fam::name, bits.c_str());
+}
+
+struct MomentumKernels {   // k_momentum_tendencies_v5
+  // waves/SIMD the register allocator is held to: 4 (128 VGPRs) in fp32; fp64 operands are register pairs,
+  // so the Float64 build asks for 2 (256 VGPRs) instead of spilling.  TYm: rows (= waves) per block: 4 blocks per CU cover
+  // each other's barriers
+  static constexpr int MW = sizeof(real) == 8 ? 2 : 4, TYm = 4, n = 6;
+  static constexpr const char* name = "momentum (AHEAD IMM CURV LAZY DRAG WFLY)";
+  using kernel_t = decltype(&k_momentum_tendencies_v5<MW, TYm, false, false>);
+  static constexpr bool admits(bool a, bool i, bool c, bool l, bool d, bool w) { return momentum_variant(a, i, c, l, d, w); }
+  template <bool... B> static kernel_t instance() { return k_momentum_tendencies_v5<MW, TYm, B...>; }
+};
+// part: see momentum_impl.  WFLY: w on the fly in a lazy step, or beside the corrector's sweep (memory holds the corrected
+// velocities, only w is not read) -- in the passes over the whole domain
+std::array<bool, MomentumKernels::n> momentum_flags(const gb25_model* m, int part) {
+  const bool ahead = m->ab2_ahead == 1 && !m->ptr_exposed, curv = m->g.cv.on;
+  return {ahead, m->immersed || curv, curv, m->uv_lazy, m->bottom_drag != 0, ahead && m->w_fly_now && (m->uv_lazy || part == 0)};
+}
+
+struct TracerKernels {   // k_tracer_tendencies_v5; the flag O7: ORD = 7 (WENO(order = 7)), else 5
+  static constexpr int TW = sizeof(real) == 8 ? 3 : 6;    // see MomentumKernels::MW (Float32: held to 80 VGPRs, six waves per SIMD)
+  static constexpr int TW7 = sizeof(real) == 8 ? 2 : 5;   // (the order-7 windows: 9 register pairs per direction; 90-96 VGPRs without a spill)
+  static constexpr int n = 8;
+  static constexpr const char* name = "tracer (AHEAD IMM FOLD CURV LAZY O7 WFLY WCORR)";
+  using kernel_t = decltype(&k_tracer_tendencies_v5<TW, false, false, false>);
+  static constexpr bool admits(bool a, bool i, bool f, bool c, bool l, bool o7, bool w, bool wc) {
+    return tracer_variant(a, i, f, c, l, o7 ? 7 : 5, w, wc);
+  }
+  template <bool A, bool I, bool F, bool C, bool L, bool O7, bool W, bool WC>
+  static kernel_t instance() { return k_tracer_tendencies_v5<O7 ? TW7 : TW, A, I, F, C, L, O7 ? 7 : 5, W, WC>; }
+};
+// WCORR: the corrector through the tracer kernel -- it adds du, dv as it loads (LAZY) and writes the corrected u, v; the halo
+// cells of the next T, S are then left to the fill (no FOLD)
+std::array<bool, TracerKernels::n> tracer_flags(const gb25_model* m) {
+  const bool ahead = m->ab2_ahead && !m->ptr_exposed, curv = m->g.cv.on, wcorr = m->uv_corr_pending;
+  return {ahead, m->immersed || curv, ahead && producers_fold(m) && !wcorr, curv, m->uv_lazy || wcorr, m->tracer_order == 7,
+          ahead && m->w_fly_now, wcorr};
+}
+
+struct SingleKernels {   // k_tracer_tendencies_single (CATKE's e); O7 as in TracerKernels
+  static constexpr int TW = sizeof(real) == 8 ? 2 : 4, n = 4;
+  static constexpr const char* name = "one-tracer (IMM CURV O7 WFLY)";
+  using kernel_t = decltype(&k_tracer_tendencies_single<TW, false, false, 5>);
+  static constexpr bool admits(bool i, bool c, bool o7, bool w) { return single_variant(i, c, o7 ? 7 : 5, w); }
+  template <bool I, bool C, bool O7, bool W> static kernel_t instance() { return k_tracer_tendencies_single<TW, I, C, O7 ? 7 : 5, W>; }
+};
+// (WFLY: the field w is stale, the kernel carries w up its chunks like the two others)
+std::array<bool, SingleKernels::n> single_flags(const gb25_model* m) {
+  const bool curv = m->g.cv.on;
+  return {m->immersed || curv, curv, m->tracer_order == 7, m->w_fly_now};
+}
+
 // part: 0 = every tile column; 1 = the interior tile columns (a12: launched before the x-halo bundle has arrived);
 //       2 = the edge tile columns, then whatever follows the complete evaluation (the look-ahead's finish kernel).
 gb25_status materialize_prev_uv(gb25_model* m);
@@ -1156,7 +1230,7 @@ gb25_status momentum_impl(gb25_model* m, int part = 0) {
   if (m->kernel_gen >= 2) {
     Timed t(m, GB25_K_GU);   // the fused G_u + G_v kernel is accounted under the "gu" timer
     nbx = (g.Nx + V2_TX - 1) / V2_TX;
-    constexpr int TYm = 4;   // rows (= waves) per block: 4 blocks per CU cover each other's barriers
+    constexpr int TYm = MomentumKernels::TYm;
     const int nby = (v_rows(g) + TYm - 1) / TYm;   // (zipper fold: the y faces on the fold line have a tendency too)
     const int kchunks = mom_kchunks(m);
     TileCols tc{nbx, nbx, 0, 0};
@@ -1167,10 +1241,8 @@ gb25_status momentum_impl(gb25_model* m, int part = 0) {
     }
     tc.cr = ChunkRange{0, kchunks, 0};
     nb = tc.n * nby * kchunks;
-    // waves/SIMD the register allocator is held to: 4 (128 VGPRs) in fp32; fp64 operands are register pairs,
-    // so the Float64 build asks for 2 (256 VGPRs) instead of spilling
-    constexpr int MW = sizeof(real) == 8 ? 2 : 4;
-    const bool ahead = m->ab2_ahead == 1 && !m->ptr_exposed;
+    const std::array<bool, MomentumKernels::n> flags = momentum_flags(m, part);
+    const bool ahead = flags[0];
     UvAhead nx{};
     const real dt = (real)m->last_dt, chi = (real)m->cfg.chi;
     if (ahead && m->prev_uv_src == 2)   // (the partner buffers still hold CATKE's previous velocities: a caller of the single phases)
@@ -1194,25 +1266,10 @@ gb25_status momentum_impl(gb25_model* m, int part = 0) {
     }
     const LazyCorr lz{m->corr[0].d, m->corr[1].d, m->wbase, m->g.sx * m->g.sy_v};
     // (single domain: the kernel also writes the halo images of the next u, v; a slab's come with the next bundle)
-    if (m->uv_lazy && !(ahead && (m->slab || (nx.fold && part == 0))))
+    if (m->uv_lazy && !(m->slab || (nx.fold && part == 0)))
       return fail(m, GB25_ERR_STATE, "internal: uncorrected velocities in a step whose momentum kernel cannot correct them");
-    const bool drag = m->bottom_drag != 0;
-    const bool fly_sweep = ahead && m->w_fly_now && part == 0 && !m->uv_lazy;   // (w on the fly beside the corrector's sweep)
-    auto k5 = (drag && fly_sweep) ? (g.cv.on ? k_momentum_tendencies_v5<MW, TYm, true, true, true, false, true, true>
-                                     : m->immersed ? k_momentum_tendencies_v5<MW, TYm, true, true, false, false, true, true>
-                                                   : k_momentum_tendencies_v5<MW, TYm, true, false, false, false, true, true>)
-              : drag ? (g.cv.on ? (ahead ? k_momentum_tendencies_v5<MW, TYm, true, true, true, false, true> : k_momentum_tendencies_v5<MW, TYm, false, true, true, false, true>)
-                      : m->immersed ? (ahead ? k_momentum_tendencies_v5<MW, TYm, true, true, false, false, true> : k_momentum_tendencies_v5<MW, TYm, false, true, false, false, true>)
-                                    : (ahead ? k_momentum_tendencies_v5<MW, TYm, true, false, false, false, true> : k_momentum_tendencies_v5<MW, TYm, false, false, false, false, true>))
-              : (m->uv_lazy && ahead && m->w_fly_now) ? k_momentum_tendencies_v5<MW, TYm, true, false, false, true, false, true>
-              : (m->uv_lazy && ahead) ? k_momentum_tendencies_v5<MW, TYm, true, false, false, true>
-              // (w on the fly beside the corrector's sweep: memory holds the corrected velocities, only w is not read)
-              : (ahead && m->w_fly_now && part == 0) ? (g.cv.on ? k_momentum_tendencies_v5<MW, TYm, true, true, true, false, false, true>
-                                                        : m->immersed ? k_momentum_tendencies_v5<MW, TYm, true, true, false, false, false, true>
-                                                                      : k_momentum_tendencies_v5<MW, TYm, true, false, false, false, false, true>)
-              : g.cv.on ? (ahead ? k_momentum_tendencies_v5<MW, TYm, true, true, true> : k_momentum_tendencies_v5<MW, TYm, false, true, true>)
-              : m->immersed ? (ahead ? k_momentum_tendencies_v5<MW, TYm, true, true> : k_momentum_tendencies_v5<MW, TYm, false, true>)
-                            : (ahead ? k_momentum_tendencies_v5<MW, TYm, true, false> : k_momentum_tendencies_v5<MW, TYm, false, false>);
+    MomentumKernels::kernel_t k5;
+    if (gb25_status s_ = tendency_instance<MomentumKernels>(m, flags, &k5)) return s_;
     if (nb > 0) {
       // The kernel's per-lane offsets are 32-bit BYTE offsets from the array pointers.  An array beyond that reach (4.4 GB per
       // field for config 5 as one domain) takes several launches, each a run of chunks of levels whose planes -- stencil and
@@ -1274,10 +1331,10 @@ gb25_status tracers_impl(gb25_model* m) {
     Timed t(m, GB25_K_TRACERS);
     nbx = (g.Nx + V3_OUT - 1) / V3_OUT;
     const int nby = (g.Ny + 3) / 4;
-    const int kchunks = std::max(1, g.Nz / m->trc_chunk_levels);   // >= 12 levels per block: the z-carry start-up stays ~3 %
+    const int kchunks = trc_kchunks(m);
     nb = nbx * nby * kchunks;
-    constexpr int TW = sizeof(real) == 8 ? 3 : 6;   // see MW in momentum_impl (Float32: held to 80 VGPRs, six waves per SIMD)
-    const bool ahead = m->ab2_ahead && !m->ptr_exposed;
+    const std::array<bool, TracerKernels::n> flags = tracer_flags(m);
+    const bool ahead = flags[0], fold = flags[2];
     Ab2Ahead nx{};
     if (ahead) {   // predicted parameters of the next ab2_step!: the clock's dt and the model's chi
       nx.GmT = m->f[GB25_GM_T].d; nx.GmS = m->f[GB25_GM_S].d;
@@ -1285,43 +1342,17 @@ gb25_status tracers_impl(gb25_model* m) {
       nx.dt = (real)m->last_dt;
       nx.C1 = real(1.5) + (real)m->cfg.chi; nx.C2 = real(0.5) + (real)m->cfg.chi;
     }
-    const bool fold = ahead && producers_fold(m);
     const LazyCorr lz{m->corr[0].d, m->corr[1].d, m->wbase, m->g.sx * m->g.sy_v};
-    if (m->uv_lazy && !(ahead && (fold || m->slab)))
+    if (m->uv_lazy && !(fold || m->slab))
       return fail(m, GB25_ERR_STATE, "internal: uncorrected velocities in a step whose tracer kernel cannot correct them");
-    constexpr int TWL = sizeof(real) == 8 ? 3 : 6;   // (the headline instance: held to 80 VGPRs, six waves per SIMD)
-    constexpr int TW7 = sizeof(real) == 8 ? 2 : 5;   // (the order-7 windows: 9 register pairs per direction; 90-96 VGPRs without a spill)
-    auto kern = (m->tracer_order == 7 && ahead && m->w_fly_now)   // (w on the fly beside the corrector's sweep, WENO(order = 7))
-                    ? (g.cv.on ? k_tracer_tendencies_v5<TW7, true, true, false, true, false, 7, true>
-                       : m->immersed ? k_tracer_tendencies_v5<TW7, true, true, false, false, false, 7, true>
-                                     : k_tracer_tendencies_v5<TW7, true, false, false, false, false, 7, true>)
-                : m->tracer_order == 7
-                    ? (g.cv.on ? (ahead ? k_tracer_tendencies_v5<TW7, true, true, false, true, false, 7> : k_tracer_tendencies_v5<TW7, false, true, false, true, false, 7>)
-                       : m->immersed ? (ahead ? k_tracer_tendencies_v5<TW7, true, true, false, false, false, 7> : k_tracer_tendencies_v5<TW7, false, true, false, false, false, 7>)
-                                     : (ahead ? k_tracer_tendencies_v5<TW7, true, false, false, false, false, 7> : k_tracer_tendencies_v5<TW7, false, false, false, false, false, 7>))
-                : (m->uv_lazy && ahead && fold && m->w_fly_now) ? k_tracer_tendencies_v5<TWL, true, false, true, false, true, 5, true>
-                : (m->uv_lazy && ahead && fold) ? k_tracer_tendencies_v5<TWL, true, false, true, false, true>
-                : (m->uv_lazy && ahead && m->w_fly_now) ? k_tracer_tendencies_v5<TWL, true, false, false, false, true, 5, true>   // (slab)
-                : (m->uv_lazy && ahead) ? k_tracer_tendencies_v5<TWL, true, false, false, false, true>
-                // (the corrector through the tracer kernel: adds du, dv as it loads, writes the corrected u, v; w on the fly)
-                : (ahead && m->w_fly_now && m->uv_corr_pending) ? (g.cv.on ? k_tracer_tendencies_v5<TW, true, true, false, true, true, 5, true, true>
-                                                                            : k_tracer_tendencies_v5<TW, true, true, false, false, true, 5, true, true>)
-                // (w on the fly beside the corrector's sweep)
-                : (ahead && m->w_fly_now) ? (g.cv.on ? (fold ? k_tracer_tendencies_v5<TW, true, true, true, true, false, 5, true> : k_tracer_tendencies_v5<TW, true, true, false, true, false, 5, true>)
-                                             : m->immersed ? (fold ? k_tracer_tendencies_v5<TW, true, true, true, false, false, 5, true> : k_tracer_tendencies_v5<TW, true, true, false, false, false, 5, true>)
-                                                           : (fold ? k_tracer_tendencies_v5<TW, true, false, true, false, false, 5, true> : k_tracer_tendencies_v5<TW, true, false, false, false, false, 5, true>))
-                : g.cv.on ? (ahead ? (fold ? k_tracer_tendencies_v5<TW, true, true, true, true> : k_tracer_tendencies_v5<TW, true, true, false, true>)
-                                 : k_tracer_tendencies_v5<TW, false, true, false, true>)
-                : m->immersed ? (ahead ? (fold ? k_tracer_tendencies_v5<TW, true, true, true> : k_tracer_tendencies_v5<TW, true, true, false>)
-                                     : k_tracer_tendencies_v5<TW, false, true, false>)
-                            : (ahead ? (fold ? k_tracer_tendencies_v5<TW, true, false, true> : k_tracer_tendencies_v5<TW, true, false, false>)
-                                     : k_tracer_tendencies_v5<TW, false, false, false>);
+    TracerKernels::kernel_t kern;
+    if (gb25_status s_ = tendency_instance<TracerKernels>(m, flags, &kern)) return s_;
     if (m->uv_corr_pending) {
-      if (!(ahead && m->w_fly_now && m->tracer_order == 5 && m->uvc[0].d)) return fail(m, GB25_ERR_STATE, "internal: no tracer kernel instance writes the corrected velocities here");
+      if (!m->uvc[0].d) return fail(m, GB25_ERR_STATE, "internal: the corrected velocities have no arrays");
       nx.uc = m->uvc[0].d;
       nx.vc = m->uvc[1].d;
     }
-    m->ahead_ts_folded = fold && !m->uv_corr_pending;
+    m->ahead_ts_folded = fold;
     hipLaunchKernelGGL(kern, dim3(nb), dim3(64, 4), 0, m->stream, g, m->f[GB25_U].d,
                        m->f[GB25_V].d, m->f[GB25_W].d, m->f[GB25_T].d, m->f[GB25_S].d, m->f[GB25_GN_T].d,
                        m->f[GB25_GN_S].d, nbx, kchunks, nb, nx, lz);
@@ -1752,6 +1783,30 @@ gb25_status barotropic_impl(gb25_model* m, real dt, bool ahead = false, const In
   return GB25_OK;
 }
 
+// cache_previous_tendencies!: G^- <- G^n is a pointer exchange; the next tendency evaluation overwrites the (old G^-) buffers
+// that now carry the G^n name.  (closure = CATKE: G^-.e is written by the e step itself -- cache_previous_tendencies! skips e)
+void cache_previous_tendencies(gb25_model* m) {
+  for (int q = 0; q < 4; q++) std::swap(m->f[GB25_GN_U + q].d, m->f[GB25_GM_U + q].d);
+  m->ahead_valid = m->ahead_uv_valid = m->ahead_baro_valid = false;   // the look-aheads used the tendency pairs as they were before
+}
+// the corrector inside its consumers: du, dv (k_corrector_2d) on columns i0 + [0, ni) (from skip_from on: + skip), rows jr0 + [0, nj)
+gb25_status corrector_2d_impl(gb25_model* m, dim3 b, int i0, int ni, int skip_from, int skip, int jr0, int nj) {
+  hipLaunchKernelGGL(m->immersed ? k_corrector_2d<true> : k_corrector_2d<false>, grid2(ni, nj, b), b, 0, m->stream, m->g,
+                     m->f[GB25_BT_U].d, m->f[GB25_BT_V].d, m->colsum[0].d, m->colsum[1].d, m->f[GB25_U_BAR].d, m->f[GB25_V_BAR].d,
+                     m->corr[0].d, m->corr[1].d, i0, ni, skip_from, skip, jr0, nj);
+  LAUNCHCHK();
+  return GB25_OK;
+}
+// w on the fly: w at the chunk boundaries (k_w_bases) on columns i0 + [0, ni) (from skip_from on: + skip), rows -2 .. Ny + 1
+gb25_status w_bases_impl(gb25_model* m, dim3 b, int i0, int ni, int skip_from, int skip) {
+  const Grid& g = m->g;
+  auto kb = g.cv.on ? k_w_bases<true, true> : (m->immersed ? k_w_bases<true, false> : k_w_bases<false, false>);
+  hipLaunchKernelGGL(kb, grid2(ni, g.Ny + 4, b), b, 0, m->stream, g, m->uv_partials, mom_kchunks(m), g.sx * g.sy_v,
+                     LazyCorr{m->corr[0].d, m->corr[1].d, nullptr, 0}, m->wbase, i0, ni, skip_from, skip);
+  LAUNCHCHK();
+  return GB25_OK;
+}
+
 // use_colsum: only inside a composite time step, where nothing can have touched u, v since the AB2 kernel.
 // part: 0 = every column this model corrects (a slab of a decomposition includes its x-halo columns);
 //       1 = the slab's own columns only (needs no halo data: runs while the last exchanges are in flight);
@@ -1798,11 +1853,7 @@ gb25_status corrector_impl(gb25_model* m, bool use_colsum = false, int part = 0)
   }
   if (part == 2) return GB25_OK;
   m->colsum_valid = false;
-  // cache_previous_tendencies!: G^- <- G^n is a pointer exchange; the next tendency evaluation
-  // overwrites the (old G^-) buffers that now carry the G^n name.
-  for (int q = 0; q < 4; q++) std::swap(m->f[GB25_GN_U + q].d, m->f[GB25_GM_U + q].d);
-  // (closure = CATKE: G^-.e is written by the e step itself -- cache_previous_tendencies! skips e)
-  m->ahead_valid = m->ahead_uv_valid = m->ahead_baro_valid = false;   // the look-aheads used the tendency pairs as they were before
+  cache_previous_tendencies(m);
   return GB25_OK;
 }
 
@@ -1938,25 +1989,10 @@ gb25_status catke_tendency_impl(gb25_model* m) {
   Timed t_closure(m, GB25_K_CLOSURE);
   const Grid& g = m->g;
   {
-    const int nbx = (g.Nx + V3_PAIR - 1) / V3_PAIR, nby = (g.Ny + 3) / 4, kchunks = std::max(1, g.Nz / m->trc_chunk_levels);
+    const int nbx = (g.Nx + V3_PAIR - 1) / V3_PAIR, nby = (g.Ny + 3) / 4, kchunks = trc_kchunks(m);
     const int nb = nbx * nby * kchunks;
-    constexpr int TW = sizeof(real) == 8 ? 2 : 4;
-    const bool fly = m->w_fly_now;   // (w on the fly: the field w is stale, the kernel carries w up its chunks like the two others)
-    void (*kt)(Grid, const real*, const real*, const real*, const real*, real*, int, int, int, LazyCorr) =
-        (m->tracer_order == 7 && fly)
-            ? (g.cv.on       ? k_tracer_tendencies_single<TW, true, true, 7, true>
-               : m->immersed ? k_tracer_tendencies_single<TW, true, false, 7, true>
-                             : k_tracer_tendencies_single<TW, false, false, 7, true>)
-        : m->tracer_order == 7
-            ? (g.cv.on       ? k_tracer_tendencies_single<TW, true, true, 7>
-               : m->immersed ? k_tracer_tendencies_single<TW, true, false, 7>
-                             : k_tracer_tendencies_single<TW, false, false, 7>)
-        : fly ? (g.cv.on       ? k_tracer_tendencies_single<TW, true, true, 5, true>
-                 : m->immersed ? k_tracer_tendencies_single<TW, true, false, 5, true>
-                               : k_tracer_tendencies_single<TW, false, false, 5, true>)
-        : g.cv.on       ? k_tracer_tendencies_single<TW, true, true, 5>
-        : m->immersed ? k_tracer_tendencies_single<TW, true, false, 5>
-                      : k_tracer_tendencies_single<TW, false, false, 5>;
+    SingleKernels::kernel_t kt;
+    if (gb25_status s_ = tendency_instance<SingleKernels>(m, single_flags(m), &kt)) return s_;
     const LazyCorr lz{m->corr[0].d, m->corr[1].d, m->wbase, g.sx * g.sy_v};
     hipLaunchKernelGGL(kt, dim3(nb), dim3(64, 4), 0, m->stream, g, m->f[GB25_U].d, m->f[GB25_V].d, m->f[GB25_W].d, m->f[GB25_E].d,
                        m->f[GB25_GN_E].d, nbx, kchunks, nb, lz);
@@ -2093,12 +2129,16 @@ gb25_status materialize_uv(gb25_model* m, bool need_w = true) {
   }
   return GB25_OK;
 }
-// may this step leave u, v uncorrected in memory?  Flat lat-lon single domain, both look-aheads on and able to write
-// their halos, the default kernels; `more`: the step is one of a composite call (gb25_loop), which materialises u, v, w when it returns
-inline bool lazy_corrector_ok(const gb25_model* m) {
-  return m->lazy_corrector && !m->coupled && m->bottom_drag == 0 && m->tracer_order == 5 && m->two_streams && producers_fold(m) && !m->immersed && !m->g.cv.on && m->kernel_gen >= 2 &&
-         m->ab2_ahead == 1 && !m->ptr_exposed && m->pressure_bits == 64;
+// may this step leave u, v uncorrected in memory?  The flat lat-lon grid (the LAZY instances of the tendency kernels), both
+// look-aheads on, the default kernels, no bottom drag, WENO(order = 5) -- on a single domain (lazy_corrector_ok) or a slab
+// (slab_lazy_ok, below)
+inline bool lazy_instances_ok(const gb25_model* m) {
+  return m->lazy_corrector && !m->coupled && m->bottom_drag == 0 && m->tracer_order == 5 && m->two_streams && !m->immersed &&
+         !m->g.cv.on && m->kernel_gen >= 2 && m->ab2_ahead == 1 && !m->ptr_exposed && m->pressure_bits == 64;
 }
+// ... a single domain: the look-aheads able to write their halos; `more` (time_step_impl): the step is one of a composite call
+// (gb25_loop), which materialises u, v, w when it returns
+inline bool lazy_corrector_ok(const gb25_model* m) { return lazy_instances_ok(m) && producers_fold(m); }
 
 // w on the fly beside the corrector's SWEEP (round 4): the grids the corrector-inside-its-consumers instances do not exist for --
 // a GridFittedBottom, the curvilinear grids, the zipper fold -- still drop the k_compute_w launch: the sweep leaves du, dv of the
@@ -2115,7 +2155,7 @@ inline bool wfly_sweep_ok(const gb25_model* m) {
          m->ab2_ahead == 1 && !m->ptr_exposed && m->nu == 0 && m->kappa == 0 &&
          // (closure = CATKE: the implicit solve of u, v that follows the AB2 update rewrites the look-ahead's chunk sums with
          // those of the velocities it leaves: catke_implicit_impl, ImplicitVarFields::P; e is advected by a kernel that carries w too)
-         std::max(1, m->g.Nz / m->trc_chunk_levels) == mom_kchunks(m);
+         chunkings_match(m);
 }
 
 inline bool lazy_through_tracers_ok(const gb25_model* m) {
@@ -2126,15 +2166,8 @@ inline bool lazy_through_tracers_ok(const gb25_model* m) {
 
 // ... and a slab of an x decomposition or a rank of a 2-D one: the same kernels without the halo images (its halos come with the
 // bundles, and with them the neighbours' column integrals: du, dv of the halo columns / rows are computed locally)
-inline bool slab_lazy_ok(const gb25_model* m) {
-  return m->slab && m->lazy_corrector && !m->coupled && m->bottom_drag == 0 && m->tracer_order == 5 && m->two_streams &&
-         !m->immersed && !m->g.cv.on && m->kernel_gen >= 2 && m->ab2_ahead == 1 && !m->ptr_exposed && m->pressure_bits == 64 &&
-         m->nu == 0 && m->kappa == 0 && !m->catke;
-}
-
-inline bool slab_wfly_ok(const gb25_model* m) {   // (the chunkings of the two tendency kernels must be the one the chunk sums were made with)
-  return slab_lazy_ok(m) && m->w_fly && std::max(1, m->g.Nz / m->trc_chunk_levels) == mom_kchunks(m);
-}
+inline bool slab_lazy_ok(const gb25_model* m) { return m->slab && lazy_instances_ok(m) && m->nu == 0 && m->kappa == 0 && !m->catke; }
+inline bool slab_wfly_ok(const gb25_model* m) { return slab_lazy_ok(m) && m->w_fly && chunkings_match(m); }
 
 // One time step on a single slab.  Two HIP streams: the tracer branch (AB2 of T,S -> their halos -> hydrostatic
 // pressure: HBM- then fp64-bound) is independent of the velocity branch (AB2 of u,v -> split-explicit sub-cycle,
@@ -2230,22 +2263,15 @@ gb25_status time_step_impl(gb25_model* m, int euler, bool more = false) {
     const Grid& g = m->g;
     dim3 b(64, 4);
     Timed t(m, GB25_K_CORRECTOR);
-    hipLaunchKernelGGL(k_corrector_2d<false>, grid2(g.Nx, g.Ny + 1, b), b, 0, main, g, m->f[GB25_BT_U].d, m->f[GB25_BT_V].d,
-                       m->colsum[0].d, m->colsum[1].d, m->f[GB25_U_BAR].d, m->f[GB25_V_BAR].d, m->corr[0].d, m->corr[1].d,
-                       0, g.Nx, INT_MAX, 0, 0, g.Ny + 1);
-    LAUNCHCHK();
+    if ((s = corrector_2d_impl(m, b, 0, g.Nx, INT_MAX, 0, 0, g.Ny + 1))) return s;
     m->uv_lazy = true;
     m->colsum_valid = false;
-    // w on the fly: the chunkings of the two tendency kernels must be the one the partial sums were made with
-    m->w_fly_now = m->w_fly && std::max(1, g.Nz / m->trc_chunk_levels) == mom_kchunks(m);
+    m->w_fly_now = m->w_fly && chunkings_match(m);
     if (m->w_fly_now) {
-      hipLaunchKernelGGL((k_w_bases<false, false>), grid2(g.Nx + 4, g.Ny + 4, b), b, 0, main, g, m->uv_partials, mom_kchunks(m), g.sx * g.sy_v,
-                         LazyCorr{m->corr[0].d, m->corr[1].d, nullptr, 0}, m->wbase, -2, g.Nx + 4, INT_MAX, 0);
-      LAUNCHCHK();
+      if ((s = w_bases_impl(m, b, -2, g.Nx + 4, INT_MAX, 0))) return s;
       m->w_stale = true;
     }
-    for (int q = 0; q < 4; q++) std::swap(m->f[GB25_GN_U + q].d, m->f[GB25_GM_U + q].d);   // cache_previous_tendencies!
-    m->ahead_valid = m->ahead_uv_valid = m->ahead_baro_valid = false;
+    cache_previous_tendencies(m);
   } else if (lazy_t) {
     const Grid& g = m->g;
     dim3 b(64, 4);
@@ -2253,10 +2279,7 @@ gb25_status time_step_impl(gb25_model* m, int euler, bool more = false) {
     for (int q = 0; q < 2; q++)
       if (!m->uvc[q].d && (s = alloc_field(m, m->uvc[q], m->f[GB25_U + q].nx, m->f[GB25_U + q].ny, m->f[GB25_U + q].nz))) return s;
     // du, dv on the own faces (rows of y faces: [0, Ny) on a folded grid, [0, Ny] below a wall) ...
-    hipLaunchKernelGGL(m->immersed ? k_corrector_2d<true> : k_corrector_2d<false>, grid2(g.Nx, g.Ny + (g.cv.north_fold ? 0 : 1), b), b, 0, main, g,
-                       m->f[GB25_BT_U].d, m->f[GB25_BT_V].d, m->colsum[0].d, m->colsum[1].d, m->f[GB25_U_BAR].d, m->f[GB25_V_BAR].d,
-                       m->corr[0].d, m->corr[1].d, 0, g.Nx, INT_MAX, 0, 0, g.Ny + (g.cv.north_fold ? 0 : 1));
-    LAUNCHCHK();
+    if ((s = corrector_2d_impl(m, b, 0, g.Nx, INT_MAX, 0, 0, g.Ny + (g.cv.north_fold ? 0 : 1)))) return s;
     // ... and their halo cells as the fills derive them (the rows beyond a zipper fold: images with the sign of a vector component)
     if (g.cv.north_fold) {
       Halo2 hc{};
@@ -2267,21 +2290,14 @@ gb25_status time_step_impl(gb25_model* m, int euler, bool more = false) {
     }
     m->colsum_valid = false;
     m->w_fly_now = true;
-    {
-      const LazyCorr lc{m->corr[0].d, m->corr[1].d, nullptr, 0};
-      auto kb = g.cv.on ? k_w_bases<true, true> : (m->immersed ? k_w_bases<true, false> : k_w_bases<false, false>);
-      hipLaunchKernelGGL(kb, grid2(g.Nx + 4, g.Ny + 4, b), b, 0, main, g, m->uv_partials, mom_kchunks(m), g.sx * g.sy_v, lc,
-                         m->wbase, -2, g.Nx + 4, INT_MAX, 0);
-      LAUNCHCHK();
-    }
+    if ((s = w_bases_impl(m, b, -2, g.Nx + 4, INT_MAX, 0))) return s;
     m->w_stale = true;
     m->uv_corr_pending = true;
     // (the two strips of halo cells of the uncorrected u, v the tracer kernel reads: k_uncorrected_edges)
     hipLaunchKernelGGL(k_uncorrected_edges, dim3((std::max(g.Nx, g.Ny) + 255) / 256, g.Nz, g.cv.north_fold ? 3 : 2), dim3(256), 0, main, g,
                        m->f[GB25_U].d, m->f[GB25_V].d);
     LAUNCHCHK();
-    for (int q = 0; q < 4; q++) std::swap(m->f[GB25_GN_U + q].d, m->f[GB25_GM_U + q].d);   // cache_previous_tendencies!
-    m->ahead_valid = m->ahead_uv_valid = m->ahead_baro_valid = false;
+    cache_previous_tendencies(m);
   } else {
     m->corr_out = wfly_sweep;      // (the sweep leaves du, dv of the own columns behind for k_w_bases)
     s = corrector_impl(m, true);
@@ -2289,13 +2305,7 @@ gb25_status time_step_impl(gb25_model* m, int euler, bool more = false) {
     if (s) return s;
     m->w_fly_now = wfly_sweep;
     if (wfly_sweep) {
-      const Grid& g = m->g;
-      dim3 b(64, 4);
-      const LazyCorr lc{m->corr[0].d, m->corr[1].d, nullptr, 0};
-      auto kb = g.cv.on ? k_w_bases<true, true> : (m->immersed ? k_w_bases<true, false> : k_w_bases<false, false>);
-      hipLaunchKernelGGL(kb, grid2(g.Nx + 4, g.Ny + 4, b), b, 0, main, g, m->uv_partials, mom_kchunks(m), g.sx * g.sy_v, lc,
-                         m->wbase, -2, g.Nx + 4, INT_MAX, 0);
-      LAUNCHCHK();
+      if ((s = w_bases_impl(m, dim3(64, 4), -2, m->g.Nx + 4, INT_MAX, 0))) return s;
       m->w_stale = true;
     }
   }

@@ -418,23 +418,16 @@ gb25_status slab_stage(gb25_model* m, int stage, int euler) {
       Timed t(m, GB25_K_CORRECTOR);
       // (a rank of a 2-D decomposition has no interior pass: du, dv and the chunk bases of w over its whole extended range at
       // once, in stage 3, when every halo is in)
-      if (m->Ry == 1)
-        hipLaunchKernelGGL(k_corrector_2d<false>, grid2(g.Nx, g.Ny + 1, b), b, 0, m->stream, g, m->f[GB25_BT_U].d, m->f[GB25_BT_V].d,
-                           m->colsum[0].d, m->colsum[1].d, m->f[GB25_U_BAR].d, m->f[GB25_V_BAR].d, m->corr[0].d, m->corr[1].d,
-                           0, g.Nx, INT_MAX, 0, 0, g.Ny + 1);
-      LAUNCHCHK();
+      if (m->Ry == 1 && (s = corrector_2d_impl(m, b, 0, g.Nx, INT_MAX, 0, 0, g.Ny + 1))) return s;
       m->uv_lazy = true;
       if (m->Ry == 1) m->colsum_valid = false;
       if (m->w_fly_now && m->Ry == 1) {
         // chunk bases of w on the columns [0, Nx - 2] (their u faces are own columns), before the interior momentum pass
         // overwrites the chunk sums they are made from
-        hipLaunchKernelGGL((k_w_bases<false, false>), grid2(g.Nx - 1, g.Ny + 4, b), b, 0, m->stream, g, m->uv_partials, mom_kchunks(m), g.sx * g.sy_v,
-                           LazyCorr{m->corr[0].d, m->corr[1].d, nullptr, 0}, m->wbase, 0, g.Nx - 1, INT_MAX, 0);
-        LAUNCHCHK();
+        if ((s = w_bases_impl(m, b, 0, g.Nx - 1, INT_MAX, 0))) return s;
         m->w_stale = true;
       }
-      for (int q = 0; q < 4; q++) std::swap(m->f[GB25_GN_U + q].d, m->f[GB25_GM_U + q].d);   // cache_previous_tendencies!
-      m->ahead_valid = m->ahead_uv_valid = m->ahead_baro_valid = false;
+      cache_previous_tendencies(m);
     } else if ((s = corrector_impl(m, true, 1))) {
       return s;
     }
@@ -492,25 +485,18 @@ gb25_status slab_stage(gb25_model* m, int stage, int euler) {
           dim3 b(64, 4);
           // rows: from the southern halo rows (or row 0) to the last northern halo row of the cell-shaped arrays (or the wall face)
           const int hs = m->ys_open ? g.H : 0, nj = hs + g.Ny + (m->yn_open ? g.H : 1);
-          hipLaunchKernelGGL(k_corrector_2d<false>, grid2(g.Nx + 2 * g.H, nj, b), b, 0, m->stream, g, m->f[GB25_BT_U].d,
-                             m->f[GB25_BT_V].d, m->colsum[0].d, m->colsum[1].d, m->f[GB25_U_BAR].d, m->f[GB25_V_BAR].d, m->corr[0].d,
-                             m->corr[1].d, -g.H, g.Nx + 2 * g.H, INT_MAX, 0, -hs, nj);
+          if ((s = corrector_2d_impl(m, b, -g.H, g.Nx + 2 * g.H, INT_MAX, 0, -hs, nj))) return s;
           m->colsum_valid = false;
           if (m->w_fly_now) {
-            hipLaunchKernelGGL((k_w_bases<false, false>), grid2(g.Nx + 4, g.Ny + 4, b), b, 0, m->stream, g, m->uv_partials, mom_kchunks(m), g.sx * g.sy_v,
-                               LazyCorr{m->corr[0].d, m->corr[1].d, nullptr, 0}, m->wbase, -2, g.Nx + 4, INT_MAX, 0);
+            if ((s = w_bases_impl(m, b, -2, g.Nx + 4, INT_MAX, 0))) return s;
             m->w_stale = true;
           }
-          LAUNCHCHK();   // (the bottom / top layers of the halo rows, which arrived with their interior levels: the fill below)
+          // (the bottom / top layers of the halo rows, which arrived with their interior levels: the fill below)
         } else {
           dim3 b(16, 16);
-          hipLaunchKernelGGL(k_corrector_2d<false>, grid2(2 * g.H, g.Ny + 1, b), b, 0, m->stream, g, m->f[GB25_BT_U].d, m->f[GB25_BT_V].d,
-                             m->colsum[0].d, m->colsum[1].d, m->f[GB25_U_BAR].d, m->f[GB25_V_BAR].d, m->corr[0].d, m->corr[1].d,
-                             -g.H, 2 * g.H, 0, g.Nx, 0, g.Ny + 1);
-          if (m->w_fly_now)   // the chunk bases of w on the columns -2, -1 and Nx - 1, Nx, Nx + 1 (the w tiles reach two columns out)
-            hipLaunchKernelGGL((k_w_bases<false, false>), grid2(5, g.Ny + 4, b), b, 0, m->stream, g, m->uv_partials, mom_kchunks(m), g.sx * g.sy_v,
-                               LazyCorr{m->corr[0].d, m->corr[1].d, nullptr, 0}, m->wbase, -2, 5, 0, g.Nx - 1);
-          LAUNCHCHK();
+          if ((s = corrector_2d_impl(m, b, -g.H, 2 * g.H, 0, g.Nx, 0, g.Ny + 1))) return s;
+          // the chunk bases of w on the columns -2, -1 and Nx - 1, Nx, Nx + 1 (the w tiles reach two columns out)
+          if (m->w_fly_now && (s = w_bases_impl(m, b, -2, 5, 0, g.Nx - 1))) return s;
         }
       } else if (m->Ry == 1 && (s = corrector_impl(m, true, 2))) {   // (2-D decomposition: done in stage 32)
         return s;

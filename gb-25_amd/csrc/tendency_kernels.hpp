@@ -105,13 +105,16 @@ struct UvAhead {
 // level comes from lz.wbase (k_w_bases).  Saves the 4.6 B per cell of the w tile and, with the tracer kernel doing the same,
 // the whole k_compute_w launch of a step.  With or without LAZY (round 4: the grids with a bottom and the curvilinear ones keep the
 // corrector's sweep but not the w launch); CURV: the tile holds Az w, so Az w is what is carried: Az w(k+1) = Az w(k) - (DU + DV).
+// The variants that exist: the kernel's static_assert and the host's choice of instance (momentum_impl) both use this rule.
+constexpr bool momentum_variant(bool AHEAD, bool IMM, bool CURV, bool LAZY, bool DRAG, bool WFLY) {
+  return (!CURV || IMM) && (!WFLY || AHEAD) && (!LAZY || (AHEAD && !IMM && !DRAG));
+}
 template <int MINW, int V2_TY, bool AHEAD, bool IMM, bool CURV = false, bool LAZY = false, bool DRAG = false, bool WFLY = false>
 __global__ __launch_bounds__(V2_TX* V2_TY, MINW) void k_momentum_tendencies_v5(
     Grid g, const real* __restrict__ u, const real* __restrict__ v, const real* __restrict__ w,
     const real* __restrict__ dpx, const real* __restrict__ dpy, real* __restrict__ Gu, real* __restrict__ Gv,
     TileCols tc, int kchunks, int nb, UvAhead next, LazyCorr lz) {
-  static_assert(!CURV || IMM, "the curvilinear variant takes its orders from the tables");
-  static_assert(!LAZY || (!IMM && !CURV), "the corrector is applied inside its consumers on the flat lat-lon grid only");
+  static_assert(momentum_variant(AHEAD, IMM, CURV, LAZY, DRAG, WFLY), "no such variant of the momentum kernel");
   __shared__ MomentumLds<V2_TY> lds;
   __shared__ typename std::conditional<CURV, MomentumMetricLds<V2_TY>, NoLds>::type mt;
   __shared__ typename std::conditional<LAZY, MomentumCorrLds<V2_TY>, NoLds>::type cr;
@@ -709,6 +712,11 @@ struct Ab2Ahead {
 // WFLY: w is not read; Az w on the top face follows from the divergence of the transports the lane holds anyway --
 // Az w(k+1) = Az w(k) - [(Axu(i+1) - Axu(i)) + (Ayn - Ays)], the east face's transport from the next lane -- starting from
 // lz.wbase at the chunk's first level (k_w_bases).  Continuity and advection then see the very same transports.
+// The variants that exist: tracer_tile's static_assert and the host's choice of instance (tracers_impl) both use this rule.
+constexpr bool tracer_variant(bool AHEAD, bool IMM, bool FOLD, bool CURV, bool LAZY, int ORD, bool WFLY, bool WCORR) {
+  return (!CURV || IMM) && (!FOLD || AHEAD) && (!WFLY || AHEAD) && (ORD == 5 || (ORD == 7 && !FOLD && !LAZY && !WCORR)) &&
+         (!LAZY || (AHEAD && (!IMM || WCORR))) && (!WCORR || (LAZY && WFLY && IMM && !FOLD));
+}
 template <bool AHEAD, bool IMM, bool FOLD, bool CURV = false, bool LAZY = false, int ORD = 5, bool WFLY = false, bool WCORR = false>
 __device__ __forceinline__ void tracer_tile(const Grid& g, const real* __restrict__ u, const real* __restrict__ v,
                                             const real* __restrict__ w, const real* __restrict__ T,
@@ -723,12 +731,11 @@ __device__ __forceinline__ void tracer_tile(const Grid& g, const real* __restric
   if (j >= g.Ny) return;                       // whole wave (one row) leaves together: no barriers in this kernel
   const bool writes = (lane < V3_OUT) && (i < g.Nx);
   const int sx = g.sx, pc = g.pl_c, pv = g.pl_v;
-  static_assert(!CURV || IMM, "the curvilinear variant takes its orders from the tables");
+  static_assert(tracer_variant(AHEAD, IMM, FOLD, CURV, LAZY, ORD, WFLY, WCORR), "no such variant of the tracer kernel");
   const int om = i2(g, min(i, g.Nx), j);
   const real dy = CURV ? g.cv.dyfc[om] : g.dy, Az = CURV ? g.cv.azcc[om] : g.azc[j];
   const real dxf_s = CURV ? g.cv.dxcf[om] : g.dxf[j], dxf_n = CURV ? g.cv.dxcf[om + g.sx] : g.dxf[j + 1];
   const real razc_j = CURV ? g.cv.razcc[om] : g.razc[j];
-  static_assert(!WCORR || LAZY, "the corrected velocities are what the lazy loads form");
   real du_l = real(0.), dv_s = real(0.), dv_n = real(0.);
   // (with a bottom the correction acts from the face's first free level on: the faces below touch the solid and stay zero)
   int KPUl = 0, KPVs = 0, KPVn = 0;
@@ -742,7 +749,6 @@ __device__ __forceinline__ void tracer_tile(const Grid& g, const real* __restric
     }
   }
   constexpr int R = ORD == 7 ? 4 : 3;   // reach of the reconstruction stencils
-  static_assert(ORD == 5 || ORD == 7, "WENO(order = 5) or WENO(order = 7)");
   const int jw_ = j - g.jws, Nyw_ = g.jwn - g.jws;   // (rows counted from the global southern wall)
   int oys = ORD == 7 ? biased_order_face7(jw_, Nyw_) : biased_order_face(jw_, Nyw_);
   int oyn = ORD == 7 ? biased_order_face7(jw_ + 1, Nyw_) : biased_order_face(jw_ + 1, Nyw_), ox = ORD;
@@ -922,6 +928,8 @@ __global__ __launch_bounds__(256, MINW) void k_tracer_tendencies_v5(Grid g, cons
 // WFLY: w is not read (the field is stale in a step that carries w inside its tendency kernels): Az w of both columns from the
 // divergence of their transports, the east faces' from the next lane, starting from lz.wbase -- as tracer_tile does.
 constexpr int V3_PAIR = 2 * V3_OUT;   // outputs per wavefront
+// The variants that exist: tracer_tile_single's static_assert and the host's choice of instance (catke_tendency_impl) both use this rule.
+constexpr bool single_variant(bool IMM, bool CURV, int ORD, bool WFLY) { return (!CURV || IMM) && (ORD == 5 || ORD == 7); }
 template <bool IMM, bool CURV, int ORD, bool WFLY = false>
 __device__ __forceinline__ void tracer_tile_single(const Grid& g, const real* __restrict__ u, const real* __restrict__ v,
                                                    const real* __restrict__ w, const real* __restrict__ E,
@@ -938,7 +946,7 @@ __device__ __forceinline__ void tracer_tile_single(const Grid& g, const real* __
   const bool wr0 = (lane < V3_OUT) && (i0 < g.Nx), wr1 = (lane < V3_OUT) && (i1 < g.Nx);
   const int c0 = min(i0, g.Nx), c1 = min(i1, g.Nx);              // (lanes past the east edge work on a clamped column)
   const int sx = g.sx, pc = g.pl_c, pv = g.pl_v;
-  static_assert(!CURV || IMM, "the curvilinear variant takes its orders from the tables");
+  static_assert(single_variant(IMM, CURV, ORD, WFLY), "no such variant of the one-tracer kernel");
   const int om0 = i2(g, c0, j), om1 = i2(g, c1, j);
   auto m2 = [&](const real* tab, int d) { return v2(tab[om0 + d], tab[om1 + d]); };
   const real2v dy = CURV ? m2(g.cv.dyfc, 0) : real2v(g.dy), Az = CURV ? m2(g.cv.azcc, 0) : real2v(g.azc[j]);

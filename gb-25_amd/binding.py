@@ -27,11 +27,11 @@ FIELD_IDS = {
 }
 METRIC2_IDS = ["dxfc", "dxcc", "dxcf", "dxff", "dyfc", "dycc", "dycf", "dyff", "azcc", "azfc", "azcf", "azff", "fff", "phicc"]
 METRIC_IDS = {"phif": 0, "phic": 1, "dxc": 2, "dxf": 3, "azc": 4, "azf": 5, "fcor": 6,
-              "zf": 7, "zc": 8, "dzc": 9, "dzf": 10}
+              "zf": 7, "zc": 8, "dzc": 9, "dzf": 10, "dy": 11}
 ATMOSPHERE_IDS = {"u": 0, "v": 1, "T": 2, "q": 3, "p": 4, "shortwave": 5, "longwave": 6}
 KERNEL_IDS = {"fill_halos": 0, "compute_w": 1, "compute_p": 2, "gu": 3, "gv": 4, "tracers": 5,
               "ab2_velocities": 6, "ab2_tracers": 7, "barotropic": 8, "corrector": 9, "implicit": 10, "closure": 11,
-              "fluxes": 12}
+              "fluxes": 12, "diagnostics": 13}
 
 # every symbol include/gb25.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -54,6 +54,8 @@ ABI_SYMBOLS = [
     "gb25_comm_info", "gb25_debug_exchange_plan",
     "gb25_lookahead_state", "gb25_debug_sequence", "gb25_save_state",
     "gb25_profile_enable", "gb25_profile_reset", "gb25_profile_get",
+    "gb25_field_stats_bytes", "gb25_field_diff_bytes", "gb25_state_monitor_bytes", "gb25_get_field_stats", "gb25_compare_field",
+    "gb25_get_state_monitor", "gb25_field_device_ptr_readonly",
 ]
 # gb25_option (include/gb25.h)
 OPTION_IDS = {"kernels": 0, "ab2_lookahead": 1, "subcycle_lookahead": 2, "subcycle_block": 3, "fill_fused": 4,
@@ -92,6 +94,57 @@ class Config(C.Structure):
         ("g", C.c_double), ("Omega", C.c_double), ("radius", C.c_double), ("rho0", C.c_double),
         ("slab_mode", C.c_int32), ("grid_type", C.c_int32), ("ranks_y", C.c_int32),
     ]
+
+
+class _Record(C.Structure):
+    """A result struct of the device diagnostics: compared and printed by value."""
+
+    def as_dict(self):
+        out = {}
+        for name, _ in self._fields_:
+            v = getattr(self, name)
+            out[name] = v.as_dict() if isinstance(v, _Record) else (tuple(v) if hasattr(v, "__len__") else v)
+        out.pop("reserved", None)
+        return out
+
+    def __eq__(self, other):
+        return type(other) is type(self) and bytes(self) == bytes(other)
+
+    __hash__ = None
+
+    def __repr__(self):
+        return f"{type(self).__name__}({', '.join(f'{k}={v!r}' for k, v in self.as_dict().items())})"
+
+
+class FieldStats(_Record):
+    """gb25_field_stats (include/gb25.h): positions are 1-based (i, j, k) in the box; position + global_offset = 1-based
+    index into the global interior."""
+    _fields_ = [("min", C.c_double), ("max", C.c_double), ("max_abs", C.c_double), ("sum", C.c_double), ("sum_sq", C.c_double),
+                ("count", C.c_int64), ("nonfinite", C.c_int64),
+                ("at_max_abs", C.c_int32 * 3), ("first_nonfinite", C.c_int32 * 3), ("global_offset", C.c_int32 * 3),
+                ("reserved", C.c_int32)]
+
+
+class FieldDiff(_Record):
+    """gb25_field_diff (include/gb25.h): a = the model's field, b = the other array, delta = a - b in fp64."""
+    _fields_ = [("max_abs_a", C.c_double), ("max_abs_b", C.c_double), ("max_abs_delta", C.c_double),
+                ("sum_sq_a", C.c_double), ("sum_sq_b", C.c_double), ("sum_sq_delta", C.c_double),
+                ("count", C.c_int64), ("nonfinite", C.c_int64),
+                ("at_max_abs_delta", C.c_int32 * 3), ("global_offset", C.c_int32 * 3)]
+
+
+class StateMonitor(_Record):
+    """gb25_state_monitor (include/gb25.h).  str() is one progress line in the shape of the reference's callback
+    (simulations/ocean_climate_simulation.jl:95-116)."""
+    _fields_ = [("u", FieldStats), ("v", FieldStats), ("w", FieldStats), ("eta", FieldStats), ("T", FieldStats), ("S", FieldStats),
+                ("cfl", C.c_double), ("at_cfl", C.c_int32 * 3), ("reserved", C.c_int32),
+                ("nonfinite_total", C.c_int64), ("iteration", C.c_int64), ("time", C.c_double)]
+
+    def __str__(self):
+        return ("iter: %d, time: %.6g s, max|u, v, w|: (%.2e, %.2e, %.2e) m/s, extrema(T): (%.3f, %.3f), extrema(S): (%.3f, %.3f), "
+                "max|eta|: %.3e m, advective CFL rate: %.3e 1/s at (%d, %d, %d), non-finite: %d"
+                % (self.iteration, self.time, self.u.max_abs, self.v.max_abs, self.w.max_abs, self.T.min, self.T.max,
+                   self.S.min, self.S.max, self.eta.max_abs, self.cfl, *self.at_cfl, self.nonfinite_total))
 
 
 class GB25Error(RuntimeError):
@@ -206,6 +259,11 @@ def load_library(float_type="Float32"):
     lib.gb25_debug_sequence.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_int64]
     lib.gb25_debug_sequence.restype = C.c_int64
     lib.gb25_lookahead_state.argtypes = [P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.gb25_get_field_stats.argtypes = [P, C.c_int, C.c_int, C.POINTER(FieldStats)]
+    lib.gb25_compare_field.argtypes = [P, C.c_int, C.c_int, P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                       C.POINTER(FieldDiff)]
+    lib.gb25_get_state_monitor.argtypes = [P, C.POINTER(StateMonitor)]
+    lib.gb25_field_device_ptr_readonly.argtypes = [P, C.c_int, C.POINTER(P), C.POINTER(C.c_int32)]
     lib.gb25_profile_enable.argtypes = [P, C.c_int]
     lib.gb25_profile_get.argtypes = [P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     for name in ["gb25_use_own_stream", "gb25_synchronize", "gb25_set_baroclinic_instability", "gb25_initialize",
@@ -223,6 +281,12 @@ def load_library(float_type="Float32"):
         raise GB25Error(f"{path}: gb25_config is {lib.gb25_config_bytes()} bytes there and {C.sizeof(Config)} in this binding "
                         f"(gb25_catke_parameters: {lib.gb25_catke_parameters_bytes()} / {C.sizeof(CatkeParameters)}): "
                         "the library and gb25_amd/binding.py are of different versions")
+    for fn, struct in (("gb25_field_stats_bytes", FieldStats), ("gb25_field_diff_bytes", FieldDiff),
+                       ("gb25_state_monitor_bytes", StateMonitor)):
+        getattr(lib, fn).restype = C.c_int32
+        if getattr(lib, fn)() != C.sizeof(struct):
+            raise GB25Error(f"{path}: {fn}() = {getattr(lib, fn)()} there, {C.sizeof(struct)} bytes in this binding: "
+                            "the library and gb25_amd/binding.py are of different versions")
     _libs[float_type] = lib
     return lib
 
@@ -309,7 +373,46 @@ class HipBackend:
         self._call("gb25_field_device_ptr", FIELD_IDS[name], C.byref(p))
         return p.value
 
-    def metric(self, name, index):
+    # ---- diagnostics on the device (no field crosses PCIe; read-only for the schedule)
+    def field_stats(self, name, include_halos=False):
+        """gb25_get_field_stats: min, max, max|x| and where, sums, non-finite count of the interior (or the parent)."""
+        out = FieldStats()
+        self._call("gb25_get_field_stats", FIELD_IDS[name], int(include_halos), C.byref(out))
+        return out
+
+    def field_device_ptr_readonly(self, name):
+        """(device pointer of parent(field) for reading, the array's extents on the device); pins nothing, valid until the
+        next call on this model."""
+        p, d = C.c_void_p(), (C.c_int32 * 3)()
+        self._call("gb25_field_device_ptr_readonly", FIELD_IDS[name], C.byref(p), d)
+        return p.value, tuple(d)
+
+    def compare_field(self, name, other, include_halos=False, *, other_name=None, real_bytes=None, dims=None, origin=None):
+        """gb25_compare_field of this model's field `name` (a) against b.  other: another HipBackend of this process, of
+        either float type (b = its field `other_name`, default the same name; interior against interior or parent against
+        parent, b may be the larger) -- or a device pointer (int) with real_bytes, dims and origin given."""
+        if isinstance(other, HipBackend):
+            ptr, dims = other.field_device_ptr_readonly(other_name or name)
+            real_bytes = np.dtype(other.dtype).itemsize
+            h = 0 if include_halos else other.cfg.halo
+            origin = (h, h, 0 if dims[2] == 1 else h)
+        else:
+            ptr = other
+            if real_bytes is None or dims is None:
+                raise TypeError("compare_field with a device pointer needs real_bytes and dims")
+        out = FieldDiff()
+        d = (C.c_int32 * 3)(*dims)
+        o = (C.c_int32 * 3)(*origin) if origin is not None else None
+        self._call("gb25_compare_field", FIELD_IDS[name], int(include_halos), C.c_void_p(ptr), int(real_bytes), d, o, C.byref(out))
+        return out
+
+    def state_monitor(self):
+        """gb25_get_state_monitor: interior statistics of u, v, w, eta, T, S, the advective CFL rate, the clock."""
+        out = StateMonitor()
+        self._call("gb25_get_state_monitor", C.byref(out))
+        return out
+
+    def metric(self, name, index=1):
         v = C.c_double()
         self._call("gb25_get_metric", METRIC_IDS[name], index, C.byref(v))
         return v.value

@@ -1,0 +1,246 @@
+// diagnostics_host.hpp -- host side of gb25_get_field_stats / gb25_compare_field / gb25_get_state_monitor /
+// gb25_field_device_ptr_readonly (include/gb25.h); the last part of gb25_api.hip, which includes it.  Kernels:
+// diagnostics_kernels.hpp.  Nothing here writes model memory or a schedule flag: the calls may sit between any two steps.
+#pragma once
+
+namespace {
+
+constexpr size_t DIAG_RECORD = 64;   // bytes of a slot of the scratch buffer: the largest per-block record
+constexpr int DIAG_RESULTS = 8;      // result slots behind the per-block records (a state monitor fills seven)
+static_assert(sizeof(StatsPartial) <= DIAG_RECORD && sizeof(DiffPartial) <= DIAG_RECORD && sizeof(CflPartial) <= DIAG_RECORD, "slot size");
+
+inline long long diag_blocks(const DiagBox& b) { return ((long long)b.by * b.bz + DIAG_ROWS - 1) / DIAG_ROWS; }
+
+// once per model: per-block records for the tallest box a field of this model has (w's parent), plus the result slots
+gb25_status diag_scratch(gb25_model* m) {
+  if (m->diag_scratch) return GB25_OK;
+  const int H = m->cfg.halo;
+  const long long rows = (long long)(m->Ny + 2 * H + 1) * (m->cfg.Nz + 2 * H + 1);
+  const size_t records = (size_t)((rows + DIAG_ROWS - 1) / DIAG_ROWS);
+  HIPCHK(hipMalloc(&m->diag_scratch, (records + DIAG_RESULTS) * DIAG_RECORD));
+  m->diag_scratch_records = records;
+  return GB25_OK;
+}
+inline void* diag_result_slot(gb25_model* m, int q) { return (char*)m->diag_scratch + (m->diag_scratch_records + q) * DIAG_RECORD; }
+
+// the whole model is quiet (what gb25_synchronize waits for)
+gb25_status diag_wait_for_model(gb25_model* m) {
+  HIPCHK(hipStreamSynchronize(m->stream));
+  HIPCHK(hipStreamSynchronize(m->side_stream));
+  if (m->baro_stream) HIPCHK(hipStreamSynchronize(m->baro_stream));
+  if (m->group) HIPCHK(m->group->sync_side());
+  return GB25_OK;
+}
+
+// The array that holds what gb25_get_field(id) would return, without moving anything: previous_velocities are read where they
+// live (prev_uv_src), a stale pHY' is recomputed from the T, S it belongs to (the launch is filed under GB25_K_DIAGNOSTICS).
+gb25_status diag_source(gb25_model* m, gb25_field id, const real** src) {
+  if (id < 0 || id >= GB25_FIELD_COUNT) return GB25_ERR_INVALID_ARGUMENT;
+  if (!m->f[id].d) return fail(m, GB25_ERR_INVALID_ARGUMENT, "this model has no such field (closure = CATKEVerticalDiffusivity() only)");
+  if (m->uv_lazy)   // (only after a composite call that failed half-way)
+    if (gb25_status s = materialize_uv(m)) return s;
+  if (id == GB25_PHY && m->phy_stale) {
+    m->prof_redirect = GB25_K_DIAGNOSTICS;
+    const gb25_status s = compute_p_impl(m);
+    m->prof_redirect = -1;
+    if (s) return s;
+  }
+  *src = m->f[id].d;
+  if ((id == GB25_PREV_U || id == GB25_PREV_V) && m->catke && m->prev_uv_src != 0) {
+    const int q = id - GB25_PREV_U;
+    *src = m->prev_uv_src == 1 ? m->f[GB25_U + q].d : m->ahead_uv[q].d;
+  }
+  return GB25_OK;
+}
+
+gb25_status diag_box(const gb25_model* m, gb25_field id, int include_halos, DiagBox* b) {
+  int32_t d[3];
+  if (gb25_field_dims(m, id, include_halos, d)) return GB25_ERR_INVALID_ARGUMENT;
+  const Field& F = m->f[id];
+  const long long H = include_halos ? 0 : m->cfg.halo;
+  b->bx = d[0]; b->by = d[1]; b->bz = d[2];
+  b->pitch = F.nx;
+  b->plane = (long long)F.nx * F.ny;
+  b->origin = H + b->pitch * H + b->plane * (is_2d(id) ? 0 : H);
+  return GB25_OK;
+}
+// position + global_offset = 1-based index into the global interior
+void diag_global_offset(const gb25_model* m, gb25_field id, int include_halos, int32_t off[3]) {
+  const int H = include_halos ? m->cfg.halo : 0;
+  off[0] = m->rx * m->Nx - H;
+  off[1] = m->j0 - H;
+  off[2] = is_2d(id) ? 0 : -H;
+}
+void diag_position(long long at, const DiagBox& b, int32_t pos[3]) {
+  if (at == DIAG_NONE) {
+    pos[0] = pos[1] = pos[2] = 0;
+    return;
+  }
+  pos[0] = (int32_t)(at % b.bx) + 1;
+  pos[1] = (int32_t)((at / b.bx) % b.by) + 1;
+  pos[2] = (int32_t)(at / ((long long)b.bx * b.by)) + 1;
+}
+
+template <class P>
+gb25_status diag_finish(gb25_model* m, long long nblocks, int slot) {
+  hipLaunchKernelGGL(k_diag_finish<P>, dim3(1), dim3(DIAG_THREADS), 0, m->stream, (const P*)m->diag_scratch, (int)nblocks,
+                     (P*)diag_result_slot(m, slot));
+  LAUNCHCHK();
+  return GB25_OK;
+}
+gb25_status diag_launch_stats(gb25_model* m, const real* src, const DiagBox& b, int slot) {
+  const long long nb = diag_blocks(b);
+  hipLaunchKernelGGL(k_field_stats<real>, dim3((unsigned)nb), dim3(DIAG_THREADS), 0, m->stream, src, b, (StatsPartial*)m->diag_scratch);
+  LAUNCHCHK();
+  return diag_finish<StatsPartial>(m, nb, slot);
+}
+void diag_fill_stats(const gb25_model* m, gb25_field id, const StatsPartial& p, const DiagBox& b, int include_halos, gb25_field_stats* out) {
+  memset(out, 0, sizeof *out);
+  out->min = p.mn; out->max = p.mx;
+  out->max_abs = p.amax < 0 ? 0.0 : p.amax;
+  out->sum = p.sum; out->sum_sq = p.sumsq;
+  out->count = (int64_t)b.bx * b.by * b.bz;
+  out->nonfinite = p.nonfinite;
+  diag_position(p.amax < 0 ? DIAG_NONE : p.at, b, out->at_max_abs);
+  diag_position(p.first, b, out->first_nonfinite);
+  diag_global_offset(m, id, include_halos, out->global_offset);
+}
+gb25_status diag_check_box(gb25_model* m, const DiagBox& b) {
+  if (b.bx <= 0 || b.by <= 0 || b.bz <= 0) return fail(m, GB25_ERR_INVALID_ARGUMENT, "the field has an empty box");
+  if ((size_t)diag_blocks(b) > m->diag_scratch_records) return fail(m, GB25_ERR_STATE, "diagnostics: the box needs more per-block records than the model's scratch buffer holds");
+  return GB25_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t gb25_field_stats_bytes(void) { return (int32_t)sizeof(gb25_field_stats); }
+int32_t gb25_field_diff_bytes(void) { return (int32_t)sizeof(gb25_field_diff); }
+int32_t gb25_state_monitor_bytes(void) { return (int32_t)sizeof(gb25_state_monitor); }
+
+gb25_status gb25_get_field_stats(gb25_model* m, gb25_field f, int include_halos, gb25_field_stats* out) {
+  if (!m || !out) return GB25_ERR_INVALID_ARGUMENT;
+  const real* src = nullptr;
+  DiagBox b;
+  if (gb25_status s = diag_source(m, f, &src)) return s;
+  if (gb25_status s = diag_scratch(m)) return s;
+  if (gb25_status s = diag_box(m, f, include_halos, &b)) return s;
+  if (gb25_status s = diag_check_box(m, b)) return s;
+  if (gb25_status s = diag_wait_for_model(m)) return s;
+  {
+    Timed t(m, GB25_K_DIAGNOSTICS);
+    if (gb25_status s = diag_launch_stats(m, src, b, 0)) return s;
+  }
+  StatsPartial p;
+  HIPCHK(hipMemcpyAsync(&p, diag_result_slot(m, 0), sizeof p, hipMemcpyDeviceToHost, m->stream));
+  HIPCHK(hipStreamSynchronize(m->stream));
+  diag_fill_stats(m, f, p, b, include_halos, out);
+  return GB25_OK;
+}
+
+gb25_status gb25_compare_field(gb25_model* m, gb25_field f, int include_halos, const void* other_dev, int32_t other_real_bytes,
+                               const int32_t other_dims[3], const int32_t other_origin[3], gb25_field_diff* out) {
+  if (!m || !out || !other_dev || !other_dims) return GB25_ERR_INVALID_ARGUMENT;
+  if (other_real_bytes != 4 && other_real_bytes != 8)
+    return fail(m, GB25_ERR_INVALID_ARGUMENT, "other_real_bytes must be 4 (float) or 8 (double), got %d", other_real_bytes);
+  const real* src = nullptr;
+  DiagBox b, ob;
+  if (gb25_status s = diag_source(m, f, &src)) return s;
+  if (gb25_status s = diag_scratch(m)) return s;
+  if (gb25_status s = diag_box(m, f, include_halos, &b)) return s;
+  if (gb25_status s = diag_check_box(m, b)) return s;
+  const int32_t zero[3] = {0, 0, 0};
+  const int32_t* o = other_origin ? other_origin : zero;
+  const int ext[3] = {b.bx, b.by, b.bz};
+  for (int q = 0; q < 3; q++)
+    if (other_dims[q] <= 0 || o[q] < 0 || (long long)o[q] + ext[q] > other_dims[q])
+      return fail(m, GB25_ERR_INVALID_ARGUMENT, "the other array (%d x %d x %d from %d %d %d) does not hold the %d x %d x %d box of this field",
+                  other_dims[0], other_dims[1], other_dims[2], o[0], o[1], o[2], b.bx, b.by, b.bz);
+  ob = b;
+  ob.pitch = other_dims[0];
+  ob.plane = (long long)other_dims[0] * other_dims[1];
+  ob.origin = o[0] + ob.pitch * o[1] + ob.plane * o[2];
+  if (gb25_status s = diag_wait_for_model(m)) return s;
+  const long long nb = diag_blocks(b);
+  {
+    Timed t(m, GB25_K_DIAGNOSTICS);
+    DiffPartial* part = (DiffPartial*)m->diag_scratch;
+    if (other_real_bytes == 4)
+      hipLaunchKernelGGL((k_field_diff<real, float>), dim3((unsigned)nb), dim3(DIAG_THREADS), 0, m->stream, src, b, (const float*)other_dev, ob, part);
+    else
+      hipLaunchKernelGGL((k_field_diff<real, double>), dim3((unsigned)nb), dim3(DIAG_THREADS), 0, m->stream, src, b, (const double*)other_dev, ob, part);
+    LAUNCHCHK();
+    if (gb25_status s = diag_finish<DiffPartial>(m, nb, 0)) return s;
+  }
+  DiffPartial p;
+  HIPCHK(hipMemcpyAsync(&p, diag_result_slot(m, 0), sizeof p, hipMemcpyDeviceToHost, m->stream));
+  HIPCHK(hipStreamSynchronize(m->stream));
+  memset(out, 0, sizeof *out);
+  out->max_abs_a = p.amax_a < 0 ? 0.0 : p.amax_a;
+  out->max_abs_b = p.amax_b < 0 ? 0.0 : p.amax_b;
+  out->max_abs_delta = p.amax_d < 0 ? 0.0 : p.amax_d;
+  out->sum_sq_a = p.ss_a; out->sum_sq_b = p.ss_b; out->sum_sq_delta = p.ss_d;
+  out->count = (int64_t)b.bx * b.by * b.bz;
+  out->nonfinite = p.nonfinite;
+  diag_position(p.amax_d < 0 ? DIAG_NONE : p.at, b, out->at_max_abs_delta);
+  diag_global_offset(m, f, include_halos, out->global_offset);
+  return GB25_OK;
+}
+
+gb25_status gb25_get_state_monitor(gb25_model* m, gb25_state_monitor* out) {
+  if (!m || !out) return GB25_ERR_INVALID_ARGUMENT;
+  static const gb25_field ids[6] = {GB25_U, GB25_V, GB25_W, GB25_ETA, GB25_T, GB25_S};
+  const real* src[6];
+  DiagBox b[6];
+  for (int q = 0; q < 6; q++) {
+    if (gb25_status s = diag_source(m, ids[q], &src[q])) return s;
+    if (gb25_status s = diag_box(m, ids[q], 0, &b[q])) return s;
+  }
+  if (gb25_status s = diag_scratch(m)) return s;
+  for (int q = 0; q < 6; q++)
+    if (gb25_status s = diag_check_box(m, b[q])) return s;
+  if (gb25_status s = diag_wait_for_model(m)) return s;
+  {
+    Timed t(m, GB25_K_DIAGNOSTICS);
+    for (int q = 0; q < 6; q++)
+      if (gb25_status s = diag_launch_stats(m, src[q], b[q], q)) return s;
+    const long long nb = diag_blocks(b[0]);   // (the interior of u: Nx x Ny x Nz, the cells)
+    hipLaunchKernelGGL(k_advective_cfl, dim3((unsigned)nb), dim3(DIAG_THREADS), 0, m->stream, m->g, src[0], src[1], src[2], b[0],
+                       (CflPartial*)m->diag_scratch);
+    LAUNCHCHK();
+    if (gb25_status s = diag_finish<CflPartial>(m, nb, 6)) return s;
+  }
+  char host[7 * DIAG_RECORD];
+  HIPCHK(hipMemcpyAsync(host, diag_result_slot(m, 0), sizeof host, hipMemcpyDeviceToHost, m->stream));
+  HIPCHK(hipStreamSynchronize(m->stream));
+  memset(out, 0, sizeof *out);
+  gb25_field_stats* dst[6] = {&out->u, &out->v, &out->w, &out->eta, &out->T, &out->S};
+  for (int q = 0; q < 6; q++) {
+    StatsPartial p;
+    memcpy(&p, host + q * DIAG_RECORD, sizeof p);
+    diag_fill_stats(m, ids[q], p, b[q], 0, dst[q]);
+    out->nonfinite_total += p.nonfinite;
+  }
+  CflPartial c;
+  memcpy(&c, host + 6 * DIAG_RECORD, sizeof c);
+  out->cfl = c.cfl < 0 ? 0.0 : c.cfl;
+  diag_position(c.cfl < 0 ? DIAG_NONE : c.at, b[0], out->at_cfl);
+  out->iteration = m->iteration;
+  out->time = m->time;
+  return GB25_OK;
+}
+
+gb25_status gb25_field_device_ptr_readonly(gb25_model* m, gb25_field f, const void** dev, int32_t device_dims[3]) {
+  if (!m || !dev) return GB25_ERR_INVALID_ARGUMENT;
+  const real* src = nullptr;
+  if (gb25_status s = diag_source(m, f, &src)) return s;
+  if (gb25_status s = diag_wait_for_model(m)) return s;
+  *dev = src;
+  if (device_dims) {
+    device_dims[0] = m->f[f].nx; device_dims[1] = m->f[f].ny; device_dims[2] = m->f[f].nz;
+  }
+  return GB25_OK;
+}
+
+}  // extern "C"

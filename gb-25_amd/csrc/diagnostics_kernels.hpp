@@ -1,0 +1,289 @@
+// diagnostics_kernels.hpp -- reductions over the model's fields where the fields live (gb25_get_field_stats,
+// gb25_compare_field, gb25_get_state_monitor: include/gb25.h).  Three streaming reads and one tiny second launch:
+//
+//   k_field_stats     one pass over a box of a field's parent array: min, max, max|x| and where, sum x, sum x^2 (fp64), the
+//                     number of non-finite values and where the first one is.  4 (Float32) / 8 (Float64) bytes per element.
+//   k_field_diff      the same pass over two arrays a, b (b: float or double, dims of its own, an origin of its own):
+//                     max|a|, max|b|, sum a^2, sum b^2, d = a - b in fp64, max|d| and where, sum d^2.  sizeof a + sizeof b.
+//   k_advective_cfl   over the interior cells max of |u|/dx(u point) + |v|/dy(v point) + |w|/dz(w face) in fp64, IEEE
+//                     divisions, the three values at the same index (i, j, k), summed left to right.  The metrics are the
+//                     numbers gb25_get_metric / gb25_get_metric2 return:
+//                       LatitudeLongitudeGrid:  dx = GB25_M_DXC(j),  dy = GB25_M_DY,        dz = GB25_M_DZF(k)
+//                       curvilinear grids:      dx = GB25_M2_DXFC,   dy = GB25_M2_DYCF,     dz = GB25_M_DZF(k)
+//                     12 / 24 bytes per cell.
+//   k_diag_finish<P>  combines the per-block records of any of the three in a fixed order.
+//
+// Bitwise repeatable, whatever the order in which blocks run: the assignment of elements to lanes is a function of the box
+// alone (a block = DIAG_ROWS rows of the box, a wave = every fourth of them, a lane = every 64th chunk of four elements of a
+// row), a lane accumulates in the order of its elements, lanes are combined by a fixed shuffle tree, the four waves through LDS
+// in wave order, the blocks' records (plain vector stores into the model's scratch buffer) by one block of the second launch in
+// the same manner.  No atomics.  Extrema do not depend on any order; ties in a position go to the smallest linear offset in
+// memory order (i fastest), Julia's findmax.  Offsets are 64-bit.
+//
+// Loads: a row is cut into chunks of four elements aligned to 4 sizeof(T) in MEMORY (the interior of a row starts H elements
+// into a row of Nx + 2H: whatever that does to the alignment, the body of a row goes through one 16-byte (Float32) or two
+// 16-byte (Float64) loads per lane and only the cut chunks at its two ends through element loads).  Nothing outside the box
+// is read.
+#pragma once
+#include "device_common.hpp"
+
+namespace gb25 {
+
+constexpr int DIAG_THREADS = 256;   // four waves
+constexpr int DIAG_ROWS = 16;       // rows of the box per block
+constexpr long long DIAG_NONE = 0x7fffffffffffffffLL;
+
+// a box of an array: extent, the array's pitches, the box's first element
+struct DiagBox {
+  int bx, by, bz;
+  long long pitch, plane, origin;
+};
+
+struct StatsPartial {
+  double mn, mx, amax, sum, sumsq;
+  long long at, nonfinite, first;
+};
+struct DiffPartial {
+  double amax_a, amax_b, amax_d, ss_a, ss_b, ss_d;
+  long long at, nonfinite;
+};
+struct CflPartial {
+  double cfl;
+  long long at;
+};
+
+__device__ __forceinline__ StatsPartial diag_identity(const StatsPartial*) {
+  return {__builtin_inf(), -__builtin_inf(), -1.0, 0.0, 0.0, DIAG_NONE, 0, DIAG_NONE};
+}
+__device__ __forceinline__ DiffPartial diag_identity(const DiffPartial*) { return {-1.0, -1.0, -1.0, 0.0, 0.0, 0.0, DIAG_NONE, 0}; }
+__device__ __forceinline__ CflPartial diag_identity(const CflPartial*) { return {-1.0, DIAG_NONE}; }
+
+// larger value wins; equal values: the smaller offset
+__device__ __forceinline__ void diag_take_max(double& best, long long& at, double v, long long o) {
+  const bool take = v > best || (v == best && o < at);
+  best = take ? v : best;
+  at = take ? o : at;
+}
+// a (the earlier in the fixed order) combined with b
+__device__ __forceinline__ StatsPartial diag_combine(StatsPartial a, const StatsPartial& b) {
+  a.mn = __builtin_fmin(a.mn, b.mn);
+  a.mx = __builtin_fmax(a.mx, b.mx);
+  diag_take_max(a.amax, a.at, b.amax, b.at);
+  a.sum += b.sum;
+  a.sumsq += b.sumsq;
+  a.nonfinite += b.nonfinite;
+  a.first = b.first < a.first ? b.first : a.first;
+  return a;
+}
+__device__ __forceinline__ DiffPartial diag_combine(DiffPartial a, const DiffPartial& b) {
+  a.amax_a = __builtin_fmax(a.amax_a, b.amax_a);
+  a.amax_b = __builtin_fmax(a.amax_b, b.amax_b);
+  diag_take_max(a.amax_d, a.at, b.amax_d, b.at);
+  a.ss_a += b.ss_a;
+  a.ss_b += b.ss_b;
+  a.ss_d += b.ss_d;
+  a.nonfinite += b.nonfinite;
+  return a;
+}
+__device__ __forceinline__ CflPartial diag_combine(CflPartial a, const CflPartial& b) {
+  diag_take_max(a.cfl, a.at, b.cfl, b.at);
+  return a;
+}
+
+// lane l <- combine(lane l, lane l + off), off = 1, 2, ... 32: lane 0 ends with the whole wave in a fixed association
+template <class P>
+__device__ __forceinline__ P diag_wave_reduce(P p) {
+  constexpr int W = sizeof(P) / sizeof(int);
+  static_assert(sizeof(P) % sizeof(int) == 0, "records are whole dwords");
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    int w[W];
+    __builtin_memcpy(w, &p, sizeof(P));
+#pragma unroll
+    for (int q = 0; q < W; q++) w[q] = __shfl_down(w[q], off, 64);
+    P o;
+    __builtin_memcpy(&o, w, sizeof(P));
+    p = diag_combine(p, o);
+  }
+  return p;
+}
+// the block's record, in thread 0
+template <class P>
+__device__ __forceinline__ P diag_block_reduce(P p) {
+  __shared__ P lds[DIAG_THREADS / 64];
+  p = diag_wave_reduce(p);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) lds[wave] = p;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int w = 1; w < DIAG_THREADS / 64; w++) p = diag_combine(p, lds[w]);
+  return p;
+}
+
+// Four elements of a row: in-row positions [x0, x0 + 4), of which [0, bx) exist.  `row` points at position 0.  A chunk that
+// lies inside the row and is aligned in memory is one vector load; any other is element loads of what exists (0 elsewhere).
+template <class T>
+__device__ __forceinline__ void diag_load4(const T* row, int x0, int bx, T out[4]) {
+  using V4 = T __attribute__((ext_vector_type(4)));
+  const T* p = row + x0;
+  if (x0 >= 0 && x0 + 4 <= bx && ((unsigned long long)p & (4 * sizeof(T) - 1)) == 0) {
+    const V4 v = *reinterpret_cast<const V4*>(p);
+    out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w;
+  } else {
+#pragma unroll
+    for (int s = 0; s < 4; s++) out[s] = (x0 + s >= 0 && x0 + s < bx) ? p[s] : T(0);
+  }
+}
+// how many elements the row's first element lies beyond a 4 sizeof(T) boundary
+template <class T>
+__device__ __forceinline__ int diag_misalignment(const T* row) {
+  return (int)(((unsigned long long)row / sizeof(T)) & 3);
+}
+
+// The rows of a block: row r of the box is (j, k) = (r % by, r / by); the wave takes every fourth row of the block's DIAG_ROWS,
+// a lane every 64th chunk of the row.  body(row offset into the array, box offset of the row's first element, j, k).
+template <class Body>
+__device__ __forceinline__ void diag_for_rows(const DiagBox& box, Body body) {
+  const long long rows = (long long)box.by * box.bz;
+  const long long r0 = (long long)blockIdx.x * DIAG_ROWS;
+  const int wave = threadIdx.x >> 6;
+  for (int q = wave; q < DIAG_ROWS; q += DIAG_THREADS / 64) {
+    const long long r = r0 + q;
+    if (r >= rows) break;
+    const int k = (int)(r / box.by), j = (int)(r - (long long)k * box.by);
+    body(box.origin + box.pitch * j + box.plane * k, r * box.bx, j, k);
+  }
+}
+
+template <class T>
+__global__ __launch_bounds__(DIAG_THREADS) void k_field_stats(const T* __restrict__ a, DiagBox box, StatsPartial* __restrict__ partials) {
+  StatsPartial p = diag_identity((StatsPartial*)nullptr);
+  const int lane = threadIdx.x & 63;
+  diag_for_rows(box, [&](long long row_off, long long box_off, int, int) {
+    const T* row = a + row_off;
+    const int mis = diag_misalignment(row), nchunks = (mis + box.bx + 3) >> 2;
+    for (int c = lane; c < nchunks; c += 64) {
+      const int x0 = 4 * c - mis;
+      T e[4];
+      diag_load4(row, x0, box.bx, e);
+#pragma unroll
+      for (int s = 0; s < 4; s++) {
+        const int x = x0 + s;
+        if (x < 0 || x >= box.bx) continue;
+        const double v = (double)e[s];
+        const long long o = box_off + x;
+        if (__builtin_isfinite(v)) {
+          p.mn = __builtin_fmin(p.mn, v);
+          p.mx = __builtin_fmax(p.mx, v);
+          diag_take_max(p.amax, p.at, __builtin_fabs(v), o);
+          p.sum += v;
+          p.sumsq = __builtin_fma(v, v, p.sumsq);
+        } else {
+          p.nonfinite++;
+          p.first = o < p.first ? o : p.first;
+        }
+      }
+    }
+  });
+  p = diag_block_reduce(p);
+  if (threadIdx.x == 0) partials[blockIdx.x] = p;
+}
+
+// a: box `box` of the model's field; b: the box of the same extent of another array (pitches and first element in bbox)
+template <class TA, class TB>
+__global__ __launch_bounds__(DIAG_THREADS) void k_field_diff(const TA* __restrict__ a, DiagBox box, const TB* __restrict__ b, DiagBox bbox,
+                                                             DiffPartial* __restrict__ partials) {
+  DiffPartial p = diag_identity((DiffPartial*)nullptr);
+  const int lane = threadIdx.x & 63;
+  diag_for_rows(box, [&](long long row_off, long long box_off, int j, int k) {
+    const TA* row = a + row_off;
+    const TB* rowb = b + (bbox.origin + bbox.pitch * j + bbox.plane * k);
+    const int mis = diag_misalignment(row), nchunks = (mis + box.bx + 3) >> 2;
+    for (int c = lane; c < nchunks; c += 64) {
+      const int x0 = 4 * c - mis;
+      TA ea[4];
+      TB eb[4];
+      diag_load4(row, x0, box.bx, ea);
+      diag_load4(rowb, x0, box.bx, eb);   // (chunks cut like a's: a vector load where b happens to be aligned as well)
+#pragma unroll
+      for (int s = 0; s < 4; s++) {
+        const int x = x0 + s;
+        if (x < 0 || x >= box.bx) continue;
+        const double va = (double)ea[s], vb = (double)eb[s], d = va - vb;
+        const bool fa = __builtin_isfinite(va), fb = __builtin_isfinite(vb);
+        if (fa) {
+          p.amax_a = __builtin_fmax(p.amax_a, __builtin_fabs(va));
+          p.ss_a = __builtin_fma(va, va, p.ss_a);
+        }
+        if (fb) {
+          p.amax_b = __builtin_fmax(p.amax_b, __builtin_fabs(vb));
+          p.ss_b = __builtin_fma(vb, vb, p.ss_b);
+        }
+        if (fa && fb && __builtin_isfinite(d)) {
+          diag_take_max(p.amax_d, p.at, __builtin_fabs(d), box_off + x);
+          p.ss_d = __builtin_fma(d, d, p.ss_d);
+        } else {
+          p.nonfinite++;
+        }
+      }
+    }
+  });
+  p = diag_block_reduce(p);
+  if (threadIdx.x == 0) partials[blockIdx.x] = p;
+}
+
+// box: the interior of u (w has the same pitches; v the plane g.pl_v)
+__global__ __launch_bounds__(DIAG_THREADS) void k_advective_cfl(Grid g, const real* __restrict__ u, const real* __restrict__ v,
+                                                                const real* __restrict__ w, DiagBox box, CflPartial* __restrict__ partials) {
+  CflPartial p = diag_identity((CflPartial*)nullptr);
+  const int lane = threadIdx.x & 63;
+  diag_for_rows(box, [&](long long row_off, long long box_off, int j, int k) {
+    const real *ru = u + row_off, *rw = w + row_off;
+    const real* rv = v + (box.origin + box.pitch * j + (long long)g.pl_v * k + ((long long)g.pl_v - g.pl_c) * g.H);
+    const real *rdx = nullptr, *rdy = nullptr;
+    double dx = 0, dy = (double)g.dy;
+    if (g.cv.on) {
+      rdx = g.cv.dxfc + i2(g, 0, j);
+      rdy = g.cv.dycf + i2(g, 0, j);
+    } else {
+      dx = (double)g.dxc[j];
+    }
+    const double dz = (double)g.dzf[k];
+    const int mis = diag_misalignment(ru), nchunks = (mis + box.bx + 3) >> 2;
+    for (int c = lane; c < nchunks; c += 64) {
+      const int x0 = 4 * c - mis;
+      real eu[4], ev[4], ew[4], ex[4], ey[4];
+      diag_load4(ru, x0, box.bx, eu);
+      diag_load4(rv, x0, box.bx, ev);
+      diag_load4(rw, x0, box.bx, ew);
+      if (g.cv.on) {
+        diag_load4(rdx, x0, box.bx, ex);
+        diag_load4(rdy, x0, box.bx, ey);
+      }
+#pragma unroll
+      for (int s = 0; s < 4; s++) {
+        const int x = x0 + s;
+        if (x < 0 || x >= box.bx) continue;
+        if (g.cv.on) {
+          dx = (double)ex[s];
+          dy = (double)ey[s];
+        }
+        const double c3 = (__builtin_fabs((double)eu[s]) / dx + __builtin_fabs((double)ev[s]) / dy) + __builtin_fabs((double)ew[s]) / dz;
+        if (__builtin_isfinite(c3)) diag_take_max(p.cfl, p.at, c3, box_off + x);
+      }
+    }
+  });
+  p = diag_block_reduce(p);
+  if (threadIdx.x == 0) partials[blockIdx.x] = p;
+}
+
+// one block: the records of the first launch in index order -- thread t takes t, t + 256, ... --, then the block's tree
+template <class P>
+__global__ __launch_bounds__(DIAG_THREADS) void k_diag_finish(const P* __restrict__ partials, int n, P* __restrict__ out) {
+  P p = diag_identity((P*)nullptr);
+  for (int q = threadIdx.x; q < n; q += DIAG_THREADS) p = diag_combine(p, partials[q]);
+  p = diag_block_reduce(p);
+  if (threadIdx.x == 0) *out = p;
+}
+
+}  // namespace gb25

@@ -8,6 +8,7 @@
 #include <dlfcn.h>
 #include "kernels.hpp"
 #include "tendency_kernels.hpp"
+#include "diagnostics_kernels.hpp"
 
 #include <cmath>
 #include <cstdarg>
@@ -226,6 +227,12 @@ struct gb25_model {
   struct SlabGroup* group = nullptr; // exchange context (transport, buffers, comm stream) once gb25_comm_init_* was called
   int group_index = 0;               // this slab's position in group->slabs
   int fold_flip = 0;                 // folded slab: which of the two widened state sets the next substep reads
+  // diagnostics (diagnostics_host.hpp): the per-block records of the reduction kernels and the seven result records of a
+  // state monitor, one allocation made by the first call that needs it; prof_redirect >= 0: every timed launch is filed
+  // under that kernel id instead of its own (the pressure recomputed for the statistics of a stale pHY' is a diagnostic)
+  void* diag_scratch = nullptr;
+  size_t diag_scratch_records = 0;
+  int prof_redirect = -1;
 };
 
 namespace {
@@ -305,6 +312,7 @@ inline const char* phase_name(int k) {
     case GB25_K_IMPLICIT: return "ab2_step:implicit_step";
     case GB25_K_CORRECTOR: return "correct_velocities_and_cache_previous_tendencies";
     case GB25_K_FLUXES: return "compute_atmosphere_ocean_fluxes";
+    case GB25_K_DIAGNOSTICS: return "diagnostics";
     default: return "gb25";
   }
 }
@@ -314,9 +322,9 @@ struct Timed {
   EventPair ev;
   bool on;
   Range range;
-  Timed(gb25_model* m_, int k_) : m(m_), k(k_), on(m_->profile && (m_->profile_only < 0 || m_->profile_only == k_)), range(m_, phase_name(k_)) {
+  Timed(gb25_model* m_, int k_) : m(m_), k(m_->prof_redirect >= 0 ? m_->prof_redirect : k_), on(m_->profile && (m_->profile_only < 0 || m_->profile_only == k)), range(m_, phase_name(k)) {
     // one kernel alone: every fourth launch is timed (the event records cost the step ~1.6 % when every launch carries them)
-    if (on && m->profile_only == k_ && (m->prof_seen[k_]++ & 3) != 0) on = false;
+    if (on && m->profile_only == k && (m->prof_seen[k]++ & 3) != 0) on = false;
     if (!on) return;
     if (!m->free_events.empty()) {
       ev = m->free_events.back();
@@ -2681,6 +2689,7 @@ void gb25_destroy(gb25_model* m) {
     for (Field* p : {&m->ahead[q], &m->ahead_uv[q], &m->ahead_G[q], &m->ahead_colsum[q]})
       if (p->d) hipFree(p->d);
   if (m->uv_partials) hipFree(m->uv_partials);
+  if (m->diag_scratch) hipFree(m->diag_scratch);
   if (m->wbase) hipFree(m->wbase);
   for (auto p : m->d_ord)
     if (p) hipFree(p);
@@ -2895,7 +2904,11 @@ gb25_status gb25_field_device_ptr(gb25_model* m, gb25_field id, void** dev) {
   return GB25_OK;
 }
 gb25_status gb25_get_metric(const gb25_model* m, gb25_metric id, int32_t logical_index, double* v) {
-  if (!m || id < 0 || id > GB25_M_DZF || !v) return GB25_ERR_INVALID_ARGUMENT;
+  if (!m || id < 0 || id > GB25_M_DY || !v) return GB25_ERR_INVALID_ARGUMENT;
+  if (id == GB25_M_DY) {   // (one number: the spacing of a regular latitude grid)
+    *v = (double)m->g.dy;
+    return GB25_OK;
+  }
   int off = (id <= GB25_M_FCOR) ? m->metric_off_j : m->metric_off_k;
   long a = (long)logical_index - 1 + off;  // logical_index is 1-based like the Julia sources
   if (a < 0 || a >= (long)m->h_metric[id].size()) return GB25_ERR_INVALID_ARGUMENT;
@@ -3698,3 +3711,5 @@ gb25_status gb25_profile_get(gb25_model* m, gb25_kernel k, int64_t* launches, do
 }
 
 }  // extern "C"
+
+#include "diagnostics_host.hpp"

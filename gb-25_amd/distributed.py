@@ -15,10 +15,13 @@ module only
 No collective is needed in a time step: every rank talks to its west and east neighbour only.
 """
 import os
+from types import SimpleNamespace
+
 import numpy as np
 import torch
 
-from .binding import HipBackend
+from .binding import HipBackend, StateMonitor
+from .correctness import combine_diffs, combine_stats, _best   # noqa: F401  (combine_*: the host arithmetic over ranks)
 from .model import HydrostaticFreeSurfaceModel
 from .sharding import mesh_neighbours, slab_neighbours
 
@@ -190,6 +193,23 @@ class LocalSlabEnsemble:
         rows = [np.concatenate([self.backends[ry * self.Rx + rx].get_field(name, False) for rx in range(self.Rx)], axis=0)
                 for ry in range(self.Ry)]
         return rows[0] if self.Ry == 1 else np.concatenate(rows, axis=1)
+
+    # diagnostics: every slab reduces its own interior on the device (local, not collective), the host combines
+    def field_stats(self, name):
+        return combine_stats([b.field_stats(name, False) for b in self.backends])
+
+    def state_monitor(self):
+        mons = [b.state_monitor() for b in self.backends]
+        out = StateMonitor()
+        for name in ("u", "v", "w", "eta", "T", "S"):
+            setattr(out, name, combine_stats([getattr(m, name) for m in mons]))
+        # (the CFL record has no offset of its own: the cells are the interior of u)
+        cfls = [SimpleNamespace(cfl=m.cfl, at_cfl=m.at_cfl, global_offset=m.u.global_offset) for m in mons]
+        out.cfl, at = _best(cfls, lambda r: r.cfl, "at_cfl")
+        out.at_cfl[:] = at
+        out.nonfinite_total = sum(m.nonfinite_total for m in mons)
+        out.iteration, out.time = mons[0].iteration, mons[0].time
+        return out
 
     def set_option(self, name, value):
         for b in self.backends:

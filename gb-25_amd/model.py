@@ -31,6 +31,10 @@ class Field:
     def interior(self):
         return self._b.get_field(self.name, False)
 
+    def stats(self, include_halos=False):
+        """min, max, max|x| and where, sums and non-finite count, reduced on the device (binding.FieldStats)."""
+        return self._b.field_stats(self.name, include_halos)
+
     def set(self, array, include_halos=False):
         a = np.asarray(array)
         if not include_halos and a.ndim >= 2:
@@ -164,6 +168,13 @@ class HydrostaticFreeSurfaceModel:
         Nx, Ny, Nz = self.grid.size
         return (f"HydrostaticFreeSurfaceModel({Nx}x{Ny}x{Nz} LatitudeLongitudeGrid, halo {self.grid.halo}, "
                 f"{np.dtype(getattr(self.backend, 'dtype', np.float32)).name}, MI355X)")
+
+
+def state_monitor(model):
+    """What the progress callback of simulations/ocean_climate_simulation.jl:95-116 prints -- max|u|, |v|, |w|, extrema(T), ...
+    plus the advective CFL rate and the number of non-finite values -- reduced on the device: `print(state_monitor(model))`.
+    Does not change what the model computes or how fast it steps."""
+    return model.backend.state_monitor()
 
 
 def resolution_to_points(resolution):

@@ -181,7 +181,8 @@ typedef enum {
 /* Metric identifiers for gb25_get_metric (diagnostics / tests). */
 typedef enum {
   GB25_M_PHIF = 0, GB25_M_PHIC, GB25_M_DXC, GB25_M_DXF, GB25_M_AZC, GB25_M_AZF, GB25_M_FCOR,
-  GB25_M_ZF, GB25_M_ZC, GB25_M_DZC, GB25_M_DZF
+  GB25_M_ZF, GB25_M_ZC, GB25_M_DZC, GB25_M_DZF,
+  GB25_M_DY            /* the LatitudeLongitudeGrid's constant meridional spacing (the index is ignored): what k_advective_cfl divides v by */
 } gb25_metric;
 /* Horizontal metrics of an orthogonal curvilinear grid by location, for gb25_get_metric2 (Oceananigans' names:
  * GB25_M2_DXFC = dx at (Face, Center), ...; FFF = Coriolis parameter at (f,f); PHICC = latitude of the cell centres). */
@@ -197,6 +198,8 @@ typedef enum {
   GB25_K_IMPLICIT,     /* implicit_step!: the vertical solves of a closure (all of a step's launches together)        */
   GB25_K_CLOSURE,      /* CATKE: advection of e, surface flux, diffusivities                                          */
   GB25_K_FLUXES,       /* data-free forcing: similarity-theory fluxes; the bottom drag's flux kernel                   */
+  GB25_K_DIAGNOSTICS,  /* gb25_get_field_stats / gb25_compare_field / gb25_get_state_monitor: every launch they make,   */
+                       /* a pressure recomputed for the statistics of a stale GB25_PHY included                         */
   GB25_K_COUNT
 } gb25_kernel;
 
@@ -440,6 +443,59 @@ int64_t gb25_debug_sequence(int32_t nslabs, int32_t first, int32_t adopted, int3
  *      j0, j1, k0, k1) and the global shape, plus iteration, time, rank, nranks.  Offline gather (load_all_fields,
  *      src/sharded_io.jl:198-213): gb-25_amd/sharded_io.py. */
 gb25_status gb25_save_state(gb25_model *m, const char *directory, const char *label);
+
+/* ---- diagnostics on the device: reductions over the fields where they live (csrc/diagnostics_kernels.hpp).  What
+ *      src/correctness.jl:4-26 (compare_parent / compare_interior) computes per field and what the progress callback of
+ *      simulations/ocean_climate_simulation.jl:95-116 prints (max|u|, max|v|, max|w|, extrema(T), ...), without a field crossing
+ *      PCIe.  All of them
+ *        - see the state gb25_get_field would return at that moment and are ordered after the model's streams;
+ *        - are READ-ONLY for the schedule: no buffer is pinned, every look-ahead stays valid, every later field is bit for bit
+ *          what it would have been (unlike gb25_field_device_ptr);
+ *        - are LOCAL on a rank of a decomposition (not collective): the rank's own interior or parent.  global_offset places it:
+ *          reported position + global_offset = 1-based index into the global INTERIOR (combine ranks on the host:
+ *          gb-25_amd/distributed.py combine_stats / combine_diffs);
+ *        - are bitwise repeatable.
+ *      Positions are 1-based (i, j, k) relative to the box (the interior, or the parent with include_halos != 0); among equal
+ *      values the one with the smallest linear offset in memory order (i fastest) is reported, like Julia's findmax.
+ *      min, max, max_abs, sum, sum_sq range over the FINITE values (none: min = +Inf, max = -Inf, max_abs = 0, position 0 0 0);
+ *      first_nonfinite is 0 0 0 when nonfinite == 0.  count = elements of the box. */
+typedef struct {
+  double min, max, max_abs, sum, sum_sq;
+  int64_t count, nonfinite;
+  int32_t at_max_abs[3], first_nonfinite[3], global_offset[3];
+  int32_t reserved;
+} gb25_field_stats;
+/* a: the model's field, b: the other array, delta = a - b formed in fp64.  max_abs_a / sum_sq_a over the finite a, likewise b;
+ * max_abs_delta / sum_sq_delta over the positions where a, b and delta are finite; nonfinite counts the other positions. */
+typedef struct {
+  double max_abs_a, max_abs_b, max_abs_delta, sum_sq_a, sum_sq_b, sum_sq_delta;
+  int64_t count, nonfinite;
+  int32_t at_max_abs_delta[3], global_offset[3];
+} gb25_field_diff;
+/* the interior statistics of u, v, w, eta, T, S; the advective CFL rate [1/s] max(|u|/dx + |v|/dy + |w|/dz) over the interior
+ * cells (multiply by dt for the Courant number; metrics: csrc/diagnostics_kernels.hpp) and its position; the clock */
+typedef struct {
+  gb25_field_stats u, v, w, eta, T, S;
+  double cfl;
+  int32_t at_cfl[3], reserved;
+  int64_t nonfinite_total, iteration;
+  double time;
+} gb25_state_monitor;
+int32_t gb25_field_stats_bytes(void);   /* sizeof the three structs as THIS library was built (like gb25_config_bytes) */
+int32_t gb25_field_diff_bytes(void);
+int32_t gb25_state_monitor_bytes(void);
+gb25_status gb25_get_field_stats(gb25_model *m, gb25_field f, int include_halos, gb25_field_stats *out);
+/* other_dev: a device pointer of this process to elements of other_real_bytes (4: float, 8: double -- whatever this library's
+ * float type is), an array of other_dims (i fastest) at least as large as the box of f; other_origin: its 0-based element that
+ * pairs with the first element of the box (NULL: 0 0 0) -- compare_parent's view(psi2, 1:Nx, 1:Ny, 1:Nz).  The caller orders
+ * the producer of other_dev before the call (gb25_field_device_ptr_readonly does, for a field of another model). */
+gb25_status gb25_compare_field(gb25_model *m, gb25_field f, int include_halos, const void *other_dev, int32_t other_real_bytes,
+                               const int32_t other_dims[3], const int32_t other_origin[3], gb25_field_diff *out);
+gb25_status gb25_get_state_monitor(gb25_model *m, gb25_state_monitor *out);
+/* parent(field) on the device for READING, brought up to date like gb25_get_field and complete when the call returns; nothing
+ * is pinned and no look-ahead is given up.  device_dims: the extents of the array as the device holds it (its pitches; a y-face
+ * field of a folded grid has one row more there than gb25_field_dims reports).  Valid until the next call on m. */
+gb25_status gb25_field_device_ptr_readonly(gb25_model *m, gb25_field f, const void **dev, int32_t device_dims[3]);
 
 /* ---- built-in per-kernel HIP-event timing (bench.py's roofline numbers) */
 gb25_status gb25_profile_enable(gb25_model *m, int on); /* 0: off, 1: every kernel, 2 + k: kernel k alone */

@@ -16,7 +16,8 @@ export Config, Model, create, destroy!, first_time_step!, time_step!, loop!, ini
        fill_halo_regions!, compute_auxiliaries!, compute_tendencies!, ab2_step!, mask_immersed_fields!,
        correct_velocities_and_cache_previous_tendencies!, set_baroclinic_instability!, synchronize,
        parent_array, interior_array, set_parent!, set_interior!, clock, set_dt!, set_option!, get_option,
-       comm_unique_id, comm_init_rccl!, comm_finalize!, set_top_flux!, set_bottom_height!, set_vertical_diffusivity!, set_closure_catke!, CatkeParameters, default_catke_parameters, set_catke_parameters!, set_bottom_drag!, set_tracer_advection_order!, set_prescribed_atmosphere!, compute_atmosphere_ocean_fluxes!, metric2, FIELD, OPTION, METRIC2
+       comm_unique_id, comm_init_rccl!, comm_finalize!, set_top_flux!, set_bottom_height!, set_vertical_diffusivity!, set_closure_catke!, CatkeParameters, default_catke_parameters, set_catke_parameters!, set_bottom_drag!, set_tracer_advection_order!, set_prescribed_atmosphere!, compute_atmosphere_ocean_fluxes!, metric2, FIELD, OPTION, METRIC2,
+       FieldStats, FieldDiff, StateMonitor, field_stats, compare_field, state_monitor, device_pointer_readonly
 
 # One library per Oceananigans float type (src/arg_parsing.jl:12-16): Float32 -> libgb25hip.so, Float64 ->
 # libgb25hip_f64.so; same symbols, gb25_real_bytes() tells them apart.
@@ -313,5 +314,64 @@ function comm_unique_id(::Type{FT} = Float32) where {FT}
 end
 comm_init_rccl!(m::Model, id::Vector{UInt8}) =
     check(m, ccall((:gb25_comm_init_rccl, m.lib), Cint, (Ptr{Cvoid}, Ptr{UInt8}), m.ptr, id), "gb25_comm_init_rccl")
+
+# ---- diagnostics on the device (gb25_get_field_stats / gb25_compare_field / gb25_get_state_monitor): mirrors of the three
+#      result structs of include/gb25.h, checked against the library's gb25_*_bytes before the first use
+struct FieldStats
+    min::Float64; max::Float64; max_abs::Float64; sum::Float64; sum_sq::Float64
+    count::Int64; nonfinite::Int64
+    at_max_abs::NTuple{3, Int32}; first_nonfinite::NTuple{3, Int32}; global_offset::NTuple{3, Int32}
+    reserved::Int32
+end
+struct FieldDiff
+    max_abs_a::Float64; max_abs_b::Float64; max_abs_delta::Float64; sum_sq_a::Float64; sum_sq_b::Float64; sum_sq_delta::Float64
+    count::Int64; nonfinite::Int64
+    at_max_abs_delta::NTuple{3, Int32}; global_offset::NTuple{3, Int32}
+end
+struct StateMonitor
+    u::FieldStats; v::FieldStats; w::FieldStats; eta::FieldStats; T::FieldStats; S::FieldStats
+    cfl::Float64
+    at_cfl::NTuple{3, Int32}; reserved::Int32
+    nonfinite_total::Int64; iteration::Int64
+    time::Float64
+end
+function check_diagnostic_structs(m::Model)
+    sizes = (ccall((:gb25_field_stats_bytes, m.lib), Int32, ()), ccall((:gb25_field_diff_bytes, m.lib), Int32, ()),
+             ccall((:gb25_state_monitor_bytes, m.lib), Int32, ()))
+    sizes == (sizeof(FieldStats), sizeof(FieldDiff), sizeof(StateMonitor)) ||
+        error("gb25_field_stats / gb25_field_diff / gb25_state_monitor are $sizes bytes in the library and " *
+              "$((sizeof(FieldStats), sizeof(FieldDiff), sizeof(StateMonitor))) in GB25HIP.jl: different versions")
+end
+"min, max, max|x| and where (1-based, in the box), sums and non-finite count of a field, reduced on the device; read-only for the schedule."
+function field_stats(m::Model, field::Integer, include_halos::Bool = false)
+    check_diagnostic_structs(m)
+    out = Ref{FieldStats}()
+    check(m, ccall((:gb25_get_field_stats, m.lib), Cint, (Ptr{Cvoid}, Cint, Cint, Ref{FieldStats}), m.ptr, field, include_halos, out),
+          "gb25_get_field_stats")
+    return out[]
+end
+"parent(field) on the device for reading (and the array's extents there): nothing is pinned, valid until the next call on m."
+function device_pointer_readonly(m::Model{FT}, field::Integer) where {FT}
+    p, d = Ref{Ptr{Cvoid}}(C_NULL), zeros(Int32, 3)
+    check(m, ccall((:gb25_field_device_ptr_readonly, m.lib), Cint, (Ptr{Cvoid}, Cint, Ref{Ptr{Cvoid}}, Ptr{Int32}), m.ptr, field, p, d),
+          "gb25_field_device_ptr_readonly")
+    return Ptr{FT}(p[]), Tuple(d)
+end
+"compare_parent / compare_interior (src/correctness.jl:4-26) against a device array of `eltype` (Float32 | Float64), `dims`, from the 0-based `origin`."
+function compare_field(m::Model, field::Integer, include_halos::Bool, other::Ptr, eltype::Type, dims, origin = (0, 0, 0))
+    check_diagnostic_structs(m)
+    out = Ref{FieldDiff}()
+    check(m, ccall((:gb25_compare_field, m.lib), Cint,
+                   (Ptr{Cvoid}, Cint, Cint, Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Int32}, Ref{FieldDiff}),
+                   m.ptr, field, include_halos, other, sizeof(eltype), Int32[dims...], Int32[origin...], out), "gb25_compare_field")
+    return out[]
+end
+"the interior statistics of u, v, w, eta, T, S, the advective CFL rate [1/s] and the clock: the numbers of the progress callback."
+function state_monitor(m::Model)
+    check_diagnostic_structs(m)
+    out = Ref{StateMonitor}()
+    check(m, ccall((:gb25_get_state_monitor, m.lib), Cint, (Ptr{Cvoid}, Ref{StateMonitor}), m.ptr, out), "gb25_get_state_monitor")
+    return out[]
+end
 
 end # module

@@ -29,16 +29,14 @@ while done < a.steps:
     done += a.every
     line = [f"step {done:4d}"]
     bad = False
+    mon = m.backend.state_monitor()      # reduced on the device: no field is downloaded, the schedule is not disturbed
     for n in ("u", "v", "w", "eta", "T"):
-        x = m.backend.get_field(n, False)
-        fin = np.isfinite(x)
-        if not fin.all():
-            idx = np.argwhere(~fin)
-            line.append(f"{n}: {len(idx)} non-finite, first at {idx[0].tolist()}")
+        s = getattr(mon, n)
+        if s.nonfinite:                  # (positions 0-based [i, j, k], as the downloaded arrays were indexed)
+            line.append(f"{n}: {s.nonfinite} non-finite, first at {[q - 1 for q in s.first_nonfinite]}")
             bad = True
         else:
-            k = np.unravel_index(np.argmax(np.abs(x)), x.shape)
-            line.append(f"{n} max {np.abs(x).max():.3e} at {tuple(int(q) for q in k)}")
+            line.append(f"{n} max {s.max_abs:.3e} at {tuple(q - 1 for q in s.at_max_abs)}")
     print("  ".join(line), flush=True)
     if bad:
         break

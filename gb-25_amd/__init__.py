@@ -7,8 +7,9 @@ C ABI of include/gb25.h; this package only sequences calls and moves host arrays
 from .binding import GB25Error, HipBackend, LIB_PATH, load_library
 from .build import build_library
 from .correctness import approx_equal, combine_diffs, combine_stats, compare_states, sync_states
+from .integrals import cell_measure, combine_budgets, combine_moments, fold_records, integrate_host
 from .model import (CATKEVerticalDiffusivity, default_ocean_closure, Field, HydrostaticFreeSurfaceModel, VerticalScalarDiffusivity,
-                    baroclinic_instability_model, first_time_step, initialize,
+                    baroclinic_instability_model, budget, first_time_step, initialize,
                     loop, resolution_to_points, state_monitor, set_baroclinic_instability, set_top_flux, time_step, update_state,
                     tupled_fill_halo_regions_workload, compute_tendencies_workload,
                     compute_boundary_tendencies_workload, compute_interior_momentum_tendencies_workload,

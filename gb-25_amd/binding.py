@@ -56,7 +56,9 @@ ABI_SYMBOLS = [
     "gb25_profile_enable", "gb25_profile_reset", "gb25_profile_get",
     "gb25_field_stats_bytes", "gb25_field_diff_bytes", "gb25_state_monitor_bytes", "gb25_get_field_stats", "gb25_compare_field",
     "gb25_get_state_monitor", "gb25_field_device_ptr_readonly",
+    "gb25_integrate_field", "gb25_get_budget", "gb25_moments_bytes", "gb25_budget_bytes",
 ]
+SUM_SHAPES = {"rows": 0, "levels": 1, "total": 2}   # gb25_sum_shape
 # gb25_option (include/gb25.h)
 OPTION_IDS = {"kernels": 0, "ab2_lookahead": 1, "subcycle_lookahead": 2, "subcycle_block": 3, "fill_fused": 4,
               "two_streams": 5, "store_pressure": 6, "split_tendencies": 7, "pressure_precision": 8, "immersed_kernels": 9, "fold_fills": 10,
@@ -145,6 +147,31 @@ class StateMonitor(_Record):
                 "max|eta|: %.3e m, advective CFL rate: %.3e 1/s at (%d, %d, %d), non-finite: %d"
                 % (self.iteration, self.time, self.u.max_abs, self.v.max_abs, self.w.max_abs, self.T.min, self.T.max,
                    self.S.min, self.S.max, self.eta.max_abs, self.cfl, *self.at_cfl, self.nonfinite_total))
+
+
+class Moments(_Record):
+    """gb25_moments (include/gb25.h): sum mu, sum mu x, sum mu x^2 over the points with mu > 0 and x finite, how many those
+    are, and how many wet points were skipped because x is not finite."""
+    _fields_ = [("measure", C.c_double), ("first", C.c_double), ("second", C.c_double),
+                ("points", C.c_int64), ("nonfinite", C.c_int64)]
+
+
+MOMENTS_DTYPE = np.dtype([("measure", np.float64), ("first", np.float64), ("second", np.float64),
+                          ("points", np.int64), ("nonfinite", np.int64)])
+
+
+class Budget(_Record):
+    """gb25_budget (include/gb25.h): the totals of T, S, u, v, eta and what follows from them."""
+    _fields_ = [("T", Moments), ("S", Moments), ("u", Moments), ("v", Moments), ("eta", Moments),
+                ("volume", C.c_double), ("surface_area", C.c_double), ("kinetic_energy", C.c_double),
+                ("eta_potential_energy", C.c_double), ("iteration", C.c_int64), ("time", C.c_double),
+                ("global_offset", C.c_int32 * 3), ("reserved", C.c_int32)]
+
+    def __str__(self):
+        return ("iter: %d, time: %.6g s, volume: %.9e m3, heat: %.9e, salt: %.9e, kinetic energy: %.6e m5/s2, "
+                "eta: volume %.3e m3, potential energy %.6e m5/s2"
+                % (self.iteration, self.time, self.volume, self.T.first, self.S.first, self.kinetic_energy, self.eta.first,
+                   self.eta_potential_energy))
 
 
 class GB25Error(RuntimeError):
@@ -264,6 +291,8 @@ def load_library(float_type="Float32"):
                                        C.POINTER(FieldDiff)]
     lib.gb25_get_state_monitor.argtypes = [P, C.POINTER(StateMonitor)]
     lib.gb25_field_device_ptr_readonly.argtypes = [P, C.c_int, C.POINTER(P), C.POINTER(C.c_int32)]
+    lib.gb25_integrate_field.argtypes = [P, C.c_int, C.c_int, P, C.c_int64]
+    lib.gb25_get_budget.argtypes = [P, C.POINTER(Budget)]
     lib.gb25_profile_enable.argtypes = [P, C.c_int]
     lib.gb25_profile_get.argtypes = [P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     for name in ["gb25_use_own_stream", "gb25_synchronize", "gb25_set_baroclinic_instability", "gb25_initialize",
@@ -282,7 +311,8 @@ def load_library(float_type="Float32"):
                         f"(gb25_catke_parameters: {lib.gb25_catke_parameters_bytes()} / {C.sizeof(CatkeParameters)}): "
                         "the library and gb25_amd/binding.py are of different versions")
     for fn, struct in (("gb25_field_stats_bytes", FieldStats), ("gb25_field_diff_bytes", FieldDiff),
-                       ("gb25_state_monitor_bytes", StateMonitor)):
+                       ("gb25_state_monitor_bytes", StateMonitor), ("gb25_moments_bytes", Moments),
+                       ("gb25_budget_bytes", Budget)):
         getattr(lib, fn).restype = C.c_int32
         if getattr(lib, fn)() != C.sizeof(struct):
             raise GB25Error(f"{path}: {fn}() = {getattr(lib, fn)()} there, {C.sizeof(struct)} bytes in this binding: "
@@ -410,6 +440,24 @@ class HipBackend:
         """gb25_get_state_monitor: interior statistics of u, v, w, eta, T, S, the advective CFL rate, the clock."""
         out = StateMonitor()
         self._call("gb25_get_state_monitor", C.byref(out))
+        return out
+
+    def integrate_field(self, name, shape="total"):
+        """gb25_integrate_field: sums weighted by the cell measure (include/gb25.h) over the interior, as numpy records of
+        MOMENTS_DTYPE -- shape "rows": [j, k], one per row (zonal sums); "levels": [k]; "total": one record."""
+        d = (C.c_int32 * 3)()
+        if self.lib.gb25_field_dims(self.h, FIELD_IDS[name], 0, d) != 0:
+            raise GB25Error(f"integrate_field: this model has no such field: {name!r} (closure = CATKEVerticalDiffusivity() only)")
+        by, bz = d[1], d[2]
+        n = {"rows": by * bz, "levels": bz, "total": 1}[shape]
+        out = np.zeros(n, MOMENTS_DTYPE)
+        self._call("gb25_integrate_field", FIELD_IDS[name], SUM_SHAPES[shape], out.ctypes.data_as(C.c_void_p), n)
+        return out.reshape(bz, by).T if shape == "rows" else out if shape == "levels" else out[0]
+
+    def budget(self):
+        """gb25_get_budget: the totals of T, S, u, v, eta, volume, surface area, kinetic and free-surface potential energy."""
+        out = Budget()
+        self._call("gb25_get_budget", C.byref(out))
         return out
 
     def metric(self, name, index=1):

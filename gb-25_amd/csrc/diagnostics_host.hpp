@@ -1,5 +1,5 @@
 // diagnostics_host.hpp -- host side of gb25_get_field_stats / gb25_compare_field / gb25_get_state_monitor /
-// gb25_field_device_ptr_readonly (include/gb25.h); the last part of gb25_api.hip, which includes it.  Kernels:
+// gb25_field_device_ptr_readonly / gb25_integrate_field / gb25_get_budget (include/gb25.h); the last part of gb25_api.hip, which includes it.  Kernels:
 // diagnostics_kernels.hpp.  Nothing here writes model memory or a schedule flag: the calls may sit between any two steps.
 #pragma once
 
@@ -108,6 +108,135 @@ void diag_fill_stats(const gb25_model* m, gb25_field id, const StatsPartial& p, 
 gb25_status diag_check_box(gb25_model* m, const DiagBox& b) {
   if (b.bx <= 0 || b.by <= 0 || b.bz <= 0) return fail(m, GB25_ERR_INVALID_ARGUMENT, "the field has an empty box");
   if ((size_t)diag_blocks(b) > m->diag_scratch_records) return fail(m, GB25_ERR_STATE, "diagnostics: the box needs more per-block records than the model's scratch buffer holds");
+  return GB25_OK;
+}
+
+// ---- integrals: the measure's location of a field, diagnostics' own tables, the records' buffer
+static_assert(sizeof(MomentsPartial) == sizeof(gb25_moments), "a row record is a gb25_moments");
+
+MomentLoc moments_loc(int id) {
+  const bool flat = is_2d(id);
+  if (is_v_shaped(id)) return flat ? LOC_CF : LOC_CFC;
+  switch (id) {
+    case GB25_U: case GB25_GN_U: case GB25_GM_U: case GB25_PREV_U: return LOC_FCC;
+    case GB25_BT_U: case GB25_U_BAR: case GB25_GN_BT_U: return LOC_FC;
+    case GB25_W: case GB25_KAPPA_U: case GB25_KAPPA_C: case GB25_KAPPA_E: return LOC_CCF;
+    default: return flat ? LOC_CC : LOC_CCC;
+  }
+}
+
+// areas by location as `real` (what gb25_get_metric2 returns, rounded back: exact) and the first wet level per column and
+// location, from the host's tables; parent layout of a (c,f) field
+gb25_status moments_tables(gb25_model* m) {
+  if (m->diag_tables_valid) return GB25_OK;
+  const int Nx = m->Nx, Ny = m->Ny, Nz = m->cfg.Nz, H = m->cfg.halo, sx = Nx + 2 * H, sy = Ny + 2 * H + 1;
+  const size_t n2 = (size_t)sx * sy;
+  for (int q = 0; q < 3; q++) {
+    if (m->diag_area[q]) HIPCHK(hipFree(m->diag_area[q]));
+    if (m->diag_first_wet[q]) HIPCHK(hipFree(m->diag_first_wet[q]));
+    m->diag_area[q] = nullptr;
+    m->diag_first_wet[q] = nullptr;
+  }
+  if (m->g.cv.on) {
+    static const int ids[3] = {GB25_M2_AZCC, GB25_M2_AZFC, GB25_M2_AZCF};
+    std::vector<real> a(n2);
+    for (int q = 0; q < 3; q++) {
+      const std::vector<double>& h = m->h_curv[ids[q]];
+      if (h.size() != n2) return fail(m, GB25_ERR_STATE, "integrals: the curvilinear metrics are not built");
+      for (size_t o = 0; o < n2; o++) a[o] = (real)h[o];
+      HIPCHK(hipMalloc(&m->diag_area[q], n2 * sizeof(real)));
+      HIPCHK(hipMemcpy(m->diag_area[q], a.data(), n2 * sizeof(real), hipMemcpyHostToDevice));
+    }
+  }
+  if (!m->kbot.empty()) {
+    const int E = m->kb_E, ksx = Nx + 2 * E;
+    auto kb = [&](int ii, int jj) {   // (gb25_get_bottom_info's: clamped at the walls, a neighbour's row otherwise)
+      const int jl = std::min(std::max(jj + m->j0, 0), m->cfg.Ny - 1) - m->j0;
+      return m->kbot[(size_t)(ii + E) + (size_t)ksx * (std::min(std::max(jl, -m->kb_Ey), Ny + m->kb_Ey - 1) + m->kb_Ey)];
+    };
+    std::vector<unsigned short> f(n2);
+    for (int q = 0; q < 3; q++) {
+      std::fill(f.begin(), f.end(), MOMENTS_DRY);
+      for (int j = 0; j <= Ny; j++) {
+        if (j == Ny && q != 2) continue;   // (only y faces have a row Ny)
+        for (int i = 0; i < Nx; i++) {
+          const int k = q == 0 ? kb(i, j) : q == 1 ? std::max(kb(i - 1, j), kb(i, j)) : std::max(kb(i, j - 1), kb(i, j));
+          f[(size_t)(i + H) + (size_t)sx * (j + H)] = k < Nz ? (unsigned short)k : MOMENTS_DRY;
+        }
+      }
+      HIPCHK(hipMalloc(&m->diag_first_wet[q], n2 * sizeof(unsigned short)));
+      HIPCHK(hipMemcpy(m->diag_first_wet[q], f.data(), n2 * sizeof(unsigned short), hipMemcpyHostToDevice));
+    }
+  }
+  m->diag_tables_valid = true;
+  return GB25_OK;
+}
+
+// once per model: MOMENTS_SLOTS sets of row records for the tallest interior a field of this model has, their level records,
+// their totals
+gb25_status moments_buffer(gb25_model* m) {
+  if (m->diag_moments) return GB25_OK;
+  const size_t levels = (size_t)m->cfg.Nz + 1, rows = (size_t)(m->Ny + 1) * levels;
+  HIPCHK(hipMalloc(&m->diag_moments, (size_t)MOMENTS_SLOTS * (rows + levels + 1) * sizeof(MomentsPartial)));
+  m->diag_moments_rows = rows;
+  m->diag_moments_levels = levels;
+  return GB25_OK;
+}
+inline MomentsPartial* moments_rows(gb25_model* m, int slot) { return (MomentsPartial*)m->diag_moments + m->diag_moments_rows * slot; }
+inline MomentsPartial* moments_levels(gb25_model* m, int slot) {
+  return (MomentsPartial*)m->diag_moments + m->diag_moments_rows * MOMENTS_SLOTS + m->diag_moments_levels * slot;
+}
+inline MomentsPartial* moments_totals(gb25_model* m) {
+  return (MomentsPartial*)m->diag_moments + (m->diag_moments_rows + m->diag_moments_levels) * MOMENTS_SLOTS;
+}
+gb25_status moments_check_box(gb25_model* m, const DiagBox& b) {
+  if (b.bx <= 0 || b.by <= 0 || b.bz <= 0) return fail(m, GB25_ERR_INVALID_ARGUMENT, "the field has an empty box");
+  if ((size_t)b.by * b.bz > m->diag_moments_rows || (size_t)b.bz > m->diag_moments_levels)
+    return fail(m, GB25_ERR_STATE, "integrals: the box needs more row records than the model's buffer holds");
+  return GB25_OK;
+}
+
+template <int LOC>
+void moments_launch_loc(gb25_model* m, const MomentsTables& tab, const real* src, const DiagBox& b, MomentsPartial* rows) {
+  const long long nb = ((long long)b.by * b.bz + DIAG_THREADS / 64 - 1) / (DIAG_THREADS / 64);
+  hipLaunchKernelGGL((k_field_moments<real, LOC>), dim3((unsigned)nb), dim3(DIAG_THREADS), 0, m->stream, m->g, tab, src, b, rows);
+}
+// the row records of field id into slot `slot`
+gb25_status moments_launch(gb25_model* m, gb25_field id, const real* src, const DiagBox& b, int slot) {
+  MomentsTables tab;
+  for (int q = 0; q < 3; q++) {
+    tab.area[q] = m->diag_area[q];
+    tab.first[q] = m->diag_first_wet[q];
+  }
+  tab.pivot_row = (m->cfg.grid_type >= GB25_GRID_TRIPOLAR && !m->yn_open) ? m->Ny - 1 : -1;
+  MomentsPartial* rows = moments_rows(m, slot);
+  switch (moments_loc(id)) {
+    case LOC_CCC: moments_launch_loc<LOC_CCC>(m, tab, src, b, rows); break;
+    case LOC_FCC: moments_launch_loc<LOC_FCC>(m, tab, src, b, rows); break;
+    case LOC_CFC: moments_launch_loc<LOC_CFC>(m, tab, src, b, rows); break;
+    case LOC_CCF: moments_launch_loc<LOC_CCF>(m, tab, src, b, rows); break;
+    case LOC_CC: moments_launch_loc<LOC_CC>(m, tab, src, b, rows); break;
+    case LOC_FC: moments_launch_loc<LOC_FC>(m, tab, src, b, rows); break;
+    case LOC_CF: moments_launch_loc<LOC_CF>(m, tab, src, b, rows); break;
+  }
+  LAUNCHCHK();
+  return GB25_OK;
+}
+// rows -> levels -> totals of the first n slots, two launches
+gb25_status moments_fold(gb25_model* m, const DiagBox* b, int n) {
+  MomentsFold f = {}, t = {};
+  int most = 0;
+  for (int s = 0; s < n; s++) {
+    f.len[s] = b[s].by; f.n[s] = b[s].bz;
+    t.len[s] = b[s].bz; t.n[s] = 1;
+    most = std::max(most, b[s].bz);
+  }
+  hipLaunchKernelGGL(k_moments_fold, dim3(most, n), dim3(64), 0, m->stream, (const MomentsPartial*)moments_rows(m, 0),
+                     (long long)m->diag_moments_rows, f, moments_levels(m, 0), (long long)m->diag_moments_levels);
+  LAUNCHCHK();
+  hipLaunchKernelGGL(k_moments_fold, dim3(1, n), dim3(64), 0, m->stream, (const MomentsPartial*)moments_levels(m, 0),
+                     (long long)m->diag_moments_levels, t, moments_totals(m), 1LL);
+  LAUNCHCHK();
   return GB25_OK;
 }
 
@@ -228,6 +357,72 @@ gb25_status gb25_get_state_monitor(gb25_model* m, gb25_state_monitor* out) {
   diag_position(c.cfl < 0 ? DIAG_NONE : c.at, b[0], out->at_cfl);
   out->iteration = m->iteration;
   out->time = m->time;
+  return GB25_OK;
+}
+
+int32_t gb25_moments_bytes(void) { return (int32_t)sizeof(gb25_moments); }
+int32_t gb25_budget_bytes(void) { return (int32_t)sizeof(gb25_budget); }
+
+gb25_status gb25_integrate_field(gb25_model* m, gb25_field f, gb25_sum_shape shape, gb25_moments* out, int64_t count) {
+  if (!m || !out) return GB25_ERR_INVALID_ARGUMENT;
+  if (shape != GB25_SUM_ROWS && shape != GB25_SUM_LEVELS && shape != GB25_SUM_TOTAL)
+    return fail(m, GB25_ERR_INVALID_ARGUMENT, "gb25_integrate_field: shape must be GB25_SUM_ROWS, GB25_SUM_LEVELS or GB25_SUM_TOTAL, got %d", (int)shape);
+  const real* src = nullptr;
+  DiagBox b;
+  if (gb25_status s = diag_source(m, f, &src)) return s;
+  if (gb25_status s = diag_box(m, f, 0, &b)) return s;
+  const int64_t want = shape == GB25_SUM_ROWS ? (int64_t)b.by * b.bz : shape == GB25_SUM_LEVELS ? (int64_t)b.bz : 1;
+  if (count != want)
+    return fail(m, GB25_ERR_INVALID_ARGUMENT, "gb25_integrate_field: this shape of this field has %lld records (rows %d, levels %d), count is %lld",
+                (long long)want, b.by, b.bz, (long long)count);
+  if (gb25_status s = moments_buffer(m)) return s;
+  if (gb25_status s = moments_check_box(m, b)) return s;
+  if (gb25_status s = diag_wait_for_model(m)) return s;
+  if (gb25_status s = moments_tables(m)) return s;
+  {
+    Timed t(m, GB25_K_DIAGNOSTICS);
+    if (gb25_status s = moments_launch(m, f, src, b, 0)) return s;
+    if (shape != GB25_SUM_ROWS)
+      if (gb25_status s = moments_fold(m, &b, 1)) return s;
+  }
+  const MomentsPartial* from = shape == GB25_SUM_ROWS ? moments_rows(m, 0) : shape == GB25_SUM_LEVELS ? moments_levels(m, 0) : moments_totals(m);
+  HIPCHK(hipMemcpyAsync(out, from, (size_t)count * sizeof(gb25_moments), hipMemcpyDeviceToHost, m->stream));
+  HIPCHK(hipStreamSynchronize(m->stream));
+  return GB25_OK;
+}
+
+gb25_status gb25_get_budget(gb25_model* m, gb25_budget* out) {
+  if (!m || !out) return GB25_ERR_INVALID_ARGUMENT;
+  static const gb25_field ids[MOMENTS_SLOTS] = {GB25_T, GB25_S, GB25_U, GB25_V, GB25_ETA};
+  const real* src[MOMENTS_SLOTS];
+  DiagBox b[MOMENTS_SLOTS];
+  for (int q = 0; q < MOMENTS_SLOTS; q++) {
+    if (gb25_status s = diag_source(m, ids[q], &src[q])) return s;
+    if (gb25_status s = diag_box(m, ids[q], 0, &b[q])) return s;
+  }
+  if (gb25_status s = moments_buffer(m)) return s;
+  for (int q = 0; q < MOMENTS_SLOTS; q++)
+    if (gb25_status s = moments_check_box(m, b[q])) return s;
+  if (gb25_status s = diag_wait_for_model(m)) return s;
+  if (gb25_status s = moments_tables(m)) return s;
+  {
+    Timed t(m, GB25_K_DIAGNOSTICS);
+    for (int q = 0; q < MOMENTS_SLOTS; q++)
+      if (gb25_status s = moments_launch(m, ids[q], src[q], b[q], q)) return s;
+    if (gb25_status s = moments_fold(m, b, MOMENTS_SLOTS)) return s;
+  }
+  gb25_moments tot[MOMENTS_SLOTS];
+  HIPCHK(hipMemcpyAsync(tot, moments_totals(m), sizeof tot, hipMemcpyDeviceToHost, m->stream));
+  HIPCHK(hipStreamSynchronize(m->stream));
+  memset(out, 0, sizeof *out);
+  out->T = tot[0]; out->S = tot[1]; out->u = tot[2]; out->v = tot[3]; out->eta = tot[4];
+  out->volume = out->T.measure;
+  out->surface_area = out->eta.measure;
+  out->kinetic_energy = 0.5 * (out->u.second + out->v.second);
+  out->eta_potential_energy = 0.5 * m->cfg.g * out->eta.second;
+  out->iteration = m->iteration;
+  out->time = m->time;
+  diag_global_offset(m, GB25_T, 0, out->global_offset);
   return GB25_OK;
 }
 

@@ -277,6 +277,116 @@ __global__ __launch_bounds__(DIAG_THREADS) void k_advective_cfl(Grid g, const re
   if (threadIdx.x == 0) partials[blockIdx.x] = p;
 }
 
+// ---- integrals (gb25_integrate_field, gb25_get_budget): sums weighted by the measure mu = A dz fold wet of include/gb25.h.
+//   k_field_moments<T, LOC>  one pass over the interior box of a field at location LOC: ONE WAVE takes ONE ROW (j, k); a lane takes
+//                     every 64th chunk of four elements (diag_load4, cut like k_field_stats' chunks) and accumulates sum mu,
+//                     sum mu x, sum mu x^2 in fp64 in the order of its elements; the fixed shuffle tree combines the lanes and
+//                     lane 0 stores the row's record (plain vector stores): rows[j + by k].  The area comes from the row tables
+//                     of the LatitudeLongitudeGrid (one number per row) or from a 2-D table of diagnostics' own (curvilinear
+//                     grids), the first wet level per column and location from a 2-D table of 16-bit numbers of diagnostics' own
+//                     (none on a grid without a bottom); all of them in the parent layout of a (c,f) field, so that a row of a
+//                     table is cut into the same chunks as the row of the field.  4 / 8 bytes per element plus the tables.
+//   k_moments_fold    one wave per level: the level's row records, 64 at a time through LDS, added by lane 0 LEFT TO RIGHT in j;
+//                     launched a second time over the levels it adds them left to right in k: the total.
+enum MomentLoc { LOC_CCC = 0, LOC_FCC, LOC_CFC, LOC_CCF, LOC_CC, LOC_FC, LOC_CF };
+constexpr unsigned short MOMENTS_DRY = 0xffff;   // first wet level of a column that has none
+constexpr int MOMENTS_SLOTS = 5;                  // fields a budget reduces before one fold
+
+struct MomentsPartial {   // = gb25_moments
+  double measure, first, second;
+  long long points, nonfinite;
+};
+__device__ __forceinline__ MomentsPartial diag_combine(MomentsPartial a, const MomentsPartial& b) {
+  a.measure += b.measure;
+  a.first += b.first;
+  a.second += b.second;
+  a.points += b.points;
+  a.nonfinite += b.nonfinite;
+  return a;
+}
+// diagnostics' own tables, by horizontal location (c,c), (f,c), (c,f): parent layout of a (c,f) field (pitch g.sx, row j + H)
+struct MomentsTables {
+  const real* area[3];              // null: the row tables of the LatitudeLongitudeGrid
+  const unsigned short* first[3];   // first wet level of the column (MOMENTS_DRY: none); null: every level of every column is wet
+  int pivot_row;                    // local row of the GLOBAL pivot row of a folded grid on this rank, else -1
+};
+
+template <class T, int LOC>
+__global__ __launch_bounds__(DIAG_THREADS) void k_field_moments(Grid g, MomentsTables tab, const T* __restrict__ a, DiagBox box,
+                                                                MomentsPartial* __restrict__ rows) {
+  constexpr int HL = (LOC == LOC_FCC || LOC == LOC_FC) ? 1 : (LOC == LOC_CFC || LOC == LOC_CF) ? 2 : 0;
+  constexpr bool FLAT = LOC >= LOC_CC;
+  const long long r = (long long)blockIdx.x * (DIAG_THREADS / 64) + (threadIdx.x >> 6);
+  if (r >= (long long)box.by * box.bz) return;
+  const int lane = threadIdx.x & 63;
+  const int k = (int)(r / box.by), j = (int)(r - (long long)k * box.by);
+  MomentsPartial p = {0.0, 0.0, 0.0, 0, 0};
+  const bool wall = HL == 2 && (j == g.jws || (j == g.jwn && !g.cv.north_fold));   // (a y face on a wall of the GLOBAL grid)
+  if (!wall) {
+    const T* row = a + (box.origin + box.pitch * j + box.plane * k);
+    const double dz = FLAT ? 1.0 : (double)(LOC == LOC_CCF ? g.dzf[k] : g.dzc[k]);
+    const double fold = (HL != 2 && j == tab.pivot_row) ? 0.5 : 1.0;
+    const int level = FLAT ? g.Nz - 1 : k;   // wet: level >= the column's first wet level
+    const real* ra = tab.area[HL] ? tab.area[HL] + i2(g, 0, j) : nullptr;
+    const unsigned short* rf = tab.first[HL] ? tab.first[HL] + i2(g, 0, j) : nullptr;
+    const double mu_row = ra ? 0.0 : ((double)(HL == 2 ? g.azf[j] : g.azc[j]) * dz) * fold;
+    const int mis = diag_misalignment(row), nchunks = (mis + box.bx + 3) >> 2;
+    for (int c = lane; c < nchunks; c += 64) {
+      const int x0 = 4 * c - mis;
+      T e[4];
+      real ea[4];
+      unsigned short ef[4];
+      diag_load4(row, x0, box.bx, e);
+      if (ra) diag_load4(ra, x0, box.bx, ea);
+      if (rf) diag_load4(rf, x0, box.bx, ef);
+#pragma unroll
+      for (int s = 0; s < 4; s++) {
+        const int x = x0 + s;
+        if (x < 0 || x >= box.bx) continue;
+        const double mu = (rf && level < (int)ef[s]) ? 0.0 : (ra ? ((double)ea[s] * dz) * fold : mu_row);
+        if (!(mu > 0.0)) continue;
+        const double v = (double)e[s];
+        if (__builtin_isfinite(v)) {
+          const double t = mu * v;
+          p.measure += mu;
+          p.first += t;
+          p.second = __builtin_fma(t, v, p.second);
+          p.points++;
+        } else {
+          p.nonfinite++;
+        }
+      }
+    }
+    p = diag_wave_reduce(p);
+  }
+  if (lane == 0) rows[r] = p;
+}
+
+// slot s (blockIdx.y) holds n[s] groups (blockIdx.x) of len[s] records each, group q at in + in_stride s + len[s] q; its sum,
+// left to right, goes to out[out_stride s + q].  One wave per group.
+struct MomentsFold {
+  int len[MOMENTS_SLOTS], n[MOMENTS_SLOTS];
+};
+__global__ __launch_bounds__(64) void k_moments_fold(const MomentsPartial* __restrict__ in, long long in_stride, MomentsFold f,
+                                                     MomentsPartial* __restrict__ out, long long out_stride) {
+  __shared__ MomentsPartial lds[64];
+  const int s = blockIdx.y, q = blockIdx.x, lane = threadIdx.x;
+  if (q >= f.n[s]) return;   // (uniform for the block)
+  const int len = f.len[s];
+  const MomentsPartial* src = in + in_stride * s + (long long)len * q;
+  MomentsPartial p = {0.0, 0.0, 0.0, 0, 0};
+  for (int base = 0; base < len; base += 64) {
+    if (base + lane < len) lds[lane] = src[base + lane];
+    __syncthreads();
+    if (lane == 0) {
+      const int m = len - base < 64 ? len - base : 64;
+      for (int t = 0; t < m; t++) p = diag_combine(p, lds[t]);
+    }
+    __syncthreads();
+  }
+  if (lane == 0) out[out_stride * s + q] = p;
+}
+
 // one block: the records of the first launch in index order -- thread t takes t, t + 256, ... --, then the block's tree
 template <class P>
 __global__ __launch_bounds__(DIAG_THREADS) void k_diag_finish(const P* __restrict__ partials, int n, P* __restrict__ out) {

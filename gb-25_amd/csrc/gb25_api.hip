@@ -233,6 +233,14 @@ struct gb25_model {
   void* diag_scratch = nullptr;
   size_t diag_scratch_records = 0;
   int prof_redirect = -1;
+  // integrals (gb25_integrate_field, gb25_get_budget): the row, level and total records of up to five fields, and diagnostics'
+  // own tables by horizontal location -- areas (curvilinear grids) and first wet levels (grids with a bottom table) --, made by
+  // the first call that needs them, dropped whenever the grid or the bottom is rebuilt.  No stepping kernel reads them.
+  void* diag_moments = nullptr;
+  size_t diag_moments_rows = 0, diag_moments_levels = 0;
+  real* diag_area[3] = {nullptr, nullptr, nullptr};
+  unsigned short* diag_first_wet[3] = {nullptr, nullptr, nullptr};
+  bool diag_tables_valid = false;
 };
 
 namespace {
@@ -374,6 +382,7 @@ gb25_status upload_table(gb25_model* m, const std::vector<double>& h, int off, c
 }
 
 gb25_status build_grid(gb25_model* m) {
+  m->diag_tables_valid = false;   // (the integrals' own tables follow the grid: rebuilt by the next call that needs them)
   const gb25_config& c = m->cfg;
   const int H = c.halo, Ny = m->Ny, Nz = c.Nz;
   // (the row tables of a rank of a 2-D decomposition also cover the rows its sub-cycle is widened by)
@@ -611,6 +620,7 @@ void curv_metrics_at(const gb25_model* m, int ig, int j, double out[GB25_M2_COUN
 // Fills m->h_curv (the local slab's columns, halo columns by their own global index) and uploads what the kernels read
 // (device_common.hpp, Curv).
 gb25_status build_curv_grid(gb25_model* m) {
+  m->diag_tables_valid = false;   // (the integrals' own tables follow the grid: rebuilt by the next call that needs them)
   const gb25_config& c = m->cfg;
   const int Nx = m->Nx, Ny = m->Ny, H = c.halo, sx = Nx + 2 * H, sy = Ny + 2 * H + 1;
   const size_t n2 = (size_t)sx * sy;
@@ -771,6 +781,7 @@ void build_substeps(gb25_model* m) {
 // by cell (inactive_cell / stencil_active) and tests/test_gpu_immersed.py compares the two.
 template <class ZB>
 gb25_status build_bottom(gb25_model* m, ZB zb) {
+  m->diag_tables_valid = false;   // (the integrals' own tables follow the grid: rebuilt by the next call that needs them)
   const gb25_config& c = m->cfg;
   const int Nx = m->Nx, Ny = m->Ny, Nz = c.Nz, H = c.halo, offk = m->metric_off_k, j0 = m->j0;
   const int E = std::max(H, m->W) + 4, ksx = Nx + 2 * E;
@@ -2690,6 +2701,11 @@ void gb25_destroy(gb25_model* m) {
       if (p->d) hipFree(p->d);
   if (m->uv_partials) hipFree(m->uv_partials);
   if (m->diag_scratch) hipFree(m->diag_scratch);
+  if (m->diag_moments) hipFree(m->diag_moments);
+  for (int q = 0; q < 3; q++) {
+    if (m->diag_area[q]) hipFree(m->diag_area[q]);
+    if (m->diag_first_wet[q]) hipFree(m->diag_first_wet[q]);
+  }
   if (m->wbase) hipFree(m->wbase);
   for (auto p : m->d_ord)
     if (p) hipFree(p);

@@ -211,6 +211,15 @@ class LocalSlabEnsemble:
         out.iteration, out.time = mons[0].iteration, mons[0].time
         return out
 
+    # integrals: likewise (gb-25_amd/integrals.py)
+    def integrate_field(self, name, shape="total"):
+        from .integrals import combine_moments
+        return combine_moments([b.integrate_field(name, shape) for b in self.backends], [b.ry * self.Ny_loc for b in self.backends])
+
+    def budget(self):
+        from .integrals import combine_budgets
+        return combine_budgets([b.budget() for b in self.backends])
+
     def set_option(self, name, value):
         for b in self.backends:
             b.set_option(name, value)

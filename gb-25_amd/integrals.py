@@ -1,0 +1,186 @@
+"""Volume-weighted integrals on the host: the cell measure of include/gb25.h restated with numpy from a backend's public
+getters, the host fallback of gb25_integrate_field, and the arithmetic that combines the records of the ranks of a
+decomposition (every rank integrates its own interior on the device; nothing here is collective).
+
+    mu(i, j, k) = A_loc(i, j) * dz_loc(k) * fold(j) * wet_loc(i, j, k)
+
+    location  fields                                    A                         dz      wet
+    (c,c,c)   T, S, e, pHY, Gn/Gm of T, S, e, Le        azcc (lat-lon: azc(j))    dzc(k)  k >= kbot(i,j)
+    (f,c,c)   u, Gn/Gm u, previous_u                    azfc (lat-lon: azc(j))    dzc(k)  k >= max(kbot(i-1,j), kbot(i,j))
+    (c,f,c)   v, Gn/Gm v, previous_v                    azcf (lat-lon: azf(j))    dzc(k)  k >= max(kbot(i,j-1), kbot(i,j)); 0 on a global wall row
+    (c,c,f)   w, kappa_u, kappa_c, kappa_e              as (c,c,c)                dzf(k)  cell k or cell k-1 is wet
+    2-D       eta, eta_bar, Jb / U, U_bar, Gn.U / V...  as the 3-D location       1       the column has a wet level
+
+fold(j) = 1/2 on the global pivot row (the last row of cell centres) of a folded grid for the locations whose rows are rows of
+cell centres, 1 elsewhere.  Works on any backend that has metric, metric2, bottom_info, field_dims, get_field and cfg.grid_type
+(binding.HipBackend; the test suite's oracle backend)."""
+import numpy as np
+
+from .binding import Budget, MOMENTS_DTYPE, Moments
+
+_FC = ("u", "Gn.u", "Gm.u", "previous_u", "U", "U_bar", "Gn.U")
+_CF = ("v", "Gn.v", "Gm.v", "previous_v", "V", "V_bar", "Gn.V")
+_FACES_Z = ("w", "kappa_u", "kappa_c", "kappa_e")
+_FLAT = ("eta", "U", "V", "eta_bar", "U_bar", "V_bar", "Gn.U", "Gn.V", "Jb")
+FOLDED_GRID_TYPES = (3, 4)      # gb25_grid_type: tripolar, tripolar with the Gaussian islands
+LAT_LON_GRID_TYPES = (0, 1)     # row tables; the others have 2-D metrics
+
+
+def location(name):
+    """(horizontal, vertical) location of a field: horizontal "cc" | "fc" | "cf"; vertical "c" | "f" | None (2-D)."""
+    h = "fc" if name in _FC else "cf" if name in _CF else "cc"
+    return h, None if name in _FLAT else "f" if name in _FACES_Z else "c"
+
+
+def _halo(backend):
+    return int(getattr(backend.cfg, "halo", getattr(backend.cfg, "H", 0)))
+
+
+def _area(backend, hloc, Nx, by):
+    if backend.cfg.grid_type in LAT_LON_GRID_TYPES:
+        row = np.array([backend.metric("azf" if hloc == "cf" else "azc", j) for j in range(1, by + 1)], np.float64)
+        return np.broadcast_to(row[None, :], (Nx, by))
+    name = "az" + hloc
+    try:
+        H = _halo(backend)
+        return np.asarray(backend.metric2(name), np.float64)[H:H + Nx, H:H + by]
+    except TypeError:          # (a backend whose metric2 answers point by point)
+        return np.array([[backend.metric2(name, i, j) for j in range(1, by + 1)] for i in range(1, Nx + 1)], np.float64)
+
+
+def _first_wet(backend, hloc, Nx, Ny, by, Nz):
+    """First wet level (0-based) of every column of the location; Nz: none."""
+    kb = np.array([[backend.bottom_info("kbot", i, j) for j in range(1, Ny + 1)] for i in range(1, Nx + 1)]).astype(int)
+    if hloc == "cc":
+        return kb
+    zf = np.array([backend.metric("zf", k) for k in range(1, Nz + 2)], np.float64)
+    depths = zf[Nz] - zf      # static depth of a column whose first wet level is k
+
+    def from_depth(which, i, j):          # the face's column depth is that of the shallower of its two columns
+        return int(np.argmin(np.abs(depths - backend.bottom_info(which, i, j))))
+
+    if hloc == "fc":
+        west = np.roll(kb, 1, axis=0)     # periodic x ...
+        if getattr(backend, "Rx", 1) > 1:  # ... or the neighbour rank's column
+            west[0, :] = [from_depth("Hfc", 1, j) for j in range(1, Ny + 1)]
+        return np.maximum(west, kb)
+    south = np.concatenate([kb[:, :1], kb[:, :-1]], axis=1)
+    out = np.maximum(south, kb)
+    if getattr(backend, "ry", 0) > 0:       # the southern neighbour rank's row
+        out[:, 0] = [from_depth("Hcf", i, 1) for i in range(1, Nx + 1)]
+    if by == Ny + 1:                         # (the row of the northern wall: dry, below)
+        out = np.concatenate([out, kb[:, -1:]], axis=1)
+    return out
+
+
+def cell_measure(backend, name):
+    """mu of every interior point of the field, float64, shaped like get_field(name, include_halos=False)."""
+    hloc, vloc = location(name)
+    Nx, by, bz = backend.field_dims(name, False)
+    Ny, Nz = backend.field_dims("T", False)[1:]
+    A = _area(backend, hloc, Nx, by)
+    if vloc is None:
+        dz = np.ones(1)
+    else:
+        dz = np.array([backend.metric("dzc" if vloc == "c" else "dzf", k) for k in range(1, bz + 1)], np.float64)
+    fold = np.ones(by)
+    top_rank = getattr(backend, "ry", 0) == getattr(backend, "Ry", 1) - 1
+    if backend.cfg.grid_type in FOLDED_GRID_TYPES and top_rank and hloc != "cf":
+        fold[Ny - 1] = 0.5
+    first = _first_wet(backend, hloc, Nx, Ny, by, Nz)
+    if vloc is None:
+        wet = (first < Nz)[:, :, None]
+    else:
+        wet = (np.arange(bz)[None, None, :] >= first[:, :, None]) & (first < Nz)[:, :, None]
+    wet = np.array(np.broadcast_to(wet, (Nx, by, bz)))
+    if hloc == "cf":
+        if getattr(backend, "ry", 0) == 0:
+            wet[:, 0, :] = False             # the southern wall of the global grid
+        if by == Ny + 1:
+            wet[:, Ny, :] = False            # the northern wall (a folded grid and a rank below a neighbour hold no such row)
+    return ((A[:, :, None] * dz[None, None, :]) * fold[None, :, None]) * wet
+
+
+def _records(shape):
+    return np.zeros(shape, MOMENTS_DTYPE)
+
+
+def integrate_host(backend, name, shape="total"):
+    """What HipBackend.integrate_field returns, computed with numpy from the downloaded field and cell_measure: the fallback
+    for a backend without the device reduction.  Rows are summed by numpy; levels and the total add them left to right."""
+    x = np.asarray(backend.get_field(name, False), np.float64)
+    mu = cell_measure(backend, name)
+    wet = mu > 0
+    ok = wet & np.isfinite(x)
+    xs = np.where(ok, x, 0.0)
+    ms = np.where(ok, mu, 0.0)
+    rows = _records(x.shape[1:])
+    rows["measure"] = ms.sum(axis=0)
+    rows["first"] = (ms * xs).sum(axis=0)
+    rows["second"] = ((ms * xs) * xs).sum(axis=0)
+    rows["points"] = ok.sum(axis=0)
+    rows["nonfinite"] = (wet & ~ok).sum(axis=0)
+    if shape == "rows":
+        return rows
+    levels = fold_records(rows)
+    return levels if shape == "levels" else fold_records(levels)
+
+
+def fold_records(records):
+    """The left-to-right sum over the first axis, member by member: LEVELS from ROWS [j, k], TOTAL from LEVELS [k] --
+    the order of k_moments_fold, so the result equals the device's bit for bit."""
+    records = np.asarray(records)
+    out = _records(records.shape[1:])
+    for f in MOMENTS_DTYPE.names:
+        out[f] = np.add.accumulate(records[f], axis=0)[-1]
+    return out if out.shape else out[()]
+
+
+def combine_moments(parts, row_offsets=None):
+    """The records of the ranks of a decomposition (HipBackend.integrate_field of every rank, the same shape) added in rank
+    order.  Totals and levels add.  Rows [j, k]: ranks with the same row_offsets entry (the global index of their first row)
+    hold the same rows and add -- x slabs; ranks with different entries are stacked in y by them -- a mesh.  A row of y faces
+    on the seam between two ranks belongs to the northern one alone, so the stacked rows are the single domain's rows."""
+    parts = [np.asarray(p) for p in parts]
+    if row_offsets is None:
+        row_offsets = [0] * len(parts)
+    bands = {}
+    for p, o in zip(parts, row_offsets):
+        if o in bands:
+            acc = bands[o]
+            for f in MOMENTS_DTYPE.names:
+                acc[f] = acc[f] + p[f]
+        else:
+            bands[o] = p.astype(MOMENTS_DTYPE, copy=True)
+    ordered = [bands[o] for o in sorted(bands)]
+    if len(ordered) == 1:
+        out = ordered[0]
+    elif ordered[0].ndim == 2:
+        out = np.concatenate(ordered, axis=0)
+    else:                         # totals / levels of a mesh: bands add, south to north
+        out = ordered[0]
+        for p in ordered[1:]:
+            for f in MOMENTS_DTYPE.names:
+                out[f] = out[f] + p[f]
+    return out if out.shape else out[()]
+
+
+def combine_budgets(budgets):
+    """One Budget from the ranks' budgets (HipBackend.budget of every rank), moments added in rank order.  volume, surface_area
+    and kinetic_energy follow from the combined moments by the formulas of gb25_budget; eta_potential_energy is the SUM of the
+    ranks' values in rank order (a budget does not carry g), which may differ from 1/2 g (combined second of eta) in the last bit."""
+    out = Budget()
+    for name in ("T", "S", "u", "v", "eta"):
+        acc = Moments()
+        for b in budgets:
+            r = getattr(b, name)
+            for f, _ in Moments._fields_:
+                setattr(acc, f, getattr(acc, f) + getattr(r, f))
+        setattr(out, name, acc)
+    out.volume, out.surface_area = out.T.measure, out.eta.measure
+    out.kinetic_energy = 0.5 * (out.u.second + out.v.second)
+    out.eta_potential_energy = sum(b.eta_potential_energy for b in budgets)
+    out.iteration, out.time = budgets[0].iteration, budgets[0].time
+    for q in range(3):
+        out.global_offset[q] = min(b.global_offset[q] for b in budgets)
+    return out

@@ -35,6 +35,29 @@ class Field:
         """min, max, max|x| and where, sums and non-finite count, reduced on the device (binding.FieldStats)."""
         return self._b.field_stats(self.name, include_halos)
 
+    def _moments(self, shape):
+        if hasattr(self._b, "integrate_field"):
+            return self._b.integrate_field(self.name, shape)
+        from .integrals import integrate_host       # (a backend without the device reduction)
+        return integrate_host(self._b, self.name, shape)
+
+    def integral(self):
+        """The field integrated over the wet interior with the cell measure of include/gb25.h (volume for a 3-D field, area
+        for a 2-D one), reduced on the device: one record -- measure, first = the integral, second, points, nonfinite."""
+        return self._moments("total")
+
+    def horizontal_mean(self):
+        """The measure-weighted mean of every level, [k] (NaN where a level has no wet point)."""
+        r = self._moments("levels")
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return r["first"] / r["measure"]
+
+    def zonal_mean(self):
+        """The measure-weighted mean of every row, [j, k] (NaN where a row has no wet point)."""
+        r = self._moments("rows")
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return r["first"] / r["measure"]
+
     def set(self, array, include_halos=False):
         a = np.asarray(array)
         if not include_halos and a.ndim >= 2:
@@ -168,6 +191,12 @@ class HydrostaticFreeSurfaceModel:
         Nx, Ny, Nz = self.grid.size
         return (f"HydrostaticFreeSurfaceModel({Nx}x{Ny}x{Nz} LatitudeLongitudeGrid, halo {self.grid.halo}, "
                 f"{np.dtype(getattr(self.backend, 'dtype', np.float32)).name}, MI355X)")
+
+
+def budget(model):
+    """Volume, heat, salt, kinetic energy and the free surface's volume and potential energy, integrated over the wet interior
+    on the device (binding.Budget; include/gb25.h gb25_get_budget): `print(budget(model))`."""
+    return model.backend.budget()
 
 
 def state_monitor(model):

@@ -198,8 +198,8 @@ typedef enum {
   GB25_K_IMPLICIT,     /* implicit_step!: the vertical solves of a closure (all of a step's launches together)        */
   GB25_K_CLOSURE,      /* CATKE: advection of e, surface flux, diffusivities                                          */
   GB25_K_FLUXES,       /* data-free forcing: similarity-theory fluxes; the bottom drag's flux kernel                   */
-  GB25_K_DIAGNOSTICS,  /* gb25_get_field_stats / gb25_compare_field / gb25_get_state_monitor: every launch they make,   */
-                       /* a pressure recomputed for the statistics of a stale GB25_PHY included                         */
+  GB25_K_DIAGNOSTICS,  /* gb25_get_field_stats / gb25_compare_field / gb25_get_state_monitor / gb25_integrate_field /   */
+                       /* gb25_get_budget: every launch they make, a pressure recomputed for a stale GB25_PHY included  */
   GB25_K_COUNT
 } gb25_kernel;
 
@@ -496,6 +496,61 @@ gb25_status gb25_get_state_monitor(gb25_model *m, gb25_state_monitor *out);
  * is pinned and no look-ahead is given up.  device_dims: the extents of the array as the device holds it (its pitches; a y-face
  * field of a folded grid has one row more there than gb25_field_dims reports).  Valid until the next call on m. */
 gb25_status gb25_field_device_ptr_readonly(gb25_model *m, gb25_field f, const void **dev, int32_t device_dims[3]);
+
+/* ---- integrals on the device: volume-weighted sums of a field over the rank's interior (csrc/diagnostics_kernels.hpp,
+ *      k_field_moments / k_moments_fold).  How much heat, salt, volume and kinetic energy the ocean holds.  Same contract as the
+ *      diagnostics above: the state gb25_get_field would return, READ-ONLY for the schedule, LOCAL on a rank (combine on the
+ *      host: gb-25_amd/integrals.py combine_moments / combine_budgets), bitwise repeatable, launches under GB25_K_DIAGNOSTICS.
+ *
+ *      THE MEASURE of interior point (i, j, k) of a field at location LOC:
+ *          mu = A_loc(i, j) * dz_loc(k) * fold(j) * wet_loc(i, j, k)
+ *      formed in fp64, in that order, from the numbers gb25_get_metric / gb25_get_metric2 return ((double)(real) of the host
+ *      tables, like the metrics of k_advective_cfl):
+ *        location  fields                                        A                                  dz       wet
+ *        (c,c,c)   T, S, e, pHY, G^n / G^- of T, S, e, L^e       AZCC  (lat-lon: GB25_M_AZC(j))     DZC(k)   k >= kbot(i,j)
+ *        (f,c,c)   u, G^n / G^- u, previous u                    AZFC  (lat-lon: GB25_M_AZC(j))     DZC(k)   k >= max(kbot(i-1,j), kbot(i,j))
+ *        (c,f,c)   v, G^n / G^- v, previous v                    AZCF  (lat-lon: GB25_M_AZF(j))     DZC(k)   k >= max(kbot(i,j-1), kbot(i,j)); 0 on a GLOBAL wall row
+ *        (c,c,f)   w, kappa_u, kappa_c, kappa_e                  as (c,c,c)                         DZF(k)   cell k or cell k-1 is wet
+ *        2-D (c,c) eta, eta_bar, J^b                             as (c,c,c)                         1        the column has a wet cell
+ *        2-D (f,c) U, U_bar, G^n U                               as (f,c,c)                         1        the face column has a wet level
+ *        2-D (c,f) V, V_bar, G^n V                               as (c,f,c)                         1        the face column has a wet level
+ *      "lat-lon" means the LatitudeLongitudeGrid with its row tables (grid types 0 and 1).  Every grid that carries 2-D metrics takes
+ *      the 2-D areas AZCC / AZFC / AZCF, GB25_GRID_LAT_LON_AS_CURVILINEAR included (its 2-D areas are the row values).
+ *      kbot = the number of immersed cells of a column (gb25_get_bottom_info, which = 0); the neighbour across x is the periodic
+ *      or the neighbour rank's column.  fold(j) = 1/2 on the GLOBAL pivot row (the last row of cell centres) of a folded grid
+ *      for the locations whose rows are rows of cell centres ((c,c,.) and (f,c,.)), 1 elsewhere: the pivot row is held twice,
+ *      each physical cell is counted once, and both copies get the 1/2 whether or not GB25_OPT_FOLD_PIVOT_SLAVED is set.  Rows
+ *      of y faces are held once.  On a rank of a decomposition the box is the rank's own interior; wall rows and the pivot row
+ *      are the global ones.
+ *
+ *      gb25_moments: measure = sum mu, first = sum mu x, second = sum mu x^2 over the points with mu > 0 and x finite; points =
+ *      how many those are; nonfinite = the points with mu > 0 whose x is not finite (skipped).  A value in an immersed cell is
+ *      invisible.
+ *      REDUCTION ORDER: one wave per row (j, k) of the interior box; a lane takes every 64th chunk of four elements and
+ *      accumulates in fp64 in the order of its elements; lanes combine by the fixed shuffle tree: that is ROWS[j + by k].
+ *      LEVELS[k] = ((ROWS[0, k] + ROWS[1, k]) + ...) left to right in j, TOTAL = ((LEVELS[0] + LEVELS[1]) + ...) left to right
+ *      in k, in fp64, member by member: a host that has ROWS can check LEVELS and TOTAL bit for bit.
+ *      count: by * bz records for ROWS (j fastest; by, bz = gb25_field_dims(f, 0)[1..2]), bz for LEVELS, 1 for TOTAL; any
+ *      other count is GB25_ERR_INVALID_ARGUMENT. */
+typedef enum { GB25_SUM_ROWS = 0, GB25_SUM_LEVELS = 1, GB25_SUM_TOTAL = 2 } gb25_sum_shape;
+typedef struct {
+  double measure, first, second;
+  int64_t points, nonfinite;
+} gb25_moments;
+gb25_status gb25_integrate_field(gb25_model *m, gb25_field f, gb25_sum_shape shape, gb25_moments *out, int64_t count);
+/* the totals of T, S, u, v, eta (each field read once) and what follows from them; global_offset as in gb25_field_stats */
+typedef struct {
+  gb25_moments T, S, u, v, eta;
+  double volume, surface_area;       /* measure of T [m^3], measure of eta [m^2] */
+  double kinetic_energy;             /* 1/2 (second of u + second of v)  [m^5 s^-2] */
+  double eta_potential_energy;       /* 1/2 g second of eta              [m^5 s^-2] */
+  int64_t iteration;
+  double time;
+  int32_t global_offset[3], reserved;
+} gb25_budget;
+gb25_status gb25_get_budget(gb25_model *m, gb25_budget *out);
+int32_t gb25_moments_bytes(void);       /* sizeof the two structs as THIS library was built */
+int32_t gb25_budget_bytes(void);
 
 /* ---- built-in per-kernel HIP-event timing (bench.py's roofline numbers) */
 gb25_status gb25_profile_enable(gb25_model *m, int on); /* 0: off, 1: every kernel, 2 + k: kernel k alone */

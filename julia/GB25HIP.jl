@@ -17,7 +17,8 @@ export Config, Model, create, destroy!, first_time_step!, time_step!, loop!, ini
        correct_velocities_and_cache_previous_tendencies!, set_baroclinic_instability!, synchronize,
        parent_array, interior_array, set_parent!, set_interior!, clock, set_dt!, set_option!, get_option,
        comm_unique_id, comm_init_rccl!, comm_finalize!, set_top_flux!, set_bottom_height!, set_vertical_diffusivity!, set_closure_catke!, CatkeParameters, default_catke_parameters, set_catke_parameters!, set_bottom_drag!, set_tracer_advection_order!, set_prescribed_atmosphere!, compute_atmosphere_ocean_fluxes!, metric2, FIELD, OPTION, METRIC2,
-       FieldStats, FieldDiff, StateMonitor, field_stats, compare_field, state_monitor, device_pointer_readonly
+       FieldStats, FieldDiff, StateMonitor, field_stats, compare_field, state_monitor, device_pointer_readonly,
+       Moments, Budget, integrate_field, budget, SUM_ROWS, SUM_LEVELS, SUM_TOTAL
 
 # One library per Oceananigans float type (src/arg_parsing.jl:12-16): Float32 -> libgb25hip.so, Float64 ->
 # libgb25hip_f64.so; same symbols, gb25_real_bytes() tells them apart.
@@ -371,6 +372,45 @@ function state_monitor(m::Model)
     check_diagnostic_structs(m)
     out = Ref{StateMonitor}()
     check(m, ccall((:gb25_get_state_monitor, m.lib), Cint, (Ptr{Cvoid}, Ref{StateMonitor}), m.ptr, out), "gb25_get_state_monitor")
+    return out[]
+end
+
+# ---- integrals on the device (gb25_integrate_field / gb25_get_budget): sums weighted by the cell measure of include/gb25.h
+const SUM_ROWS, SUM_LEVELS, SUM_TOTAL = Cint(0), Cint(1), Cint(2)
+struct Moments
+    measure::Float64; first::Float64; second::Float64
+    points::Int64; nonfinite::Int64
+end
+struct Budget
+    T::Moments; S::Moments; u::Moments; v::Moments; eta::Moments
+    volume::Float64; surface_area::Float64
+    kinetic_energy::Float64
+    eta_potential_energy::Float64
+    iteration::Int64
+    time::Float64
+    global_offset::NTuple{3, Int32}; reserved::Int32
+end
+function check_integral_structs(m::Model)
+    sizes = (ccall((:gb25_moments_bytes, m.lib), Int32, ()), ccall((:gb25_budget_bytes, m.lib), Int32, ()))
+    sizes == (sizeof(Moments), sizeof(Budget)) ||
+        error("gb25_moments / gb25_budget are $sizes bytes in the library and $((sizeof(Moments), sizeof(Budget))) in GB25HIP.jl: different versions")
+end
+"sum mu, sum mu x, sum mu x^2 of a field over its wet interior: SUM_ROWS a (by, bz) matrix of row records (zonal sums), SUM_LEVELS bz records, SUM_TOTAL one."
+function integrate_field(m::Model, field::Integer, shape::Integer = SUM_TOTAL)
+    check_integral_structs(m)
+    d = zeros(Int32, 3)
+    check(m, ccall((:gb25_field_dims, m.lib), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Int32}), m.ptr, field, 0, d), "gb25_field_dims")
+    n = shape == SUM_ROWS ? Int(d[2]) * Int(d[3]) : shape == SUM_LEVELS ? Int(d[3]) : 1
+    out = Vector{Moments}(undef, n)
+    check(m, ccall((:gb25_integrate_field, m.lib), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Moments}, Int64), m.ptr, field, shape, out, n),
+          "gb25_integrate_field")
+    return shape == SUM_ROWS ? reshape(out, Int(d[2]), Int(d[3])) : shape == SUM_LEVELS ? out : out[1]
+end
+"the totals of T, S, u, v, eta, the volume, the surface area, the kinetic and the free surface's potential energy; read-only for the schedule."
+function budget(m::Model)
+    check_integral_structs(m)
+    out = Ref{Budget}()
+    check(m, ccall((:gb25_get_budget, m.lib), Cint, (Ptr{Cvoid}, Ref{Budget}), m.ptr, out), "gb25_get_budget")
     return out[]
 end
 

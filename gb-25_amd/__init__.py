@@ -9,13 +9,16 @@ from .build import build_library
 from .correctness import approx_equal, combine_diffs, combine_stats, compare_states, sync_states
 from .integrals import cell_measure, combine_budgets, combine_moments, fold_records, integrate_host
 from .model import (CATKEVerticalDiffusivity, default_ocean_closure, Field, HydrostaticFreeSurfaceModel, VerticalScalarDiffusivity,
-                    baroclinic_instability_model, budget, first_time_step, initialize,
+                    baroclinic_instability_model, budget, density_anomaly, first_time_step, initialize, kinetic_energy,
+                    mixed_layer_depth, potential_density, vorticity,
                     loop, resolution_to_points, state_monitor, set_baroclinic_instability, set_top_flux, time_step, update_state,
                     tupled_fill_halo_regions_workload, compute_tendencies_workload,
                     compute_boundary_tendencies_workload, compute_interior_momentum_tendencies_workload,
                     compute_interior_tracer_tendencies_workload, compute_auxiliaries_workload,
                     fill_halo_regions_workload, ab2_step_workload,
                     correct_velocities_and_cache_previous_tendencies_workload)
+from .derived import (gather_derived, kinetic_energy_host, mixed_layer_depth_host, mixed_layer_depth_of_profiles,
+                      vorticity_host)
 from .data_free import (PrescribedAtmosphere, analytic_atmosphere, data_free_ocean_climate_model_init,
                         set_prescribed_atmosphere, set_data_free_state, zonal_wind, sunlight, Tatm)
 from .sharding import factors

@@ -57,7 +57,10 @@ ABI_SYMBOLS = [
     "gb25_field_stats_bytes", "gb25_field_diff_bytes", "gb25_state_monitor_bytes", "gb25_get_field_stats", "gb25_compare_field",
     "gb25_get_state_monitor", "gb25_field_device_ptr_readonly",
     "gb25_integrate_field", "gb25_get_budget", "gb25_moments_bytes", "gb25_budget_bytes",
+    "gb25_derived_dims", "gb25_compute_derived", "gb25_get_derived", "gb25_get_derived_stats", "gb25_get_field_levels",
 ]
+# gb25_derived (include/gb25.h)
+DERIVED_IDS = {"vorticity": 0, "kinetic_energy": 1, "density_anomaly": 2, "potential_density": 3, "mixed_layer_depth": 4}
 SUM_SHAPES = {"rows": 0, "levels": 1, "total": 2}   # gb25_sum_shape
 # gb25_option (include/gb25.h)
 OPTION_IDS = {"kernels": 0, "ab2_lookahead": 1, "subcycle_lookahead": 2, "subcycle_block": 3, "fill_fused": 4,
@@ -293,6 +296,11 @@ def load_library(float_type="Float32"):
     lib.gb25_field_device_ptr_readonly.argtypes = [P, C.c_int, C.POINTER(P), C.POINTER(C.c_int32)]
     lib.gb25_integrate_field.argtypes = [P, C.c_int, C.c_int, P, C.c_int64]
     lib.gb25_get_budget.argtypes = [P, C.POINTER(Budget)]
+    lib.gb25_derived_dims.argtypes = [P, C.c_int, C.POINTER(C.c_int32)]
+    lib.gb25_compute_derived.argtypes = [P, C.c_int, C.c_double, C.c_int32, C.c_int32, C.POINTER(P), C.POINTER(C.c_int32)]
+    lib.gb25_get_derived.argtypes = [P, C.c_int, C.c_double, C.c_int32, C.c_int32, P]
+    lib.gb25_get_derived_stats.argtypes = [P, C.c_int, C.c_double, C.POINTER(FieldStats)]
+    lib.gb25_get_field_levels.argtypes = [P, C.c_int, C.c_int32, C.c_int32, P]
     lib.gb25_profile_enable.argtypes = [P, C.c_int]
     lib.gb25_profile_get.argtypes = [P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     for name in ["gb25_use_own_stream", "gb25_synchronize", "gb25_set_baroclinic_instability", "gb25_initialize",
@@ -459,6 +467,50 @@ class HipBackend:
         out = Budget()
         self._call("gb25_get_budget", C.byref(out))
         return out
+
+    # ---- derived fields on the device (include/gb25.h: vorticity, kinetic_energy, density_anomaly, potential_density,
+    #      mixed_layer_depth); levels = (k_first, k_count), 0-based interior levels, k_count = -1 or levels = None: all
+    def derived_dims(self, name):
+        d = (C.c_int32 * 3)()
+        self._call("gb25_derived_dims", DERIVED_IDS[name], d)
+        return tuple(d)
+
+    @staticmethod
+    def _derived_args(name, param, levels):
+        if name == "mixed_layer_depth" and param is None:
+            param = 0.03
+        k_first, k_count = (0, -1) if levels is None else levels
+        return DERIVED_IDS[name], float(param or 0.0), int(k_first), int(k_count)
+
+    def compute_derived(self, name, param=None, levels=None):
+        """(device pointer, dims) of the packed result, elements of this backend's dtype, i fastest; read-only, valid until
+        the next call on this model."""
+        p, d = C.c_void_p(), (C.c_int32 * 3)()
+        self._call("gb25_compute_derived", *self._derived_args(name, param, levels), C.byref(p), d)
+        return p.value, tuple(d)
+
+    def get_derived(self, name, param=None, levels=None):
+        """numpy array [i, j, k] of the requested levels (a 2-D result: [i, j, 1]); only those are computed and copied."""
+        q, param, k_first, k_count = self._derived_args(name, param, levels)
+        d = self.derived_dims(name)
+        nk = d[2] - k_first if k_count == -1 else k_count
+        out = np.empty((max(nk, 0), d[1], d[0]), dtype=self.dtype)
+        self._call("gb25_get_derived", q, param, k_first, k_count, out.ctypes.data_as(C.c_void_p))
+        return out.transpose(2, 1, 0)
+
+    def derived_stats(self, name, param=None):
+        out = FieldStats()
+        q, param, _, _ = self._derived_args(name, param, None)
+        self._call("gb25_get_derived_stats", q, param, C.byref(out))
+        return out
+
+    def get_field_levels(self, name, k_first=0, k_count=-1):
+        """Interior levels [k_first, k_first + k_count) of a field, [i, j, k]: gathered on the device, one copy."""
+        d = self.field_dims(name, False)
+        nk = d[2] - k_first if k_count == -1 else k_count
+        out = np.empty((max(nk, 0), d[1], d[0]), dtype=self.dtype)
+        self._call("gb25_get_field_levels", FIELD_IDS[name], int(k_first), int(k_count), out.ctypes.data_as(C.c_void_p))
+        return out.transpose(2, 1, 0)
 
     def metric(self, name, index=1):
         v = C.c_double()

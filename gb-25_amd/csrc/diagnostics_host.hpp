@@ -1,5 +1,6 @@
 // diagnostics_host.hpp -- host side of gb25_get_field_stats / gb25_compare_field / gb25_get_state_monitor /
-// gb25_field_device_ptr_readonly / gb25_integrate_field / gb25_get_budget (include/gb25.h); the last part of gb25_api.hip, which includes it.  Kernels:
+// gb25_field_device_ptr_readonly / gb25_integrate_field / gb25_get_budget / gb25_compute_derived / gb25_get_derived /
+// gb25_get_derived_stats / gb25_get_field_levels (include/gb25.h); the last part of gb25_api.hip, which includes it.  Kernels:
 // diagnostics_kernels.hpp.  Nothing here writes model memory or a schedule flag: the calls may sit between any two steps.
 #pragma once
 
@@ -137,6 +138,26 @@ gb25_status moments_tables(gb25_model* m) {
     m->diag_area[q] = nullptr;
     m->diag_first_wet[q] = nullptr;
   }
+  if (m->diag_azff) HIPCHK(hipFree(m->diag_azff));
+  if (m->diag_zt) HIPCHK(hipFree(m->diag_zt));
+  m->diag_azff = nullptr;
+  m->diag_zt = nullptr;
+  {
+    // the derived fields' own: (double) of zc[0 .. Nz) | zf[0 .. Nz] as gb25_get_metric returns them, AZFF of a curvilinear grid
+    std::vector<double> zt((size_t)2 * Nz + 1);
+    for (int k = 0; k < Nz; k++) zt[k] = (double)(real)m->h_metric[GB25_M_ZC][m->metric_off_k + k];
+    for (int k = 0; k <= Nz; k++) zt[Nz + k] = (double)(real)m->h_metric[GB25_M_ZF][m->metric_off_k + k];
+    HIPCHK(hipMalloc(&m->diag_zt, zt.size() * sizeof(double)));
+    HIPCHK(hipMemcpy(m->diag_zt, zt.data(), zt.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (m->g.cv.on) {
+      const std::vector<double>& h = m->h_curv[GB25_M2_AZFF];
+      if (h.size() != n2) return fail(m, GB25_ERR_STATE, "derived fields: the curvilinear metrics are not built");
+      std::vector<real> a(n2);
+      for (size_t o = 0; o < n2; o++) a[o] = (real)h[o];
+      HIPCHK(hipMalloc(&m->diag_azff, n2 * sizeof(real)));
+      HIPCHK(hipMemcpy(m->diag_azff, a.data(), n2 * sizeof(real), hipMemcpyHostToDevice));
+    }
+  }
   if (m->g.cv.on) {
     static const int ids[3] = {GB25_M2_AZCC, GB25_M2_AZFC, GB25_M2_AZCF};
     std::vector<real> a(n2);
@@ -240,9 +261,194 @@ gb25_status moments_fold(gb25_model* m, const DiagBox* b, int n) {
   return GB25_OK;
 }
 
+
+// ---- derived fields
+// interior extents of a derived field, from the configuration alone (no device): zeta has the rows of v -- one more than the
+// cells below a wall, as many on a folded grid and below a northern neighbour rank
+void derived_extents(const gb25_model* m, gb25_derived q, int32_t d[3]) {
+  const bool no_wall = m->cfg.grid_type >= GB25_GRID_TRIPOLAR || m->yn_open;
+  d[0] = m->Nx;
+  d[1] = m->Ny + ((q == GB25_D_VORTICITY && !no_wall) ? 1 : 0);
+  d[2] = q == GB25_D_MIXED_LAYER_DEPTH ? 1 : m->cfg.Nz;
+}
+// interior levels [k_first, k_first + k_count) of nz; k_count = -1: all from k_first on
+gb25_status derived_levels(gb25_model* m, const char* what, int nz, int32_t k_first, int32_t k_count, int* kc) {
+  const long long n = k_count == -1 ? (long long)nz - k_first : (long long)k_count;
+  if (k_first < 0 || k_first >= nz || k_count < -1 || k_count == 0 || k_first + n > nz)
+    return fail(m, GB25_ERR_INVALID_ARGUMENT, "%s: levels k_first = %d, k_count = %d of a result with %d level%s (0-based interior levels; k_count = -1: all)",
+                what, (int)k_first, (int)k_count, nz, nz == 1 ? "" : "s");
+  *kc = (int)n;
+  return GB25_OK;
+}
+gb25_status derived_check(gb25_model* m, const char* what, gb25_derived q, double param) {
+  if (q < 0 || q >= GB25_D_COUNT) return fail(m, GB25_ERR_INVALID_ARGUMENT, "%s: no derived field %d (0 .. %d)", what, (int)q, GB25_D_COUNT - 1);
+  if (q == GB25_D_MIXED_LAYER_DEPTH && !(param > 0.0))
+    return fail(m, GB25_ERR_INVALID_ARGUMENT, "%s: the mixed-layer depth needs a density threshold > 0 kg/m^3 as param, got %g", what, param);
+  return GB25_OK;
+}
+gb25_status derived_need_device(gb25_model* m, const char* what) {
+  if (!m->own_stream) return fail(m, GB25_ERR_NO_DEVICE, "%s: this model has no device (gb25_create failed); libgb25hip has no CPU fallback", what);
+  return GB25_OK;
+}
+// once per model: one 2-D plane, then room for the largest interior a field has (w: Nz + 1 levels; v: Ny + 1 rows)
+gb25_status derived_scratch(gb25_model* m) {
+  if (m->diag_derived) return GB25_OK;
+  const size_t plane = (size_t)m->Nx * (m->Ny + 1);
+  m->diag_derived_plane = (plane + 3) & ~(size_t)3;   // (the 3-D part starts on a 16-byte boundary)
+  m->diag_derived_elems = m->diag_derived_plane + plane * ((size_t)m->cfg.Nz + 1);
+  HIPCHK(hipMalloc(&m->diag_derived, m->diag_derived_elems * sizeof(real)));
+  return GB25_OK;
+}
+inline dim3 derived_grid(int bx, int by, int kc) { return dim3((bx + 63) / 64, (by + 3) / 4, (kc + DER_LEVELS - 1) / DER_LEVELS); }
+
+// The launches of one derived field, levels [k0, k0 + kc), on m->stream behind the model; *result: where the packed result lies.
+gb25_status derived_run(gb25_model* m, gb25_derived q, double param, int k0, int kc, const real** result) {
+  const bool vel = q == GB25_D_VORTICITY || q == GB25_D_KINETIC_ENERGY;
+  const real *a = nullptr, *b = nullptr;
+  if (gb25_status s = diag_source(m, vel ? GB25_U : GB25_T, &a)) return s;
+  if (gb25_status s = diag_source(m, vel ? GB25_V : GB25_S, &b)) return s;
+  if (gb25_status s = derived_scratch(m)) return s;
+  if (gb25_status s = diag_wait_for_model(m)) return s;
+  if (gb25_status s = moments_tables(m)) return s;
+  int32_t e[3];
+  derived_extents(m, q, e);
+  const Grid& g = m->g;
+  const dim3 blk(64, 4);
+  Timed t(m, GB25_K_DIAGNOSTICS);
+  if (q == GB25_D_MIXED_LAYER_DEPTH) {
+    // sigma of every level into the 3-D part (the very values gb25_get_derived(GB25_D_POTENTIAL_DENSITY) hands out), then the march
+    real* sigma = m->diag_derived + m->diag_derived_plane;
+    const DerivedOut d{sigma, e[0], e[1], 0, g.Nz};
+    hipLaunchKernelGGL(k_derived_density<true>, derived_grid(e[0], e[1], g.Nz), blk, 0, m->stream, g, a, b, m->diag_eos0, m->diag_first_wet[0], d);
+    LAUNCHCHK();
+    hipLaunchKernelGGL(k_derived_mixed_layer, dim3((e[0] + 63) / 64, (e[1] + 3) / 4), blk, 0, m->stream, g, (const real*)sigma,
+                       m->diag_first_wet[0], (const double*)m->diag_zt, param, m->diag_derived, e[0], e[1]);
+    LAUNCHCHK();
+    *result = m->diag_derived;
+    return GB25_OK;
+  }
+  real* out = m->diag_derived + m->diag_derived_plane;
+  const DerivedOut d{out, e[0], e[1], k0, kc};
+  const dim3 grd = derived_grid(e[0], e[1], kc);
+  switch (q) {
+    case GB25_D_VORTICITY:
+      if (g.cv.on) hipLaunchKernelGGL(k_derived_vorticity<true>, grd, blk, 0, m->stream, g, a, b, (const real*)m->diag_azff, d);
+      else hipLaunchKernelGGL(k_derived_vorticity<false>, grd, blk, 0, m->stream, g, a, b, (const real*)nullptr, d);
+      break;
+    case GB25_D_KINETIC_ENERGY: hipLaunchKernelGGL(k_derived_kinetic_energy, grd, blk, 0, m->stream, g, a, b, d); break;
+    case GB25_D_DENSITY_ANOMALY:
+      hipLaunchKernelGGL(k_derived_density<false>, grd, blk, 0, m->stream, g, a, b, m->diag_eos0, m->diag_first_wet[0], d);
+      break;
+    default:
+      hipLaunchKernelGGL(k_derived_density<true>, grd, blk, 0, m->stream, g, a, b, m->diag_eos0, m->diag_first_wet[0], d);
+      break;
+  }
+  LAUNCHCHK();
+  *result = out;
+  return GB25_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+gb25_status gb25_derived_dims(const gb25_model* m, gb25_derived q, int32_t dims[3]) {
+  if (!m || !dims || q < 0 || q >= GB25_D_COUNT) return GB25_ERR_INVALID_ARGUMENT;
+  derived_extents(m, q, dims);
+  return GB25_OK;
+}
+
+gb25_status gb25_compute_derived(gb25_model* m, gb25_derived q, double param, int32_t k_first, int32_t k_count, const void** dev,
+                                 int32_t device_dims[3]) {
+  if (!m) return GB25_ERR_INVALID_ARGUMENT;
+  if (!dev) return fail(m, GB25_ERR_INVALID_ARGUMENT, "gb25_compute_derived: dev is NULL");
+  if (gb25_status s = derived_check(m, "gb25_compute_derived", q, param)) return s;
+  int32_t e[3];
+  int kc = 0;
+  derived_extents(m, q, e);
+  if (gb25_status s = derived_levels(m, "gb25_compute_derived", e[2], k_first, k_count, &kc)) return s;
+  if (gb25_status s = derived_need_device(m, "gb25_compute_derived")) return s;
+  const real* out = nullptr;
+  if (gb25_status s = derived_run(m, q, param, k_first, kc, &out)) return s;
+  HIPCHK(hipStreamSynchronize(m->stream));
+  *dev = out;
+  if (device_dims) {
+    device_dims[0] = e[0]; device_dims[1] = e[1]; device_dims[2] = kc;
+  }
+  return GB25_OK;
+}
+
+gb25_status gb25_get_derived(gb25_model* m, gb25_derived q, double param, int32_t k_first, int32_t k_count, void* host) {
+  if (!m) return GB25_ERR_INVALID_ARGUMENT;
+  if (!host) return fail(m, GB25_ERR_INVALID_ARGUMENT, "gb25_get_derived: host is NULL");
+  if (gb25_status s = derived_check(m, "gb25_get_derived", q, param)) return s;
+  int32_t e[3];
+  int kc = 0;
+  derived_extents(m, q, e);
+  if (gb25_status s = derived_levels(m, "gb25_get_derived", e[2], k_first, k_count, &kc)) return s;
+  if (gb25_status s = derived_need_device(m, "gb25_get_derived")) return s;
+  const real* out = nullptr;
+  if (gb25_status s = derived_run(m, q, param, k_first, kc, &out)) return s;
+  HIPCHK(hipMemcpyAsync(host, out, (size_t)e[0] * e[1] * kc * sizeof(real), hipMemcpyDeviceToHost, m->stream));
+  HIPCHK(hipStreamSynchronize(m->stream));
+  return GB25_OK;
+}
+
+gb25_status gb25_get_derived_stats(gb25_model* m, gb25_derived q, double param, gb25_field_stats* out) {
+  if (!m) return GB25_ERR_INVALID_ARGUMENT;
+  if (!out) return fail(m, GB25_ERR_INVALID_ARGUMENT, "gb25_get_derived_stats: out is NULL");
+  if (gb25_status s = derived_check(m, "gb25_get_derived_stats", q, param)) return s;
+  if (gb25_status s = derived_need_device(m, "gb25_get_derived_stats")) return s;
+  int32_t e[3];
+  derived_extents(m, q, e);
+  const DiagBox b{e[0], e[1], e[2], (long long)e[0], (long long)e[0] * e[1], 0};
+  if (gb25_status s = diag_scratch(m)) return s;
+  if (gb25_status s = diag_check_box(m, b)) return s;
+  const real* src = nullptr;
+  if (gb25_status s = derived_run(m, q, param, 0, e[2], &src)) return s;
+  {
+    Timed t(m, GB25_K_DIAGNOSTICS);
+    if (gb25_status s = diag_launch_stats(m, src, b, 0)) return s;
+  }
+  StatsPartial p;
+  HIPCHK(hipMemcpyAsync(&p, diag_result_slot(m, 0), sizeof p, hipMemcpyDeviceToHost, m->stream));
+  HIPCHK(hipStreamSynchronize(m->stream));
+  diag_fill_stats(m, GB25_T, p, b, 0, out);   // (interior: the offsets are those of any field of the rank, 0 in k)
+  return GB25_OK;
+}
+
+gb25_status gb25_get_field_levels(gb25_model* m, gb25_field f, int32_t k_first, int32_t k_count, void* host) {
+  if (!m) return GB25_ERR_INVALID_ARGUMENT;
+  if (f < 0 || f >= GB25_FIELD_COUNT) return fail(m, GB25_ERR_INVALID_ARGUMENT, "gb25_get_field_levels: no field %d", (int)f);
+  if (!host) return fail(m, GB25_ERR_INVALID_ARGUMENT, "gb25_get_field_levels: host is NULL");
+  if (k_first < 0 || k_count < -1 || k_count == 0)
+    return fail(m, GB25_ERR_INVALID_ARGUMENT, "gb25_get_field_levels: levels k_first = %d, k_count = %d (0-based interior levels; k_count = -1: all)",
+                (int)k_first, (int)k_count);
+  if (gb25_status s = derived_need_device(m, "gb25_get_field_levels")) return s;
+  const real* src = nullptr;
+  DiagBox b;
+  int kc = 0;
+  if (gb25_status s = diag_source(m, f, &src)) return s;
+  if (gb25_status s = diag_box(m, f, 0, &b)) return s;
+  if (gb25_status s = derived_levels(m, "gb25_get_field_levels", b.bz, k_first, k_count, &kc)) return s;
+  if (gb25_status s = derived_scratch(m)) return s;
+  const size_t n = (size_t)b.bx * b.by * kc;
+  if (n > m->diag_derived_elems - m->diag_derived_plane) return fail(m, GB25_ERR_STATE, "gb25_get_field_levels: the levels need more room than the model's result array has");
+  if (gb25_status s = diag_wait_for_model(m)) return s;
+  b.origin += b.plane * k_first;
+  b.bz = kc;
+  real* out = m->diag_derived + m->diag_derived_plane;
+  {
+    Timed t(m, GB25_K_DIAGNOSTICS);
+    constexpr int VW = 16 / sizeof(real);
+    const int chunks = (b.bx + VW - 1) / VW + 1;
+    hipLaunchKernelGGL(k_gather_levels<real>, dim3((chunks + 63) / 64, (b.by + 3) / 4, kc), dim3(64, 4), 0, m->stream, src, b, out);
+    LAUNCHCHK();
+  }
+  HIPCHK(hipMemcpyAsync(host, out, n * sizeof(real), hipMemcpyDeviceToHost, m->stream));
+  HIPCHK(hipStreamSynchronize(m->stream));
+  return GB25_OK;
+}
 
 int32_t gb25_field_stats_bytes(void) { return (int32_t)sizeof(gb25_field_stats); }
 int32_t gb25_field_diff_bytes(void) { return (int32_t)sizeof(gb25_field_diff); }

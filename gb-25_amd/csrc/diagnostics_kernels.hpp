@@ -396,4 +396,174 @@ __global__ __launch_bounds__(DIAG_THREADS) void k_diag_finish(const P* __restric
   if (threadIdx.x == 0) *out = p;
 }
 
+// ---- derived fields (gb25_compute_derived, gb25_get_derived, gb25_get_derived_stats, gb25_get_field_levels): relative vorticity,
+// kinetic energy per cell, in-situ and potential density, mixed-layer depth, and a gather of levels of an ordinary field.
+// Definitions: include/gb25.h.  Common shape: a block is 64 x 4 threads, ONE WAVE = 64 consecutive i of one row j (u, v, T, S and
+// the 2-D metrics load coalesced), and marches DER_LEVELS levels, so that the 2-D metrics, the first wet level and the row tables
+// are loaded once per block; the row and level tables (dxc, azf, the 28 coefficients of a level) are wave-uniform and go through
+// scalar loads.  The result is PACKED: out[i + bx (j + by kk)], kk = 0 .. k_count - 1 for level k_first + kk, so that only the
+// requested levels are computed, stored and copied.  Plain vector stores, no atomics, every offset into a 3-D array 64-bit.
+// Vorticity, kinetic energy and the mixed-layer depth are fp64 on (double) of the stored values with floating-point contraction
+// OFF (every product and sum rounds by itself, divisions are IEEE), rounded once to the float type: numpy restates them bit for
+// bit (gb-25_amd/derived.py).  The densities are teos10_level on s, t formed as k_compute_p forms them, compiled like it.
+constexpr int DER_LEVELS = 4;
+struct DerivedOut {
+  real* out;
+  int bx, by, k_first, k_count;
+};
+__device__ __forceinline__ long long der_off(const Grid& g, int plane, int i, int j, int k) {
+  return (long long)(i + g.H) + (long long)g.sx * (j + g.H) + (long long)plane * (k + g.H);
+}
+__device__ __forceinline__ long long der_out(const DerivedOut& d, int i, int j, int kk) {
+  return (long long)i + (long long)d.bx * ((long long)j + (long long)d.by * kk);
+}
+
+// zeta(i,j,k) = ((dy v(i,j) - dy' v(i-1,j)) - (dx u(i,j) - dx' u(i,j-1))) / Az at (f,f,c); box = the interior of v.
+// CURV: dy = DYCF(i,j), dy' = DYCF(i-1,j), dx = DXFC(i,j), dx' = DXFC(i,j-1), Az = AZFF(i,j) (azff: diagnostics' own table);
+// else dy = dy' = GB25_M_DY, dx = DXC(j), dx' = DXC(j-1), Az = AZF(j).  Az == 0 gives 0.
+template <bool CURV>
+__global__ __launch_bounds__(256) void k_derived_vorticity(Grid g, const real* __restrict__ u, const real* __restrict__ v,
+                                                            const real* __restrict__ azff, DerivedOut d) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  const int j = blockIdx.y * 4 + __builtin_amdgcn_readfirstlane(threadIdx.y);
+  if (j >= d.by) return;   // (the whole wave)
+  const bool in = i < d.bx;
+  const int ii = in ? i : d.bx - 1;   // (addresses stay in the box)
+  double dyc, dyw, dxc, dxs, az;
+  if (CURV) {
+    const int o = i2(g, ii, j);
+    dyc = (double)g.cv.dycf[o];
+    dyw = (double)g.cv.dycf[o - 1];
+    dxc = (double)g.cv.dxfc[o];
+    dxs = (double)g.cv.dxfc[o - g.sx];
+    az = (double)azff[o];
+  } else {
+    dyc = dyw = (double)g.dy;
+    dxc = (double)uniform_at(g.dxc, j);
+    dxs = (double)uniform_at(g.dxc, j - 1);
+    az = (double)uniform_at(g.azf, j);
+  }
+  const int kk0 = blockIdx.z * DER_LEVELS;
+  for (int q = 0; q < DER_LEVELS && kk0 + q < d.k_count; q++) {
+    const int k = d.k_first + kk0 + q;
+    const long long ou = der_off(g, g.pl_c, ii, j, k), ov = der_off(g, g.pl_v, ii, j, k);
+    const double vc = (double)v[ov], vw = (double)v[ov - 1], uc = (double)u[ou], us = (double)u[ou - g.sx];
+    const double a = dyc * vc, b = dyw * vw, c = dxc * uc, e = dxs * us;
+    const double z = ((a - b) - (c - e)) / az;
+    if (in) d.out[der_out(d, i, j, kk0 + q)] = (real)(az == 0.0 ? 0.0 : z);
+  }
+}
+
+// KE(i,j,k) = 0.25 ((u(i)^2 + u(i+1)^2) + (v(j)^2 + v(j+1)^2)) at (c,c,c): Oceananigans' (Ix u^2 + Iy v^2) / 2
+__global__ __launch_bounds__(256) void k_derived_kinetic_energy(Grid g, const real* __restrict__ u, const real* __restrict__ v,
+                                                                 DerivedOut d) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  const int j = blockIdx.y * 4 + __builtin_amdgcn_readfirstlane(threadIdx.y);
+  if (j >= d.by) return;
+  const bool in = i < d.bx;
+  const int ii = in ? i : d.bx - 1;
+  const int kk0 = blockIdx.z * DER_LEVELS;
+  for (int q = 0; q < DER_LEVELS && kk0 + q < d.k_count; q++) {
+    const int k = d.k_first + kk0 + q;
+    const long long ou = der_off(g, g.pl_c, ii, j, k), ov = der_off(g, g.pl_v, ii, j, k);
+    const double u0 = (double)u[ou], u1 = (double)u[ou + 1], v0 = (double)v[ov], v1 = (double)v[ov + g.sx];
+    const double a = u0 * u0, b = u1 * u1, c = v0 * v0, e = v1 * v1;
+    const double ke = 0.25 * ((a + b) + (c + e));
+    if (in) d.out[der_out(d, i, j, kk0 + q)] = (real)ke;
+  }
+}
+
+// rho(T, S, z_k) - rho0 (POT: rho(T, S, 0) - rho0, one table `eos0` folded at Z = 0) at (c,c,c); 0 in the immersed cells
+// (first_wet: diagnostics' table of the (c,c) columns, null on a grid without a bottom table)
+template <bool POT>
+__global__ __launch_bounds__(256) void k_derived_density(Grid g, const real* __restrict__ T, const real* __restrict__ S,
+                                                          const double* __restrict__ eos0, const unsigned short* __restrict__ first_wet,
+                                                          DerivedOut d) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  const int j = blockIdx.y * 4 + __builtin_amdgcn_readfirstlane(threadIdx.y);
+  if (j >= d.by) return;
+  const bool in = i < d.bx;
+  const int ii = in ? i : d.bx - 1;
+  const double sc = 0.875 / 35.16504;
+  const int kb = first_wet ? (int)first_wet[i2(g, ii, j)] : 0;
+  const int kk0 = blockIdx.z * DER_LEVELS;
+  for (int q = 0; q < DER_LEVELS && kk0 + q < d.k_count; q++) {
+    const int k = d.k_first + kk0 + q;
+    const double* c = POT ? eos0 : g.eos + 28 * k;
+    const long long o = der_off(g, g.pl_c, ii, j, k);
+    const double rho = teos10_level(c, sqrt_pos(((double)S[o] + 32.0) * sc), (double)T[o] * 0.025);
+    if (in) d.out[der_out(d, i, j, kk0 + q)] = k < kb ? real(0) : (real)rho;
+  }
+}
+
+// Mixed-layer depth, one thread per column, coalesced in i.  sigma: the potential density of every level as k_derived_density<true>
+// stored it (packed bx x by x Nz, values of the float type: the same bits gb25_get_derived hands out).  zt: (double) of the
+// model's zc[0 .. Nz) followed by zf[0 .. Nz].  d(k) = sigma(k) - sigma(Nz - 1); marching down from Nz - 2, at the first wet k with
+// d(k) >= param: -(zc(k+1) + (zc(k) - zc(k+1)) ((param - d(k+1)) / (d(k) - d(k+1)))); never: -zf(first wet level); dry column: 0.
+__global__ __launch_bounds__(256) void k_derived_mixed_layer(Grid g, const real* __restrict__ sigma, const unsigned short* __restrict__ first_wet,
+                                                              const double* __restrict__ zt, double param, real* __restrict__ out, int bx, int by) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  const int j = blockIdx.y * 4 + threadIdx.y;
+  if (i >= bx || j >= by) return;
+  const int Nz = g.Nz;
+  const int kb = first_wet ? (int)first_wet[i2(g, i, j)] : 0;
+  const long long col = (long long)i + (long long)bx * j, plane = (long long)bx * by;
+  double depth = 0.0;
+  if (kb < Nz) {
+    const double* zc = zt;
+    const double* zf = zt + Nz;
+    const double s0 = (double)sigma[col + plane * (Nz - 1)];
+    double dprev = 0.0;
+    depth = -zf[kb];
+    for (int k = Nz - 2; k >= kb; k--) {
+      const double dk = (double)sigma[col + plane * k] - s0;
+      if (dk >= param) {
+        const double frac = (param - dprev) / (dk - dprev);
+        const double step = (zc[k] - zc[k + 1]) * frac;
+        depth = -(zc[k + 1] + step);
+        break;
+      }
+      dprev = dk;
+    }
+  }
+  out[col] = (real)depth;
+}
+
+// Levels of the interior of an ordinary field into the packed scratch array.  box: the interior box whose first level is the
+// first requested one, bz = the number of levels.  One wave per row; the row is cut into 16-byte chunks aligned in the DESTINATION:
+// a whole chunk is one vector store, fed by one vector load where the source happens to be aligned as well and by element loads
+// where it is not; the cut chunks at the two ends of a row go element by element.
+template <class T>
+__global__ __launch_bounds__(256) void k_gather_levels(const T* __restrict__ src, DiagBox box, T* __restrict__ dst) {
+  constexpr int VW = 16 / sizeof(T);
+  using V = T __attribute__((ext_vector_type(VW)));
+  const int j = blockIdx.y * 4 + __builtin_amdgcn_readfirstlane(threadIdx.y);
+  if (j >= box.by) return;
+  const int kk = blockIdx.z;
+  const T* s = src + (box.origin + box.pitch * j + box.plane * kk);
+  T* t = dst + (long long)box.bx * ((long long)j + (long long)box.by * kk);
+  const int mis = (int)(((unsigned long long)t / sizeof(T)) & (VW - 1));
+  const int nchunks = (mis + box.bx + VW - 1) / VW;
+  const int c = blockIdx.x * 64 + threadIdx.x;
+  if (c >= nchunks) return;
+  const int x0 = VW * c - mis;
+  if (x0 >= 0 && x0 + VW <= box.bx) {
+    V v;
+    if (((unsigned long long)(s + x0) & 15) == 0) {
+      v = *reinterpret_cast<const V*>(s + x0);
+    } else {
+#pragma unroll
+      for (int q = 0; q < VW; q++) v[q] = s[x0 + q];
+    }
+    *reinterpret_cast<V*>(t + x0) = v;
+  } else {
+#pragma unroll
+    for (int q = 0; q < VW; q++)
+      if (x0 + q >= 0 && x0 + q < box.bx) t[x0 + q] = s[x0 + q];
+  }
+}
+
 }  // namespace gb25

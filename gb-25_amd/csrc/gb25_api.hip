@@ -241,6 +241,15 @@ struct gb25_model {
   real* diag_area[3] = {nullptr, nullptr, nullptr};
   unsigned short* diag_first_wet[3] = {nullptr, nullptr, nullptr};
   bool diag_tables_valid = false;
+  // derived fields (gb25_compute_derived, gb25_get_field_levels): the packed result array -- one 2-D plane (the mixed-layer depth)
+  // followed by room for the largest interior a field of this model has --, made by the first call that needs it; diagnostics' own
+  // AZFF (curvilinear grids) and (double) zc | zf, rebuilt with the other tables; the TEOS-10 table folded at Z = 0, part of the
+  // allocation of build_eos_tables and rebuilt with it.  No stepping kernel reads or writes them.
+  real* diag_derived = nullptr;
+  size_t diag_derived_plane = 0, diag_derived_elems = 0;
+  real* diag_azff = nullptr;
+  double* diag_zt = nullptr;
+  const double* diag_eos0 = nullptr;
 };
 
 namespace {
@@ -722,8 +731,8 @@ const double kEosR0[6] = {4.6494977072e+01, -5.2099962525e+00, 2.2601900708e-01,
 gb25_status build_eos_tables(gb25_model* m) {
   const int Nz = m->cfg.Nz, offk = m->metric_off_k;
   const std::vector<double>&zc = m->h_metric[GB25_M_ZC], &dzf = m->h_metric[GB25_M_DZF], &zf = m->h_metric[GB25_M_ZF];
-  // [28 (Nz+1): levels][28 (Nz+1): faces][Nz+1: dzf]
-  std::vector<double> tab((size_t)56 * (Nz + 1), 0.0), dz(Nz + 1);
+  // [28 (Nz+1): levels][28 (Nz+1): faces][Nz+1: dzf][28: the surface, Z = 0 -- the potential density of the derived fields]
+  std::vector<double> tab((size_t)56 * (Nz + 1), 0.0), dz(Nz + 1), surf(28, 0.0);
   auto fold = [&](double Z, double* c) {
     const double zeta = -Z * 1e-4;
     for (const EosTerm& t : kEos) {
@@ -741,8 +750,11 @@ gb25_status build_eos_tables(gb25_model* m) {
     fold((double)(real)zf[offk + k], &tab[(size_t)28 * (Nz + 1 + k)]);   // (Z^ccf: the face itself, a number of the model's float type)
     dz[k] = dzf[offk + k];
   }
+  fold(0.0, surf.data());
   double* d = nullptr;
-  HIPCHK(hipMalloc(&d, (tab.size() + dz.size()) * sizeof(double)));
+  HIPCHK(hipMalloc(&d, (tab.size() + dz.size() + surf.size()) * sizeof(double)));
+  HIPCHK(hipMemcpy(d + tab.size() + dz.size(), surf.data(), surf.size() * sizeof(double), hipMemcpyHostToDevice));
+  m->diag_eos0 = d + tab.size() + dz.size();
   HIPCHK(hipMemcpy(d, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(d + tab.size(), dz.data(), dz.size() * sizeof(double), hipMemcpyHostToDevice));
   m->dev_tables.push_back(reinterpret_cast<real*>(d));
@@ -2702,6 +2714,9 @@ void gb25_destroy(gb25_model* m) {
   if (m->uv_partials) hipFree(m->uv_partials);
   if (m->diag_scratch) hipFree(m->diag_scratch);
   if (m->diag_moments) hipFree(m->diag_moments);
+  if (m->diag_derived) hipFree(m->diag_derived);
+  if (m->diag_azff) hipFree(m->diag_azff);
+  if (m->diag_zt) hipFree(m->diag_zt);
   for (int q = 0; q < 3; q++) {
     if (m->diag_area[q]) hipFree(m->diag_area[q]);
     if (m->diag_first_wet[q]) hipFree(m->diag_first_wet[q]);

@@ -58,6 +58,18 @@ class Field:
         with np.errstate(invalid="ignore", divide="ignore"):
             return r["first"] / r["measure"]
 
+    def levels(self, k_first, k_count=1):
+        """Interior levels [k_first, k_first + k_count) (0-based; k_count = -1: all from k_first on) as [i, j, k]: gathered on the
+        device and copied once -- the parent array does not cross PCIe, nothing is pinned."""
+        if hasattr(self._b, "get_field_levels"):
+            return self._b.get_field_levels(self.name, k_first, k_count)
+        a = self._b.get_field(self.name, False)       # (a backend without the device gather)
+        return a[:, :, k_first:(None if k_count == -1 else k_first + k_count)]
+
+    def surface(self):
+        """The top interior level, [i, j, 1]: `indices = (:, :, Nz)` of the reference's surface writer."""
+        return self.levels(self._b.field_dims(self.name, False)[2] - 1, 1)
+
     def set(self, array, include_halos=False):
         a = np.asarray(array)
         if not include_halos and a.ndim >= 2:
@@ -197,6 +209,46 @@ def budget(model):
     """Volume, heat, salt, kinetic energy and the free surface's volume and potential energy, integrated over the wet interior
     on the device (binding.Budget; include/gb25.h gb25_get_budget): `print(budget(model))`."""
     return model.backend.budget()
+
+
+def _derived(model, name, param=None, levels=None):
+    b = model.backend
+    if hasattr(b, "get_derived"):
+        return b.get_derived(name, param, levels)
+    from . import derived as host                     # (a backend without the device kernels: the numpy restatement)
+    if name == "vorticity":
+        return host.vorticity_host(b, levels)
+    if name == "kinetic_energy":
+        return host.kinetic_energy_host(b, levels)
+    raise NotImplementedError(f"{name} needs a backend with get_derived")
+
+
+def vorticity(model, levels=None):
+    """Vertical relative vorticity at (f,f,c) computed on the device (include/gb25.h, GB25_D_VORTICITY), [i, j, k] shaped like
+    v's interior.  levels = (k_first, k_count), 0-based interior levels (k_count = -1: all from k_first on); only those levels
+    are computed and copied: `vorticity(model, levels=(Nz - 1, 1))` is the surface."""
+    return _derived(model, "vorticity", None, levels)
+
+
+def kinetic_energy(model, levels=None):
+    """Kinetic energy per unit mass at (c,c,c), (Ix u^2 + Iy v^2) / 2, on the device."""
+    return _derived(model, "kinetic_energy", None, levels)
+
+
+def density_anomaly(model, levels=None):
+    """In-situ density rho(T, S, z) - rho0 (TEOS-10) at (c,c,c): what the hydrostatic pressure integrates; 0 in immersed cells."""
+    return _derived(model, "density_anomaly", None, levels)
+
+
+def potential_density(model, levels=None):
+    """Potential density rho(T, S, 0) - rho0 referenced to the surface, at (c,c,c); 0 in immersed cells."""
+    return _derived(model, "potential_density", None, levels)
+
+
+def mixed_layer_depth(model, threshold=0.03):
+    """Depth [m, positive] at which the potential density exceeds the top cell's by `threshold` kg/m^3, linearly interpolated
+    between cell centres; the column's depth where it never does, 0 over land.  [i, j]."""
+    return _derived(model, "mixed_layer_depth", threshold)[:, :, 0]
 
 
 def state_monitor(model):

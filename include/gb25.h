@@ -199,7 +199,8 @@ typedef enum {
   GB25_K_CLOSURE,      /* CATKE: advection of e, surface flux, diffusivities                                          */
   GB25_K_FLUXES,       /* data-free forcing: similarity-theory fluxes; the bottom drag's flux kernel                   */
   GB25_K_DIAGNOSTICS,  /* gb25_get_field_stats / gb25_compare_field / gb25_get_state_monitor / gb25_integrate_field /   */
-                       /* gb25_get_budget: every launch they make, a pressure recomputed for a stale GB25_PHY included  */
+                       /* gb25_get_budget / the derived fields: every launch they make, a pressure recomputed for a     */
+                       /* stale GB25_PHY included                                                                       */
   GB25_K_COUNT
 } gb25_kernel;
 
@@ -551,6 +552,58 @@ typedef struct {
 gb25_status gb25_get_budget(gb25_model *m, gb25_budget *out);
 int32_t gb25_moments_bytes(void);       /* sizeof the two structs as THIS library was built */
 int32_t gb25_budget_bytes(void);
+
+/* ---- derived fields on the device: what the flow looks like, without a parent array crossing PCIe (csrc/diagnostics_kernels.hpp,
+ *      k_derived_*, k_gather_levels).  Relative vorticity, kinetic energy per cell, in-situ and potential density, mixed-layer
+ *      depth, and a few levels of any ordinary field (the surface slices `indices = (:, :, Nz)` the reference's
+ *      simulations/ocean_climate_simulation.jl writes every three days).  Same contract as the diagnostics above: the state
+ *      gb25_get_field would return, READ-ONLY for the schedule (nothing pinned, every look-ahead alive), LOCAL on a rank (a
+ *      rank's interior; gather by global_offset: gb-25_amd/derived.py gather_derived), bitwise repeatable, launches under
+ *      GB25_K_DIAGNOSTICS.
+ *
+ *      DEFINITIONS.  Values are read from the parent arrays as gb25_get_field(f, host, 1) returns them at that moment, halo cells
+ *      included; metrics are the numbers gb25_get_metric / gb25_get_metric2 return.  Vorticity, kinetic energy and mixed-layer
+ *      depth: every operation in fp64 on (double) of the stored values, in the written order, IEEE divisions, NO fused
+ *      multiply-adds, the result rounded once to the float type -- gb-25_amd/derived.py restates them with numpy bit for bit.
+ *      Indices below are 1-based interior; i-1, j-1, i+1, j+1 reach one halo column or row.
+ *        GB25_D_VORTICITY  zeta(i,j,k) = ((dy v(i,j,k) - dy' v(i-1,j,k)) - (dx u(i,j,k) - dx' u(i,j-1,k))) / Az
+ *            curvilinear grids (grid_type >= 2): dy = DYCF(i,j), dy' = DYCF(i-1,j), dx = DXFC(i,j), dx' = DXFC(i,j-1), Az = AZFF(i,j)
+ *            LatitudeLongitudeGrid:               dy = dy' = GB25_M_DY, dx = DXC(j), dx' = DXC(j-1), Az = AZF(j)
+ *            Az == 0 gives 0.  No masking of its own: masked velocities make zeta vanish inside land.
+ *        GB25_D_KINETIC_ENERGY  KE(i,j,k) = 0.25 * ((u(i)^2 + u(i+1)^2) + (v(j)^2 + v(j+1)^2)): Oceananigans' (Ix u^2 + Iy v^2) / 2
+ *        GB25_D_DENSITY_ANOMALY  the TEOS-10 polynomial folded at the level's depth, on s = sqrt((S + 32) 0.875 / 35.16504),
+ *            t = T / 40 formed and evaluated in fp64 exactly as the hydrostatic pressure kernel does (FMAs as the compiler
+ *            contracts them there), rounded once; 0 in the immersed cells, k < kbot
+ *        GB25_D_POTENTIAL_DENSITY  the same with the one table folded at Z = 0
+ *        GB25_D_MIXED_LAYER_DEPTH  sigma = the potential density as stored (rounded to the float type, then (double)); ks = the top
+ *            level; d(k) = sigma(k) - sigma(ks).  Marching down from ks - 1, at the first wet k with d(k) >= param the depth is
+ *              -(zc(k+1) + (zc(k) - zc(k+1)) * ((param - d(k+1)) / (d(k) - d(k+1))))
+ *            with zc = GB25_M_ZC; if d never reaches param, -GB25_M_ZF of the first wet level (the column's bottom face); a dry
+ *            column gives 0.  param: the density threshold in kg/m^3, > 0.
+ *
+ *      LEVELS: k_first, k_count select interior levels, 0-based; k_count = -1: all from k_first on.  A 2-D result takes 0, 1 or
+ *      0, -1.  Only the requested levels are computed and copied.  param is ignored except by the mixed-layer depth.
+ *      gb25_compute_derived: into an array the model owns (made by the first call, sized for the largest interior, freed by
+ *      gb25_destroy); *dev: elements of the library's float type, PACKED, device_dims = interior extents by k_count, i fastest;
+ *      read-only, complete when the call returns, valid until the next call on m (what gb25_compare_field of another model or a
+ *      host framework's wrapper consumes).  gb25_get_derived: the same and one device-to-host copy of exactly those elements.
+ *      gb25_get_derived_stats: gb25_field_stats of the whole derived field, positions relative to its interior.
+ *      gb25_get_field_levels: interior levels of an ordinary field, gathered on the device and copied once -- a stale GB25_PHY is
+ *      recomputed, previous_velocities are read where they live, the parent is not downloaded, nothing is pinned. */
+typedef enum {
+  GB25_D_VORTICITY = 0,      /* zeta_3 at (f,f,c); dims = dims of GB25_V */
+  GB25_D_KINETIC_ENERGY,     /* (c,c,c) */
+  GB25_D_DENSITY_ANOMALY,    /* (c,c,c) rho(T,S,z_k) - rho0, in situ: what the pressure kernel integrates */
+  GB25_D_POTENTIAL_DENSITY,  /* (c,c,c) rho(T,S,0) - rho0, referenced to the surface */
+  GB25_D_MIXED_LAYER_DEPTH,  /* 2-D (c,c), metres, positive; param = the density threshold in kg/m^3 */
+  GB25_D_COUNT
+} gb25_derived;
+gb25_status gb25_derived_dims(const gb25_model *m, gb25_derived d, int32_t dims[3]);            /* interior; needs no device */
+gb25_status gb25_compute_derived(gb25_model *m, gb25_derived d, double param, int32_t k_first, int32_t k_count,
+                                 const void **dev, int32_t device_dims[3]);
+gb25_status gb25_get_derived(gb25_model *m, gb25_derived d, double param, int32_t k_first, int32_t k_count, void *host);
+gb25_status gb25_get_derived_stats(gb25_model *m, gb25_derived d, double param, gb25_field_stats *out);
+gb25_status gb25_get_field_levels(gb25_model *m, gb25_field f, int32_t k_first, int32_t k_count, void *host);
 
 /* ---- built-in per-kernel HIP-event timing (bench.py's roofline numbers) */
 gb25_status gb25_profile_enable(gb25_model *m, int on); /* 0: off, 1: every kernel, 2 + k: kernel k alone */

@@ -18,7 +18,8 @@ export Config, Model, create, destroy!, first_time_step!, time_step!, loop!, ini
        parent_array, interior_array, set_parent!, set_interior!, clock, set_dt!, set_option!, get_option,
        comm_unique_id, comm_init_rccl!, comm_finalize!, set_top_flux!, set_bottom_height!, set_vertical_diffusivity!, set_closure_catke!, CatkeParameters, default_catke_parameters, set_catke_parameters!, set_bottom_drag!, set_tracer_advection_order!, set_prescribed_atmosphere!, compute_atmosphere_ocean_fluxes!, metric2, FIELD, OPTION, METRIC2,
        FieldStats, FieldDiff, StateMonitor, field_stats, compare_field, state_monitor, device_pointer_readonly,
-       Moments, Budget, integrate_field, budget, SUM_ROWS, SUM_LEVELS, SUM_TOTAL
+       Moments, Budget, integrate_field, budget, SUM_ROWS, SUM_LEVELS, SUM_TOTAL,
+       DERIVED, derived_dims, compute_derived, get_derived, derived_stats, field_levels
 
 # One library per Oceananigans float type (src/arg_parsing.jl:12-16): Float32 -> libgb25hip.so, Float64 ->
 # libgb25hip_f64.so; same symbols, gb25_real_bytes() tells them apart.
@@ -412,6 +413,48 @@ function budget(m::Model)
     out = Ref{Budget}()
     check(m, ccall((:gb25_get_budget, m.lib), Cint, (Ptr{Cvoid}, Ref{Budget}), m.ptr, out), "gb25_get_budget")
     return out[]
+end
+
+# ---- derived fields on the device (gb25_compute_derived / gb25_get_derived / gb25_get_derived_stats / gb25_get_field_levels):
+#      definitions in include/gb25.h.  k_first is 0-based like the ABI; k_count = -1: all levels from k_first on.
+const DERIVED = (vorticity = Cint(0), kinetic_energy = Cint(1), density_anomaly = Cint(2), potential_density = Cint(3),
+                 mixed_layer_depth = Cint(4))
+"interior extents of a derived field (zeta: those of v)"
+function derived_dims(m::Model, d::Integer)
+    out = zeros(Int32, 3)
+    check(m, ccall((:gb25_derived_dims, m.lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Int32}), m.ptr, d, out), "gb25_derived_dims")
+    return Tuple(Int.(out))
+end
+"device pointer and dims of the packed result (read-only, valid until the next call on m): what unsafe_wrap(ROCArray, ...) consumes"
+function compute_derived(m::Model{FT}, d::Integer; param::Real = 0.0, k_first::Integer = 0, k_count::Integer = -1) where {FT}
+    p, dims = Ref{Ptr{Cvoid}}(C_NULL), zeros(Int32, 3)
+    check(m, ccall((:gb25_compute_derived, m.lib), Cint, (Ptr{Cvoid}, Cint, Float64, Int32, Int32, Ref{Ptr{Cvoid}}, Ptr{Int32}),
+                   m.ptr, d, param, k_first, k_count, p, dims), "gb25_compute_derived")
+    return Ptr{FT}(p[]), Tuple(Int.(dims))
+end
+"a derived field's requested levels as an Array{FT, 3}; only those levels are computed and copied"
+function get_derived(m::Model{FT}, d::Integer; param::Real = 0.0, k_first::Integer = 0, k_count::Integer = -1) where {FT}
+    nx, ny, nz = derived_dims(m, d)
+    out = Array{FT}(undef, nx, ny, k_count == -1 ? nz - k_first : k_count)
+    check(m, ccall((:gb25_get_derived, m.lib), Cint, (Ptr{Cvoid}, Cint, Float64, Int32, Int32, Ptr{Cvoid}),
+                   m.ptr, d, param, k_first, k_count, out), "gb25_get_derived")
+    return out
+end
+function derived_stats(m::Model, d::Integer; param::Real = 0.0)
+    check_diagnostic_structs(m)
+    out = Ref{FieldStats}()
+    check(m, ccall((:gb25_get_derived_stats, m.lib), Cint, (Ptr{Cvoid}, Cint, Float64, Ref{FieldStats}), m.ptr, d, param, out),
+          "gb25_get_derived_stats")
+    return out[]
+end
+"interior levels of an ordinary field, gathered on the device: field_levels(m, FIELD.T, Nz - 1, 1) is interior(T)[:, :, Nz:Nz]"
+function field_levels(m::Model{FT}, field::Integer, k_first::Integer = 0, k_count::Integer = -1) where {FT}
+    d = zeros(Int32, 3)
+    check(m, ccall((:gb25_field_dims, m.lib), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Int32}), m.ptr, field, 0, d), "gb25_field_dims")
+    out = Array{FT}(undef, Int(d[1]), Int(d[2]), k_count == -1 ? Int(d[3]) - k_first : k_count)
+    check(m, ccall((:gb25_get_field_levels, m.lib), Cint, (Ptr{Cvoid}, Cint, Int32, Int32, Ptr{Cvoid}), m.ptr, field, k_first, k_count, out),
+          "gb25_get_field_levels")
+    return out
 end
 
 end # module

@@ -11,6 +11,7 @@ from .integrals import cell_measure, combine_budgets, combine_moments, fold_reco
 from .model import (CATKEVerticalDiffusivity, default_ocean_closure, Field, HydrostaticFreeSurfaceModel, VerticalScalarDiffusivity,
                     baroclinic_instability_model, budget, density_anomaly, first_time_step, initialize, kinetic_energy,
                     mixed_layer_depth, potential_density, vorticity,
+                    heat_transport, meridional_transport, overturning, section_transport,
                     loop, resolution_to_points, state_monitor, set_baroclinic_instability, set_top_flux, time_step, update_state,
                     tupled_fill_halo_regions_workload, compute_tendencies_workload,
                     compute_boundary_tendencies_workload, compute_interior_momentum_tendencies_workload,
@@ -19,6 +20,7 @@ from .model import (CATKEVerticalDiffusivity, default_ocean_closure, Field, Hydr
                     correct_velocities_and_cache_previous_tendencies_workload)
 from .derived import (gather_derived, kinetic_energy_host, mixed_layer_depth_host, mixed_layer_depth_of_profiles,
                       vorticity_host)
+from .transports import combine_transports, face_area, fold_transports, transport_host, transport_terms
 from .data_free import (PrescribedAtmosphere, analytic_atmosphere, data_free_ocean_climate_model_init,
                         set_prescribed_atmosphere, set_data_free_state, zonal_wind, sunlight, Tatm)
 from .sharding import factors

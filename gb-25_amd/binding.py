@@ -58,10 +58,13 @@ ABI_SYMBOLS = [
     "gb25_get_state_monitor", "gb25_field_device_ptr_readonly",
     "gb25_integrate_field", "gb25_get_budget", "gb25_moments_bytes", "gb25_budget_bytes",
     "gb25_derived_dims", "gb25_compute_derived", "gb25_get_derived", "gb25_get_derived_stats", "gb25_get_field_levels",
+    "gb25_transport_bytes", "gb25_get_transport",
 ]
 # gb25_derived (include/gb25.h)
 DERIVED_IDS = {"vorticity": 0, "kinetic_energy": 1, "density_anomaly": 2, "potential_density": 3, "mixed_layer_depth": 4}
 SUM_SHAPES = {"rows": 0, "levels": 1, "total": 2}   # gb25_sum_shape
+TRANSPORT_FACES = {"across_y": 0, "across_x": 1}                         # gb25_transport_faces
+TRANSPORT_SHAPES = {"lines": 0, "profile": 1, "streamfunction": 2}      # gb25_transport_shape
 # gb25_option (include/gb25.h)
 OPTION_IDS = {"kernels": 0, "ab2_lookahead": 1, "subcycle_lookahead": 2, "subcycle_block": 3, "fill_fused": 4,
               "two_streams": 5, "store_pressure": 6, "split_tendencies": 7, "pressure_precision": 8, "immersed_kernels": 9, "fold_fills": 10,
@@ -161,6 +164,17 @@ class Moments(_Record):
 
 MOMENTS_DTYPE = np.dtype([("measure", np.float64), ("first", np.float64), ("second", np.float64),
                           ("points", np.int64), ("nonfinite", np.int64)])
+
+
+class Transport(_Record):
+    """gb25_transport (include/gb25.h): sum a, sum a vel, sum a vel T, sum a vel S over the wet faces whose values are finite,
+    how many those are, and how many wet faces were skipped because a value is not finite."""
+    _fields_ = [("area", C.c_double), ("volume", C.c_double), ("heat", C.c_double), ("salt", C.c_double),
+                ("faces", C.c_int64), ("nonfinite", C.c_int64)]
+
+
+TRANSPORT_DTYPE = np.dtype([("area", np.float64), ("volume", np.float64), ("heat", np.float64), ("salt", np.float64),
+                            ("faces", np.int64), ("nonfinite", np.int64)])
 
 
 class Budget(_Record):
@@ -301,6 +315,7 @@ def load_library(float_type="Float32"):
     lib.gb25_get_derived.argtypes = [P, C.c_int, C.c_double, C.c_int32, C.c_int32, P]
     lib.gb25_get_derived_stats.argtypes = [P, C.c_int, C.c_double, C.POINTER(FieldStats)]
     lib.gb25_get_field_levels.argtypes = [P, C.c_int, C.c_int32, C.c_int32, P]
+    lib.gb25_get_transport.argtypes = [P, C.c_int, C.c_int, C.c_int32, C.c_int32, P, C.c_int64]
     lib.gb25_profile_enable.argtypes = [P, C.c_int]
     lib.gb25_profile_get.argtypes = [P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     for name in ["gb25_use_own_stream", "gb25_synchronize", "gb25_set_baroclinic_instability", "gb25_initialize",
@@ -320,7 +335,7 @@ def load_library(float_type="Float32"):
                         "the library and gb25_amd/binding.py are of different versions")
     for fn, struct in (("gb25_field_stats_bytes", FieldStats), ("gb25_field_diff_bytes", FieldDiff),
                        ("gb25_state_monitor_bytes", StateMonitor), ("gb25_moments_bytes", Moments),
-                       ("gb25_budget_bytes", Budget)):
+                       ("gb25_budget_bytes", Budget), ("gb25_transport_bytes", Transport)):
         getattr(lib, fn).restype = C.c_int32
         if getattr(lib, fn)() != C.sizeof(struct):
             raise GB25Error(f"{path}: {fn}() = {getattr(lib, fn)()} there, {C.sizeof(struct)} bytes in this binding: "
@@ -511,6 +526,20 @@ class HipBackend:
         out = np.empty((max(nk, 0), d[1], d[0]), dtype=self.dtype)
         self._call("gb25_get_field_levels", FIELD_IDS[name], int(k_first), int(k_count), out.ctypes.data_as(C.c_void_p))
         return out.transpose(2, 1, 0)
+
+    def transport(self, faces, shape="lines", window=None):
+        """gb25_get_transport: area, volume, heat and salt transport through the faces of v ("across_y", summed along i) or of
+        u ("across_x", summed along j), as numpy records of TRANSPORT_DTYPE -- shape "lines": [n, k], one per line (row j /
+        column i) and level; "profile": [n]; "streamfunction": [n, kf], the running sums at the Nz + 1 z faces.  window =
+        (first, count) of the summed index, 0-based local interior, count = -1: to the end; None: all."""
+        d = self.field_dims("v" if faces == "across_y" else "u", False)
+        N, Nz = (d[1] if faces == "across_y" else d[0]), d[2]
+        first, count = (0, -1) if window is None else window
+        nk = {"lines": Nz, "profile": 1, "streamfunction": Nz + 1}[shape]
+        out = np.zeros(N * nk, TRANSPORT_DTYPE)
+        self._call("gb25_get_transport", TRANSPORT_FACES[faces], TRANSPORT_SHAPES[shape], int(first), int(count),
+                   out.ctypes.data_as(C.c_void_p), out.size)
+        return out if shape == "profile" else out.reshape(nk, N).T
 
     def metric(self, name, index=1):
         v = C.c_double()

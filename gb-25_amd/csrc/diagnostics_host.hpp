@@ -1,6 +1,6 @@
 // diagnostics_host.hpp -- host side of gb25_get_field_stats / gb25_compare_field / gb25_get_state_monitor /
 // gb25_field_device_ptr_readonly / gb25_integrate_field / gb25_get_budget / gb25_compute_derived / gb25_get_derived /
-// gb25_get_derived_stats / gb25_get_field_levels (include/gb25.h); the last part of gb25_api.hip, which includes it.  Kernels:
+// gb25_get_derived_stats / gb25_get_field_levels / gb25_get_transport (include/gb25.h); the last part of gb25_api.hip, which includes it.  Kernels:
 // diagnostics_kernels.hpp.  Nothing here writes model memory or a schedule flag: the calls may sit between any two steps.
 #pragma once
 
@@ -142,6 +142,10 @@ gb25_status moments_tables(gb25_model* m) {
   if (m->diag_zt) HIPCHK(hipFree(m->diag_zt));
   m->diag_azff = nullptr;
   m->diag_zt = nullptr;
+  for (int q = 0; q < 2; q++) {
+    if (m->diag_face_length[q]) HIPCHK(hipFree(m->diag_face_length[q]));
+    m->diag_face_length[q] = nullptr;
+  }
   {
     // the derived fields' own: (double) of zc[0 .. Nz) | zf[0 .. Nz] as gb25_get_metric returns them, AZFF of a curvilinear grid
     std::vector<double> zt((size_t)2 * Nz + 1);
@@ -167,6 +171,18 @@ gb25_status moments_tables(gb25_model* m) {
       for (size_t o = 0; o < n2; o++) a[o] = (real)h[o];
       HIPCHK(hipMalloc(&m->diag_area[q], n2 * sizeof(real)));
       HIPCHK(hipMemcpy(m->diag_area[q], a.data(), n2 * sizeof(real), hipMemcpyHostToDevice));
+    }
+  }
+  if (m->g.cv.on) {
+    // the transports' own: the lengths of the y faces (DXCF) and of the x faces (DYFC)
+    static const int ids[2] = {GB25_M2_DXCF, GB25_M2_DYFC};
+    std::vector<real> a(n2);
+    for (int q = 0; q < 2; q++) {
+      const std::vector<double>& h = m->h_curv[ids[q]];
+      if (h.size() != n2) return fail(m, GB25_ERR_STATE, "transports: the curvilinear metrics are not built");
+      for (size_t o = 0; o < n2; o++) a[o] = (real)h[o];
+      HIPCHK(hipMalloc(&m->diag_face_length[q], n2 * sizeof(real)));
+      HIPCHK(hipMemcpy(m->diag_face_length[q], a.data(), n2 * sizeof(real), hipMemcpyHostToDevice));
     }
   }
   if (!m->kbot.empty()) {
@@ -348,9 +364,85 @@ gb25_status derived_run(gb25_model* m, gb25_derived q, double param, int k0, int
   return GB25_OK;
 }
 
+// ---- transports
+static_assert(sizeof(TransportPartial) == sizeof(gb25_transport), "a line record is a gb25_transport");
+
+// once per model: LINES [N Nz], the running sums [N (Nz + 1)] and PROFILE [N] for the longest set of lines a call can ask for
+// (N = by of v for the y faces, Nx for the x faces); the three parts start at multiples of that longest N
+gb25_status transport_buffer(gb25_model* m) {
+  if (m->diag_transport) return GB25_OK;
+  const size_t lines = (size_t)std::max(m->Nx, m->Ny + 1);
+  HIPCHK(hipMalloc(&m->diag_transport, lines * (2 * (size_t)m->cfg.Nz + 2) * sizeof(TransportPartial)));
+  m->diag_transport_lines = lines;
+  return GB25_OK;
+}
+inline TransportPartial* transport_lines(gb25_model* m) { return (TransportPartial*)m->diag_transport; }
+inline TransportPartial* transport_psi(gb25_model* m) { return transport_lines(m) + m->diag_transport_lines * m->cfg.Nz; }
+inline TransportPartial* transport_profile(gb25_model* m) { return transport_psi(m) + m->diag_transport_lines * (m->cfg.Nz + 1); }
+
 }  // namespace
 
 extern "C" {
+
+int32_t gb25_transport_bytes(void) { return (int32_t)sizeof(gb25_transport); }
+
+gb25_status gb25_get_transport(gb25_model* m, gb25_transport_faces faces, gb25_transport_shape shape, int32_t along_first,
+                               int32_t along_count, gb25_transport* out, int64_t count) {
+  if (!m || !out) return GB25_ERR_INVALID_ARGUMENT;
+  if (faces != GB25_ACROSS_Y && faces != GB25_ACROSS_X)
+    return fail(m, GB25_ERR_INVALID_ARGUMENT, "gb25_get_transport: faces must be GB25_ACROSS_Y or GB25_ACROSS_X, got %d", (int)faces);
+  if (shape != GB25_TR_LINES && shape != GB25_TR_PROFILE && shape != GB25_TR_STREAMFUNCTION)
+    return fail(m, GB25_ERR_INVALID_ARGUMENT, "gb25_get_transport: shape must be GB25_TR_LINES, GB25_TR_PROFILE or GB25_TR_STREAMFUNCTION, got %d", (int)shape);
+  const bool ay = faces == GB25_ACROSS_Y;
+  int32_t d[3];
+  if (gb25_field_dims(m, ay ? GB25_V : GB25_U, 0, d)) return GB25_ERR_INVALID_ARGUMENT;
+  const int Nz = d[2], N = ay ? d[1] : d[0], along = ay ? d[0] : d[1];   // lines; the extent of the summed index
+  const long long n = along_count == -1 ? (long long)along - along_first : (long long)along_count;
+  if (along_first < 0 || along_first >= along || along_count < -1 || along_count == 0 || along_first + n > along)
+    return fail(m, GB25_ERR_INVALID_ARGUMENT, "gb25_get_transport: window along_first = %d, along_count = %d of %d %s (0-based local interior indices; along_count = -1: to the end)",
+                (int)along_first, (int)along_count, along, ay ? "columns" : "rows");
+  const int64_t want = shape == GB25_TR_LINES ? (int64_t)N * Nz : shape == GB25_TR_PROFILE ? (int64_t)N : (int64_t)N * (Nz + 1);
+  if (count != want)
+    return fail(m, GB25_ERR_INVALID_ARGUMENT, "gb25_get_transport: this shape has %lld records (lines %d, levels %d), count is %lld",
+                (long long)want, N, Nz, (long long)count);
+  if (gb25_status s = derived_need_device(m, "gb25_get_transport")) return s;
+  const real *vel = nullptr, *T = nullptr, *S = nullptr;
+  if (gb25_status s = diag_source(m, ay ? GB25_V : GB25_U, &vel)) return s;
+  if (gb25_status s = diag_source(m, GB25_T, &T)) return s;
+  if (gb25_status s = diag_source(m, GB25_S, &S)) return s;
+  if (gb25_status s = transport_buffer(m)) return s;
+  if ((size_t)N > m->diag_transport_lines) return fail(m, GB25_ERR_STATE, "gb25_get_transport: more lines than the model's buffer holds");
+  if (gb25_status s = diag_wait_for_model(m)) return s;
+  if (gb25_status s = moments_tables(m)) return s;
+  const Grid& g = m->g;
+  TransportTables tab;
+  tab.length = m->diag_face_length[ay ? 0 : 1];
+  tab.first = m->diag_first_wet[ay ? 2 : 1];
+  tab.pivot_row = (!ay && m->cfg.grid_type >= GB25_GRID_TRIPOLAR && !m->yn_open) ? m->Ny - 1 : -1;
+  TransportPartial* lines = transport_lines(m);
+  {
+    Timed t(m, GB25_K_DIAGNOSTICS);
+    if (ay) {
+      const long long nb = ((long long)N * Nz + DIAG_THREADS / 64 - 1) / (DIAG_THREADS / 64);
+      if (g.cv.on) hipLaunchKernelGGL(k_transport_rows<true>, dim3((unsigned)nb), dim3(DIAG_THREADS), 0, m->stream, g, tab, vel, T, S, (int)along_first, (int)n, N, lines);
+      else hipLaunchKernelGGL(k_transport_rows<false>, dim3((unsigned)nb), dim3(DIAG_THREADS), 0, m->stream, g, tab, vel, T, S, (int)along_first, (int)n, N, lines);
+    } else {
+      const dim3 grd((N + 63) / 64, (Nz + 3) / 4), blk(64, 4);
+      if (g.cv.on) hipLaunchKernelGGL(k_transport_columns<true>, grd, blk, 0, m->stream, g, tab, vel, T, S, (int)along_first, (int)n, lines);
+      else hipLaunchKernelGGL(k_transport_columns<false>, grd, blk, 0, m->stream, g, tab, vel, T, S, (int)along_first, (int)n, lines);
+    }
+    LAUNCHCHK();
+    if (shape != GB25_TR_LINES) {
+      hipLaunchKernelGGL(k_transport_fold, dim3((N + 63) / 64), dim3(64), 0, m->stream, (const TransportPartial*)lines, N, Nz,
+                         transport_psi(m), transport_profile(m));
+      LAUNCHCHK();
+    }
+  }
+  const TransportPartial* from = shape == GB25_TR_LINES ? lines : shape == GB25_TR_PROFILE ? transport_profile(m) : transport_psi(m);
+  HIPCHK(hipMemcpyAsync(out, from, (size_t)count * sizeof(gb25_transport), hipMemcpyDeviceToHost, m->stream));
+  HIPCHK(hipStreamSynchronize(m->stream));
+  return GB25_OK;
+}
 
 gb25_status gb25_derived_dims(const gb25_model* m, gb25_derived q, int32_t dims[3]) {
   if (!m || !dims || q < 0 || q >= GB25_D_COUNT) return GB25_ERR_INVALID_ARGUMENT;

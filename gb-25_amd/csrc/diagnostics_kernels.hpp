@@ -566,4 +566,152 @@ __global__ __launch_bounds__(256) void k_gather_levels(const T* __restrict__ src
   }
 }
 
+// ---- transports (gb25_get_transport): how much water, heat and salt crosses the faces of v (GB25_ACROSS_Y) or of u
+// (GB25_ACROSS_X), summed along a window of i or of j.  Definitions: include/gb25.h.  A face's terms are formed in fp64 on (double)
+// of the stored values with floating-point contraction OFF, in the written order; gb-25_amd/transports.py restates them bit for bit.
+//   k_transport_rows<CURV>     y faces: ONE WAVE takes ONE ROW (j, k) of v's interior, cut into chunks of four like k_field_moments'
+//                     rows; v is read once, T and S twice (rows j - 1 and j), every load of a chunk ahead of its arithmetic; the
+//                     fixed shuffle tree; lines[j + by k].  The sum of a row is fixed but not sequential.
+//   k_transport_columns<CURV>  x faces: ONE THREAD per (i, k) walks j south to north and adds in that order; lanes run along i, so
+//                     u, T(i - 1), T(i), S(i - 1), S(i) and the tables are five coalesced loads a row and more; TR_UNROLL rows'
+//                     loads are issued ahead of their arithmetic.  lines[i + bx k] is the sequential sum of the terms.
+//   k_transport_fold           one lane per line n: psi[n] = 0, psi[n + N (k + 1)] = psi[n + N k] + lines[n + N k] member by member,
+//                     profile[n] = psi[n + N Nz].
+struct TransportPartial {   // = gb25_transport
+  double area, volume, heat, salt;
+  long long faces, nonfinite;
+};
+__device__ __forceinline__ TransportPartial diag_combine(TransportPartial a, const TransportPartial& b) {
+  a.area += b.area;
+  a.volume += b.volume;
+  a.heat += b.heat;
+  a.salt += b.salt;
+  a.faces += b.faces;
+  a.nonfinite += b.nonfinite;
+  return a;
+}
+// diagnostics' own tables of the faces of one direction, parent layout of a (c,f) field like MomentsTables'
+struct TransportTables {
+  const real* length;             // DXCF (y faces) / DYFC (x faces); null: GB25_M_DXF(j) / GB25_M_DY of the LatitudeLongitudeGrid
+  const unsigned short* first;    // first wet level of the face's column (MOMENTS_DRY: none); null: every level is wet
+  int pivot_row;                  // x faces: local row of the GLOBAL pivot row of a folded grid on this rank, else -1
+};
+// one face of area a: skipped whole when one of its five values is not finite
+__device__ __forceinline__ void transport_face(TransportPartial& p, double a, double vel, double t0, double t1, double s0, double s1) {
+#pragma clang fp contract(off)
+  const bool wet = a > 0.0;
+  const bool finite = __builtin_isfinite(vel) && __builtin_isfinite(t0) && __builtin_isfinite(t1) && __builtin_isfinite(s0) && __builtin_isfinite(s1);
+  if (wet && finite) {
+    const double q = a * vel;
+    const double tm = 0.5 * (t0 + t1), sm = 0.5 * (s0 + s1);
+    const double qt = q * tm, qs = q * sm;
+    p.area += a;
+    p.volume += q;
+    p.heat += qt;
+    p.salt += qs;
+  }
+  p.faces += (wet && finite) ? 1 : 0;   // (two counters by value: an if / else here becomes an indexed update in scratch memory)
+  p.nonfinite += (wet && !finite) ? 1 : 0;
+}
+
+// columns [i0, i0 + bx) of the by rows of v's interior
+template <bool CURV>
+__global__ __launch_bounds__(DIAG_THREADS) void k_transport_rows(Grid g, TransportTables tab, const real* __restrict__ v,
+                                                                 const real* __restrict__ T, const real* __restrict__ S, int i0, int bx,
+                                                                 int by, TransportPartial* __restrict__ lines) {
+#pragma clang fp contract(off)
+  const long long r = (long long)blockIdx.x * (DIAG_THREADS / 64) + (threadIdx.x >> 6);
+  if (r >= (long long)by * g.Nz) return;
+  const int lane = threadIdx.x & 63;
+  const int k = (int)(r / by), j = (int)(r - (long long)k * by);
+  TransportPartial p = {0.0, 0.0, 0.0, 0.0, 0, 0};
+  const bool wall = j == g.jws || (j == g.jwn && !g.cv.north_fold);   // (a wall of the GLOBAL grid: dry, nothing is read)
+  if (!wall) {
+    const real* rv = v + der_off(g, g.pl_v, i0, j, k);
+    const real *rt1 = T + der_off(g, g.pl_c, i0, j, k), *rt0 = rt1 - g.sx;
+    const real *rs1 = S + der_off(g, g.pl_c, i0, j, k), *rs0 = rs1 - g.sx;
+    const real* rl = CURV ? tab.length + i2(g, i0, j) : nullptr;
+    const unsigned short* rf = tab.first ? tab.first + i2(g, i0, j) : nullptr;
+    const double dz = (double)g.dzc[k];
+    const double a_row = CURV ? 0.0 : (double)g.dxf[j] * dz;
+    const int mis = diag_misalignment(rv), nchunks = (mis + bx + 3) >> 2;
+    for (int c = lane; c < nchunks; c += 64) {
+      const int x0 = 4 * c - mis;
+      real ev[4], et0[4], et1[4], es0[4], es1[4], el[4];
+      unsigned short ef[4];
+      diag_load4(rv, x0, bx, ev);
+      diag_load4(rt0, x0, bx, et0);
+      diag_load4(rt1, x0, bx, et1);
+      diag_load4(rs0, x0, bx, es0);
+      diag_load4(rs1, x0, bx, es1);
+      if (CURV) diag_load4(rl, x0, bx, el);
+      if (rf) diag_load4(rf, x0, bx, ef);
+#pragma unroll
+      for (int s = 0; s < 4; s++) {
+        const int x = x0 + s;
+        if (x < 0 || x >= bx) continue;
+        const double a = (rf && k < (int)ef[s]) ? 0.0 : (CURV ? (double)el[s] * dz : a_row);
+        transport_face(p, a, (double)ev[s], (double)et0[s], (double)et1[s], (double)es0[s], (double)es1[s]);
+      }
+    }
+    p = diag_wave_reduce(p);
+  }
+  if (lane == 0) lines[r] = p;
+}
+
+// rows [j0, j0 + nj) of u's interior; block 64 x 4: a wave = 64 consecutive i of one level
+constexpr int TR_UNROLL = 4;
+template <bool CURV>
+__global__ __launch_bounds__(256) void k_transport_columns(Grid g, TransportTables tab, const real* __restrict__ u,
+                                                           const real* __restrict__ T, const real* __restrict__ S, int j0, int nj,
+                                                           TransportPartial* __restrict__ lines) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  const int k = blockIdx.y * 4 + __builtin_amdgcn_readfirstlane(threadIdx.y);
+  if (i >= g.Nx || k >= g.Nz) return;
+  const real* length = tab.length;
+  const unsigned short* first = tab.first;
+  const int pivot_row = tab.pivot_row;
+  const double dz = (double)uniform_at(g.dzc, k);
+  const double a_all = CURV ? 0.0 : (double)g.dy * dz;
+  TransportPartial p = {0.0, 0.0, 0.0, 0.0, 0, 0};
+  for (int jb = 0; jb < nj; jb += TR_UNROLL) {
+    real eu[TR_UNROLL], et0[TR_UNROLL], et1[TR_UNROLL], es0[TR_UNROLL], es1[TR_UNROLL], el[TR_UNROLL];
+    unsigned short ef[TR_UNROLL];
+#pragma unroll
+    for (int q = 0; q < TR_UNROLL; q++) {
+      const int j = j0 + (jb + q < nj ? jb + q : jb);   // (addresses stay in the window)
+      const long long o = der_off(g, g.pl_c, i, j, k);
+      eu[q] = u[o];
+      et0[q] = T[o - 1];
+      et1[q] = T[o];
+      es0[q] = S[o - 1];
+      es1[q] = S[o];
+      el[q] = CURV ? length[i2(g, i, j)] : real(0);
+      ef[q] = first ? first[i2(g, i, j)] : (unsigned short)0;
+    }
+#pragma unroll
+    for (int q = 0; q < TR_UNROLL; q++) {
+      if (jb + q >= nj) break;
+      const double fold = (j0 + jb + q == pivot_row) ? 0.5 : 1.0;
+      const double a = k < (int)ef[q] ? 0.0 : (CURV ? (double)el[q] * dz : a_all) * fold;
+      transport_face(p, a, (double)eu[q], (double)et0[q], (double)et1[q], (double)es0[q], (double)es1[q]);
+    }
+  }
+  lines[(long long)i + (long long)g.Nx * k] = p;
+}
+
+__global__ __launch_bounds__(64) void k_transport_fold(const TransportPartial* __restrict__ lines, int N, int Nz,
+                                                       TransportPartial* __restrict__ psi, TransportPartial* __restrict__ profile) {
+  const int n = blockIdx.x * 64 + threadIdx.x;
+  if (n >= N) return;
+  TransportPartial p = {0.0, 0.0, 0.0, 0.0, 0, 0};
+  psi[n] = p;
+  for (int k = 0; k < Nz; k++) {
+    p = diag_combine(p, lines[n + (long long)N * k]);
+    psi[n + (long long)N * (k + 1)] = p;
+  }
+  profile[n] = p;
+}
+
 }  // namespace gb25

@@ -250,6 +250,11 @@ struct gb25_model {
   real* diag_azff = nullptr;
   double* diag_zt = nullptr;
   const double* diag_eos0 = nullptr;
+  // transports (gb25_get_transport): the LINES, running sums and PROFILE records of one call, made by the first call; diagnostics'
+  // own DXCF and DYFC (curvilinear grids), rebuilt with the other tables.  No stepping kernel reads or writes them.
+  void* diag_transport = nullptr;
+  size_t diag_transport_lines = 0;
+  real* diag_face_length[2] = {nullptr, nullptr};
 };
 
 namespace {
@@ -2717,6 +2722,9 @@ void gb25_destroy(gb25_model* m) {
   if (m->diag_derived) hipFree(m->diag_derived);
   if (m->diag_azff) hipFree(m->diag_azff);
   if (m->diag_zt) hipFree(m->diag_zt);
+  if (m->diag_transport) hipFree(m->diag_transport);
+  for (int q = 0; q < 2; q++)
+    if (m->diag_face_length[q]) hipFree(m->diag_face_length[q]);
   for (int q = 0; q < 3; q++) {
     if (m->diag_area[q]) hipFree(m->diag_area[q]);
     if (m->diag_first_wet[q]) hipFree(m->diag_first_wet[q]);

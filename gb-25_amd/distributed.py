@@ -220,6 +220,23 @@ class LocalSlabEnsemble:
         from .integrals import combine_budgets
         return combine_budgets([b.budget() for b in self.backends])
 
+    # transports: likewise (gb-25_amd/transports.py); window = (first, count) of the GLOBAL summed index -- i for "across_y",
+    # j for "across_x" --, clipped to every rank's interior; a rank the window misses is not asked
+    def transport(self, faces, shape="lines", window=None):
+        from .transports import _window, combine_transports
+        y = faces == "across_y"
+        w = _window(window, self.Nx_loc * self.Rx if y else self.Ny_loc * self.Ry)
+        n = self.Nx_loc if y else self.Ny_loc
+        parts, offsets = [], []
+        for b in self.backends:
+            i0, j0 = b.rx * self.Nx_loc, b.ry * self.Ny_loc
+            at = i0 if y else j0
+            lo, hi = max(w.start, at), min(w.stop, at + n)
+            if lo < hi:
+                parts.append(b.transport(faces, "lines", (lo - at, hi - lo)))
+                offsets.append((i0, j0))
+        return combine_transports(parts, faces, offsets, shape)
+
     def set_option(self, name, value):
         for b in self.backends:
             b.set_option(name, value)

@@ -73,16 +73,12 @@ def _first_wet(backend, hloc, Nx, Ny, by, Nz):
     return out
 
 
-def cell_measure(backend, name):
-    """mu of every interior point of the field, float64, shaped like get_field(name, include_halos=False)."""
+def fold_and_wet(backend, name):
+    """(fold [j], wet [i, j, k]) of the measure of every interior point of the field: the factor of the pivot row and the
+    wetness of its location (shared with the face areas of gb-25_amd/transports.py)."""
     hloc, vloc = location(name)
     Nx, by, bz = backend.field_dims(name, False)
     Ny, Nz = backend.field_dims("T", False)[1:]
-    A = _area(backend, hloc, Nx, by)
-    if vloc is None:
-        dz = np.ones(1)
-    else:
-        dz = np.array([backend.metric("dzc" if vloc == "c" else "dzf", k) for k in range(1, bz + 1)], np.float64)
     fold = np.ones(by)
     top_rank = getattr(backend, "ry", 0) == getattr(backend, "Ry", 1) - 1
     if backend.cfg.grid_type in FOLDED_GRID_TYPES and top_rank and hloc != "cf":
@@ -98,6 +94,19 @@ def cell_measure(backend, name):
             wet[:, 0, :] = False             # the southern wall of the global grid
         if by == Ny + 1:
             wet[:, Ny, :] = False            # the northern wall (a folded grid and a rank below a neighbour hold no such row)
+    return fold, wet
+
+
+def cell_measure(backend, name):
+    """mu of every interior point of the field, float64, shaped like get_field(name, include_halos=False)."""
+    hloc, vloc = location(name)
+    Nx, by, bz = backend.field_dims(name, False)
+    A = _area(backend, hloc, Nx, by)
+    if vloc is None:
+        dz = np.ones(1)
+    else:
+        dz = np.array([backend.metric("dzc" if vloc == "c" else "dzf", k) for k in range(1, bz + 1)], np.float64)
+    fold, wet = fold_and_wet(backend, name)
     return ((A[:, :, None] * dz[None, None, :]) * fold[None, :, None]) * wet
 
 

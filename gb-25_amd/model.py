@@ -251,6 +251,39 @@ def mixed_layer_depth(model, threshold=0.03):
     return _derived(model, "mixed_layer_depth", threshold)[:, :, 0]
 
 
+def _transport(model, faces, shape, window=None):
+    b = model.backend
+    if hasattr(b, "transport"):
+        return b.transport(faces, shape, window)
+    from .transports import transport_host          # (a backend without the device reduction)
+    return transport_host(b, faces, shape, window)
+
+
+def meridional_transport(model, window=None):
+    """Volume [m^3/s], heat [degC m^3/s] and salt [(g/kg) m^3/s] transport across every row of y faces, integrated over depth
+    and over the columns of `window` = (first i, count) (None: the whole row), reduced on the device (include/gb25.h,
+    gb25_get_transport): records [j] with members area, volume, heat, salt, faces, nonfinite."""
+    return _transport(model, "across_y", "profile", window)
+
+
+def overturning(model, window=None):
+    """The meridional overturning streamfunction psi [j, kf] in m^3/s at the Nz + 1 z faces of every row of y faces: the
+    northward volume transport accumulated from the bottom, 0 at kf = 0 (divide by 1e6 for Sverdrups)."""
+    return _transport(model, "across_y", "streamfunction", window)["volume"]
+
+
+def heat_transport(model, rho0_cp=1020.0 * 3991.86795711963, window=None):
+    """The meridional heat transport [W] across every row of y faces, [j]: rho0 cp times the depth-integrated sum of
+    a v T (reference density and heat capacity of ClimaOcean's ocean_simulation by default)."""
+    return rho0_cp * meridional_transport(model, window)["heat"]
+
+
+def section_transport(model, i, j_range=None):
+    """The transport through the x faces of column i (0-based interior) between the rows of j_range = (first j, count)
+    (None: every row), integrated over depth: one record -- area, volume, heat, salt, faces, nonfinite."""
+    return _transport(model, "across_x", "profile", j_range)[i]
+
+
 def state_monitor(model):
     """What the progress callback of simulations/ocean_climate_simulation.jl:95-116 prints -- max|u|, |v|, |w|, extrema(T), ...
     plus the advective CFL rate and the number of non-finite values -- reduced on the device: `print(state_monitor(model))`.

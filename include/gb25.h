@@ -605,6 +605,56 @@ gb25_status gb25_get_derived(gb25_model *m, gb25_derived d, double param, int32_
 gb25_status gb25_get_derived_stats(gb25_model *m, gb25_derived d, double param, gb25_field_stats *out);
 gb25_status gb25_get_field_levels(gb25_model *m, gb25_field f, int32_t k_first, int32_t k_count, void *host);
 
+/* ---- transports on the device: how much water, heat and salt crosses a line (csrc/diagnostics_kernels.hpp, k_transport_rows /
+ *      k_transport_columns / k_transport_fold).  The meridional overturning streamfunction, the meridional heat and salt transport,
+ *      the transport through a section.  Same contract as the diagnostics above: the state gb25_get_field would return, halo cells
+ *      included, READ-ONLY for the schedule (nothing pinned, every look-ahead alive), LOCAL on a rank (combine on the host:
+ *      gb-25_amd/transports.py combine_transports), bitwise repeatable, launches under GB25_K_DIAGNOSTICS on the model's stream.
+ *
+ *      THE TERMS of a face, formed in fp64 from (double) of the stored values and of the numbers gb25_get_metric / gb25_get_metric2
+ *      return, in the written order, NO fused multiply-adds (gb-25_amd/transports.py restates them with numpy bit for bit):
+ *        GB25_ACROSS_Y  the faces of v, (c,f,c); interior row j and level k as in gb25_field_dims(GB25_V, 0)
+ *            a  = (dx * DZC(k)) * wet     dx = DXCF(i,j) on the grids with 2-D metrics, GB25_M_DXF(j) on the LatitudeLongitudeGrid;
+ *                                         wet = the (c,f,c) wetness of the integrals' measure: k >= max(kbot(i,j-1), kbot(i,j)), 0 on
+ *                                         a GLOBAL wall row
+ *            q  = a * v(i,j,k)
+ *            qT = q * (0.5 * (T(i,j-1,k) + T(i,j,k)))        qS = q * (0.5 * (S(i,j-1,k) + S(i,j,k)))
+ *        GB25_ACROSS_X  the faces of u, (f,c,c); dims of GB25_U
+ *            a  = ((dy * DZC(k)) * fold(j)) * wet            dy = DYFC(i,j), GB25_M_DY on the LatitudeLongitudeGrid; wet = the (f,c,c)
+ *                                         wetness: k >= max(kbot(i-1,j), kbot(i,j)); fold(j) = 1/2 on the GLOBAL pivot row of a folded
+ *                                         grid as in the (f,c,c) measure, 1 elsewhere (rows of y faces are held once: no factor there)
+ *            q  = a * u(i,j,k),  qT and qS with the tracers averaged over i-1, i
+ *      A face with a > 0 contributes area += a, volume += q, heat += qT, salt += qS, faces++.  If one of its five values (the
+ *      velocity, two T, two S) is not finite the face is skipped whole and counted in nonfinite.  A dry face contributes nothing and a
+ *      wet face has two wet cells: a value in an immersed cell is invisible.  Units: m^2, m^3/s, degC m^3/s, (g/kg) m^3/s.
+ *
+ *      WINDOW: along_first, along_count select the index that is summed -- i for GB25_ACROSS_Y (a basin, a strait), j for
+ *      GB25_ACROSS_X (a section between two latitudes) --, 0-based local interior indices; along_count = -1: to the end.  An empty or
+ *      out-of-range window is GB25_ERR_INVALID_ARGUMENT.
+ *
+ *      SHAPES AND REDUCTION ORDER.  N lines: N = by of GB25_V for GB25_ACROSS_Y (one per row j), N = bx of GB25_U for GB25_ACROSS_X
+ *      (one per column i); Nz levels.
+ *        GB25_TR_LINES           [n + N k].  ACROSS_Y: one wave per row (j, k); a lane takes every 64th chunk of four faces of the
+ *                                window and accumulates in the order of its faces; lanes combine by the fixed shuffle tree (the order
+ *                                of gb25_integrate_field's ROWS).  ACROSS_X: one thread per (i, k) walks j south to north and adds in
+ *                                that order: the record is the SEQUENTIAL sum of the terms, bit for bit.
+ *        GB25_TR_PROFILE         [n] = ((LINES[n, 0] + LINES[n, 1]) + ...) left to right in k, member by member, starting from 0.
+ *        GB25_TR_STREAMFUNCTION  [n + N kf], kf = 0 .. Nz: the running sums at the z faces, psi[n, 0] = 0, psi[n, kf + 1] = psi[n, kf] +
+ *                                LINES[n, kf] in every member, so that psi[n, Nz] == PROFILE[n] bit for bit.  For GB25_ACROSS_Y
+ *                                `volume` is the meridional overturning streamfunction in m^3/s.
+ *      count: N * Nz records for LINES, N for PROFILE, N * (Nz + 1) for STREAMFUNCTION; any other count is
+ *      GB25_ERR_INVALID_ARGUMENT.  The records live in a buffer the model owns (made by the first call, freed by gb25_destroy); a call
+ *      makes one device-to-host copy of exactly the records asked for. */
+typedef enum { GB25_ACROSS_Y = 0, GB25_ACROSS_X = 1 } gb25_transport_faces;
+typedef enum { GB25_TR_LINES = 0, GB25_TR_PROFILE = 1, GB25_TR_STREAMFUNCTION = 2 } gb25_transport_shape;
+typedef struct {
+  double area, volume, heat, salt;
+  int64_t faces, nonfinite;
+} gb25_transport;
+int32_t gb25_transport_bytes(void);     /* sizeof the struct as THIS library was built */
+gb25_status gb25_get_transport(gb25_model *m, gb25_transport_faces faces, gb25_transport_shape shape, int32_t along_first,
+                               int32_t along_count, gb25_transport *out, int64_t count);
+
 /* ---- built-in per-kernel HIP-event timing (bench.py's roofline numbers) */
 gb25_status gb25_profile_enable(gb25_model *m, int on); /* 0: off, 1: every kernel, 2 + k: kernel k alone */
 gb25_status gb25_profile_reset(gb25_model *m);

@@ -19,6 +19,7 @@ export Config, Model, create, destroy!, first_time_step!, time_step!, loop!, ini
        comm_unique_id, comm_init_rccl!, comm_finalize!, set_top_flux!, set_bottom_height!, set_vertical_diffusivity!, set_closure_catke!, CatkeParameters, default_catke_parameters, set_catke_parameters!, set_bottom_drag!, set_tracer_advection_order!, set_prescribed_atmosphere!, compute_atmosphere_ocean_fluxes!, metric2, FIELD, OPTION, METRIC2,
        FieldStats, FieldDiff, StateMonitor, field_stats, compare_field, state_monitor, device_pointer_readonly,
        Moments, Budget, integrate_field, budget, SUM_ROWS, SUM_LEVELS, SUM_TOTAL,
+       Transport, transport, overturning, ACROSS_Y, ACROSS_X, TR_LINES, TR_PROFILE, TR_STREAMFUNCTION,
        DERIVED, derived_dims, compute_derived, get_derived, derived_stats, field_levels
 
 # One library per Oceananigans float type (src/arg_parsing.jl:12-16): Float32 -> libgb25hip.so, Float64 ->
@@ -456,5 +457,30 @@ function field_levels(m::Model{FT}, field::Integer, k_first::Integer = 0, k_coun
           "gb25_get_field_levels")
     return out
 end
+
+# ---- transports on the device (gb25_get_transport): definitions in include/gb25.h.  along_first is 0-based like the ABI;
+#      along_count = -1: to the end.
+const ACROSS_Y, ACROSS_X = Cint(0), Cint(1)
+const TR_LINES, TR_PROFILE, TR_STREAMFUNCTION = Cint(0), Cint(1), Cint(2)
+struct Transport
+    area::Float64; volume::Float64; heat::Float64; salt::Float64
+    faces::Int64; nonfinite::Int64
+end
+"area, volume, heat and salt transport through the y faces (summed along i) or the x faces (summed along j): TR_LINES an (N, Nz) matrix, TR_PROFILE N records, TR_STREAMFUNCTION (N, Nz + 1) running sums."
+function transport(m::Model, faces::Integer, shape::Integer = TR_LINES; along_first::Integer = 0, along_count::Integer = -1)
+    ccall((:gb25_transport_bytes, m.lib), Int32, ()) == sizeof(Transport) ||
+        error("gb25_transport has another size in the library than in GB25HIP.jl: different versions")
+    d = zeros(Int32, 3)
+    check(m, ccall((:gb25_field_dims, m.lib), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Int32}), m.ptr, faces == ACROSS_Y ? FIELD.v : FIELD.u, 0, d),
+          "gb25_field_dims")
+    N, Nz = faces == ACROSS_Y ? Int(d[2]) : Int(d[1]), Int(d[3])
+    nk = shape == TR_LINES ? Nz : shape == TR_PROFILE ? 1 : Nz + 1
+    out = Vector{Transport}(undef, N * nk)
+    check(m, ccall((:gb25_get_transport, m.lib), Cint, (Ptr{Cvoid}, Cint, Cint, Int32, Int32, Ptr{Transport}, Int64),
+                   m.ptr, faces, shape, along_first, along_count, out, length(out)), "gb25_get_transport")
+    return shape == TR_PROFILE ? out : reshape(out, N, nk)
+end
+"the meridional overturning streamfunction [j, kf] in m^3/s"
+overturning(m::Model; kw...) = map(r -> r.volume, transport(m, ACROSS_Y, TR_STREAMFUNCTION; kw...))
 
 end # module

@@ -140,6 +140,7 @@ struct gb25_model {
   int baro_block = 5;                // substeps per barotropic launch (option SUBCYCLE_BLOCK = 1: one launch per substep; 5: 64 x 17 tiles,
                                      // four blocks per CU, every block of a 1440 x 720 launch resident at once: 0.16 ms for 21 substeps against 0.21 with 7)
   int kernel_gen = 2;                // 2: LDS / flux-sharing tendency kernels (tendency_kernels.hpp); 1: direct-stencil kernels
+  int pressure_form = 0;             // option PRESSURE_FORM: 0 = the rule of compute_p_impl; 1 tiles, 2 one row, 3 four rows per thread
   int pressure_bits = 64;            // option PRESSURE_PRECISION: 64 = fp64 EOS + integral (default); 32 = the float type's own
   // single periodic domain: the last writers of u, v (corrector), T, S (tracer look-ahead) and eta, U, V (last barotropic
   // launch) also write the halo cells the fills derive from them, and the fill launches leave the step.  Halo cells
@@ -1147,13 +1148,15 @@ gb25_status compute_p_impl(gb25_model* m, int i_first = INT_MIN, int i_last = IN
   // rank 0.518 -> 0.510; but 720 columns 1.358 -> 1.401 and the folded grid's slabs 0.614 -> 0.617 (180) and 0.978 -> 1.018 (360)
   // beside their heavier curvilinear neighbours: those keep the one-row form.
   const bool narrow = (tiles_a + tiles_b) * ((nrow + PR * 4 - 1) / (PR * 4)) < 1024;
-  if (narrow && !g.cv.on && ncol + ncol_b <= 400) {
+  // (option PRESSURE_FORM forces one form, on any grid: the kernels read no horizontal metric)
+  const int form = m->pressure_form ? m->pressure_form : (narrow && !g.cv.on && ncol + ncol_b <= 400) ? 1 : narrow ? 2 : 3;
+  if (form == 1) {
     const int ta = (i_last - i_first + 1 + 14) / 15, tb = ncol_b ? (i_last_b - i_first_b + 1 + 14) / 15 : 0;
     dim3 gr(ta + tb, (nrow + 11) / 12);
     auto kern = write_p ? k_compute_p_tile<true> : k_compute_p_tile<false>;
     hipLaunchKernelGGL(kern, gr, b, 0, m->stream, g, Tsrc, Ssrc, m->f[GB25_PHY].d, dpx_out, dpy_out, i_first, i_last,
                        i_first_b, i_last_b, ta, n2, j_first, j_last);
-  } else if (narrow) {
+  } else if (form == 2) {
     dim3 gr(tiles_a + tiles_b, (nrow + 3) / 4);
     auto kern = write_p ? k_compute_p<1, true> : k_compute_p<1, false>;
     hipLaunchKernelGGL(kern, gr, b, 0, m->stream, g, Tsrc, Ssrc, m->f[GB25_PHY].d, dpx_out, dpy_out, i_first, i_last,
@@ -3345,6 +3348,10 @@ gb25_status gb25_set_option(gb25_model* m, gb25_option opt, int32_t v) {
       if (v != 32 && v != 64) return fail(m, GB25_ERR_INVALID_ARGUMENT, "GB25_OPT_PRESSURE_PRECISION: 64 or 32");
       m->pressure_bits = (sizeof(real) == 8) ? 64 : v;   // (a Float64 model's own arithmetic IS fp64)
       return GB25_OK;
+    case GB25_OPT_PRESSURE_FORM:
+      if (v < 0 || v > 3) return fail(m, GB25_ERR_INVALID_ARGUMENT, "GB25_OPT_PRESSURE_FORM: 0 (the library's rule), 1 (tiles), 2 (one row per thread) or 3 (four rows per thread)");
+      m->pressure_form = v;
+      return GB25_OK;
     case GB25_OPT_FOLD_FILLS:
       m->fold_fills = v != 0;
       m->complete_fills_needed = 2;
@@ -3418,6 +3425,7 @@ gb25_status gb25_get_option(const gb25_model* m, gb25_option opt, int32_t* v) {
     case GB25_OPT_STORE_PRESSURE: *v = m->phy_pinned; break;
     case GB25_OPT_SPLIT_TENDENCIES: *v = m->split_tendencies; break;
     case GB25_OPT_PRESSURE_PRECISION: *v = m->pressure_bits; break;
+    case GB25_OPT_PRESSURE_FORM: *v = m->pressure_form; break;
     case GB25_OPT_IMMERSED_KERNELS: *v = m->immersed; break;
     case GB25_OPT_FOLD_FILLS: *v = m->fold_fills; break;
     case GB25_OPT_LAZY_CORRECTOR: *v = m->lazy_corrector; break;

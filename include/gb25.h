@@ -175,6 +175,11 @@ typedef enum {
   GB25_OPT_FOLD_PIVOT_SLAVED,    /* [0] TripolarGrid, single domain: 1 = every fold fill also overwrites the eastern half of the pivot row
                                     (cell centres of the last row, held twice) with the image of its western half, as a later upstream
                                     fix does as recalled; 0 = both copies are stepped independently */
+  GB25_OPT_PRESSURE_FORM,        /* [0] which of the three launch forms of the fp64 hydrostatic pressure kernel runs (the same bits from
+                                    each; tests compare every form cell by cell): 0 = the library's rule (four rows per thread for
+                                    wide launches, one row per thread for narrow ones, 16 x 4 tiles for narrow lat-lon launches of
+                                    at most 400 columns); 1 = tiles; 2 = one row per thread; 3 = four rows per thread, on any grid
+                                    and for every launch.  PRESSURE_PRECISION = 32 ignores it */
   GB25_OPT_COUNT
 } gb25_option;
 

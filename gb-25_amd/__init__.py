@@ -8,10 +8,13 @@ from .binding import GB25Error, HipBackend, LIB_PATH, load_library
 from .build import build_library
 from .correctness import approx_equal, combine_diffs, combine_stats, compare_states, sync_states
 from .integrals import cell_measure, combine_budgets, combine_moments, fold_records, integrate_host
+# (the submodule first: the name `averages` of the package is the function of .model, imported after it)
+from .averages import (AveragesHost, average_terms, eddy_flux, eddy_kinetic_energy, gather_averages, tracer_variance)
 from .model import (CATKEVerticalDiffusivity, default_ocean_closure, Field, HydrostaticFreeSurfaceModel, VerticalScalarDiffusivity,
                     baroclinic_instability_model, budget, density_anomaly, first_time_step, initialize, kinetic_energy,
                     mixed_layer_depth, potential_density, vorticity,
                     heat_transport, meridional_transport, overturning, section_transport,
+                    Averages, averages, run_averaged,
                     loop, resolution_to_points, state_monitor, set_baroclinic_instability, set_top_flux, time_step, update_state,
                     tupled_fill_halo_regions_workload, compute_tendencies_workload,
                     compute_boundary_tendencies_workload, compute_interior_momentum_tendencies_workload,

@@ -59,12 +59,18 @@ ABI_SYMBOLS = [
     "gb25_integrate_field", "gb25_get_budget", "gb25_moments_bytes", "gb25_budget_bytes",
     "gb25_derived_dims", "gb25_compute_derived", "gb25_get_derived", "gb25_get_derived_stats", "gb25_get_field_levels",
     "gb25_transport_bytes", "gb25_get_transport",
+    "gb25_averages_info_bytes", "gb25_averages_begin", "gb25_averages_accumulate", "gb25_averages_get_info", "gb25_average_dims",
+    "gb25_get_average", "gb25_average_device_ptr", "gb25_averages_end",
 ]
 # gb25_derived (include/gb25.h)
 DERIVED_IDS = {"vorticity": 0, "kinetic_energy": 1, "density_anomaly": 2, "potential_density": 3, "mixed_layer_depth": 4}
 SUM_SHAPES = {"rows": 0, "levels": 1, "total": 2}   # gb25_sum_shape
 TRANSPORT_FACES = {"across_y": 0, "across_x": 1}                         # gb25_transport_faces
 TRANSPORT_SHAPES = {"lines": 0, "profile": 1, "streamfunction": 2}      # gb25_transport_shape
+AVERAGE_GROUPS = {"means": 1, "squares": 2, "fluxes": 4}              # gb25_average_group
+# gb25_average: name -> id; the first six are the MEANS, the next five the SQUARES, the last six the FLUXES
+AVERAGE_IDS = {n: q for q, n in enumerate(["u", "v", "w", "T", "S", "eta", "uu", "vv", "TT", "SS", "etaeta",
+                                           "uT", "uS", "vT", "vS", "wT", "wS"])}
 # gb25_option (include/gb25.h)
 OPTION_IDS = {"kernels": 0, "ab2_lookahead": 1, "subcycle_lookahead": 2, "subcycle_block": 3, "fill_fused": 4,
               "two_streams": 5, "store_pressure": 6, "split_tendencies": 7, "pressure_precision": 8, "immersed_kernels": 9, "fold_fills": 10,
@@ -189,6 +195,34 @@ class Budget(_Record):
                 "eta: volume %.3e m3, potential energy %.6e m5/s2"
                 % (self.iteration, self.time, self.volume, self.T.first, self.S.first, self.kinetic_energy, self.eta.first,
                    self.eta_potential_energy))
+
+
+class AveragesInfo(_Record):
+    """gb25_averages_info (include/gb25.h): the groups and the window as begun, the samples and the sum of their weights so far,
+    the clock at the first and at the last sample."""
+    _fields_ = [("groups", C.c_int32), ("k_first", C.c_int32), ("k_count", C.c_int32), ("reserved", C.c_int32),
+                ("samples", C.c_int64), ("first_iteration", C.c_int64), ("last_iteration", C.c_int64),
+                ("weight_sum", C.c_double), ("first_time", C.c_double), ("last_time", C.c_double)]
+
+
+def average_group_of(name):
+    """"means" | "squares" | "fluxes": the group a quantity of AVERAGE_IDS belongs to."""
+    q = AVERAGE_IDS[name]
+    return "means" if q <= AVERAGE_IDS["eta"] else "squares" if q <= AVERAGE_IDS["etaeta"] else "fluxes"
+
+
+def average_groups_mask(groups):
+    """The gb25_average_group mask of an iterable of group names (or of a mask)."""
+    if isinstance(groups, int):
+        return groups
+    if isinstance(groups, str):
+        groups = (groups,)
+    mask = 0
+    for g in groups:
+        if g not in AVERAGE_GROUPS:
+            raise ValueError(f"groups must be among {tuple(AVERAGE_GROUPS)}, got {g!r}")
+        mask |= AVERAGE_GROUPS[g]
+    return mask
 
 
 class GB25Error(RuntimeError):
@@ -316,6 +350,13 @@ def load_library(float_type="Float32"):
     lib.gb25_get_derived_stats.argtypes = [P, C.c_int, C.c_double, C.POINTER(FieldStats)]
     lib.gb25_get_field_levels.argtypes = [P, C.c_int, C.c_int32, C.c_int32, P]
     lib.gb25_get_transport.argtypes = [P, C.c_int, C.c_int, C.c_int32, C.c_int32, P, C.c_int64]
+    lib.gb25_averages_begin.argtypes = [P, C.c_int32, C.c_int32, C.c_int32]
+    lib.gb25_averages_accumulate.argtypes = [P, C.c_double]
+    lib.gb25_averages_get_info.argtypes = [P, C.POINTER(AveragesInfo)]
+    lib.gb25_average_dims.argtypes = [P, C.c_int, C.POINTER(C.c_int32)]
+    lib.gb25_get_average.argtypes = [P, C.c_int, C.c_int32, P, C.c_int64]
+    lib.gb25_average_device_ptr.argtypes = [P, C.c_int, C.POINTER(P), C.POINTER(C.c_int32)]
+    lib.gb25_averages_end.argtypes = [P]
     lib.gb25_profile_enable.argtypes = [P, C.c_int]
     lib.gb25_profile_get.argtypes = [P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     for name in ["gb25_use_own_stream", "gb25_synchronize", "gb25_set_baroclinic_instability", "gb25_initialize",
@@ -335,7 +376,8 @@ def load_library(float_type="Float32"):
                         "the library and gb25_amd/binding.py are of different versions")
     for fn, struct in (("gb25_field_stats_bytes", FieldStats), ("gb25_field_diff_bytes", FieldDiff),
                        ("gb25_state_monitor_bytes", StateMonitor), ("gb25_moments_bytes", Moments),
-                       ("gb25_budget_bytes", Budget), ("gb25_transport_bytes", Transport)):
+                       ("gb25_budget_bytes", Budget), ("gb25_transport_bytes", Transport),
+                       ("gb25_averages_info_bytes", AveragesInfo)):
         getattr(lib, fn).restype = C.c_int32
         if getattr(lib, fn)() != C.sizeof(struct):
             raise GB25Error(f"{path}: {fn}() = {getattr(lib, fn)()} there, {C.sizeof(struct)} bytes in this binding: "
@@ -540,6 +582,43 @@ class HipBackend:
         self._call("gb25_get_transport", TRANSPORT_FACES[faces], TRANSPORT_SHAPES[shape], int(first), int(count),
                    out.ctypes.data_as(C.c_void_p), out.size)
         return out if shape == "profile" else out.reshape(nk, N).T
+
+    # ---- time averages accumulated on the device (include/gb25.h: "time averages and eddy fluxes"); names: AVERAGE_IDS
+    def averages_begin(self, groups=("means", "squares", "fluxes"), levels=None):
+        """gb25_averages_begin: allocate and zero the accumulators of `groups` ("means" must be among them) over the cell levels
+        levels = (k_first, k_count), 0-based, k_count = -1 or levels = None: all.  Starts over if averages exist."""
+        k_first, k_count = (0, -1) if levels is None else levels
+        self._call("gb25_averages_begin", average_groups_mask(groups), int(k_first), int(k_count))
+
+    def averages_accumulate(self, weight=1.0):
+        """gb25_averages_accumulate: acc = acc + weight * term for every quantity of the active groups, one launch."""
+        self._call("gb25_averages_accumulate", float(weight))
+
+    def averages_info(self):
+        out = AveragesInfo()
+        self._call("gb25_averages_get_info", C.byref(out))
+        return out
+
+    def average_dims(self, name):
+        d = (C.c_int32 * 3)()
+        self._call("gb25_average_dims", AVERAGE_IDS[name], d)
+        return tuple(d)
+
+    def get_average(self, name, normalized=True):
+        """float64 array [i, j, k] over the active window: the accumulator (normalized = False) or accumulator / weight_sum."""
+        d = self.average_dims(name)
+        out = np.empty(d[::-1], np.float64)
+        self._call("gb25_get_average", AVERAGE_IDS[name], int(bool(normalized)), out.ctypes.data_as(C.c_void_p), out.size)
+        return out.transpose(2, 1, 0)
+
+    def average_device_ptr(self, name):
+        """(device pointer of the packed fp64 accumulator, its dims); read-only, valid until averages_begin / averages_end."""
+        p, d = C.c_void_p(), (C.c_int32 * 3)()
+        self._call("gb25_average_device_ptr", AVERAGE_IDS[name], C.byref(p), d)
+        return p.value, tuple(d)
+
+    def averages_end(self):
+        self._call("gb25_averages_end")
 
     def metric(self, name, index=1):
         v = C.c_double()

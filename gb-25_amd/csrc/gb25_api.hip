@@ -9,6 +9,7 @@
 #include "kernels.hpp"
 #include "tendency_kernels.hpp"
 #include "diagnostics_kernels.hpp"
+#include "averages_kernels.hpp"
 
 #include <cmath>
 #include <cstdarg>
@@ -256,6 +257,13 @@ struct gb25_model {
   void* diag_transport = nullptr;
   size_t diag_transport_lines = 0;
   real* diag_face_length[2] = {nullptr, nullptr};
+  // time averages (gb25_averages_*, averages_host.hpp): the accumulators of the active groups and the array a normalized read-out
+  // is divided into -- ONE allocation, made by gb25_averages_begin, freed by gb25_averages_end and gb25_destroy --, the window,
+  // the sample count and weight_sum (avg_info).  No stepping kernel reads or writes them.
+  double* avg_acc[GB25_A_COUNT] = {};
+  double* avg_out = nullptr;
+  gb25_averages_info avg_info = {};
+  bool avg_on = false;
 };
 
 namespace {
@@ -2726,6 +2734,7 @@ void gb25_destroy(gb25_model* m) {
   if (m->diag_azff) hipFree(m->diag_azff);
   if (m->diag_zt) hipFree(m->diag_zt);
   if (m->diag_transport) hipFree(m->diag_transport);
+  if (m->avg_acc[0]) hipFree(m->avg_acc[0]);
   for (int q = 0; q < 2; q++)
     if (m->diag_face_length[q]) hipFree(m->diag_face_length[q]);
   for (int q = 0; q < 3; q++) {
@@ -3760,3 +3769,4 @@ gb25_status gb25_profile_get(gb25_model* m, gb25_kernel k, int64_t* launches, do
 }  // extern "C"
 
 #include "diagnostics_host.hpp"
+#include "averages_host.hpp"

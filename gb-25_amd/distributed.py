@@ -237,6 +237,25 @@ class LocalSlabEnsemble:
                 offsets.append((i0, j0))
         return combine_transports(parts, faces, offsets, shape)
 
+    # time averages: likewise (gb-25_amd/averages.py); every slab accumulates its own interior, the read-out is placed by
+    # global offset
+    def averages_begin(self, groups=("means", "squares", "fluxes"), levels=None):
+        for b in self.backends:
+            b.averages_begin(groups, levels)
+
+    def averages_sample(self, weight=1.0):
+        for b in self.backends:
+            b.averages_accumulate(weight)
+
+    def average(self, name, normalized=True):
+        from .averages import gather_averages
+        return gather_averages([b.get_average(name, normalized) for b in self.backends],
+                               [(b.rx * self.Nx_loc, b.ry * self.Ny_loc) for b in self.backends])
+
+    def averages_end(self):
+        for b in self.backends:
+            b.averages_end()
+
     def set_option(self, name, value):
         for b in self.backends:
             b.set_option(name, value)

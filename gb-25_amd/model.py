@@ -284,6 +284,96 @@ def section_transport(model, i, j_range=None):
     return _transport(model, "across_x", "profile", j_range)[i]
 
 
+class Averages:
+    """The handle `averages(model, ...)` returns: time averages accumulated where the fields live (include/gb25.h, "time
+    averages and eddy fluxes accumulated on the device").  sample() between two composite calls adds the state, weighted, to
+    fp64 accumulators on the device -- one launch, nothing downloaded --; mean / raw copy one quantity to the host.  Names:
+    u v w T S eta (means), uu vv TT SS etaeta (squares), uT uS vT vS wT wS (fluxes at the faces of the velocity)."""
+
+    def __init__(self, model, groups=("means", "squares", "fluxes"), levels=None):
+        self.model = model
+        b = model.backend
+        self._clock = b.clock
+        self._previous_iteration = None
+        if hasattr(b, "averages_begin"):
+            b.averages_begin(groups, levels)
+            self._dev, self._host = b, None
+        else:                                            # (a backend without the device kernel: the numpy restatement)
+            from .averages import AveragesHost
+            self._dev, self._host = None, AveragesHost(b, groups, levels)
+
+    def sample(self, weight=None):
+        """Add the model's state as it is now.  weight: default the clock's last_dt times the iterations since the previous
+        sample (last_dt for the first sample), so that a mean over samples taken at uneven intervals is a time mean."""
+        _, iteration, last_dt = self._clock()
+        if weight is None:
+            steps = 1 if self._previous_iteration is None else max(1, iteration - self._previous_iteration)
+            weight = last_dt * steps
+        if self._dev:
+            self._dev.averages_accumulate(weight)
+        else:
+            self._host.sample(weight)
+        self._previous_iteration = iteration
+        return self
+
+    def info(self):
+        return self._dev.averages_info() if self._dev else self._host.info()
+
+    def mean(self, name):
+        """accumulator / weight_sum, float64 [i, j, k] over the window."""
+        return self._dev.get_average(name, True) if self._dev else self._host.mean(name)
+
+    def raw(self, name):
+        """The accumulator itself: sum of weight * term."""
+        return self._dev.get_average(name, False) if self._dev else self._host.raw(name)
+
+    def eddy_flux(self, name):
+        """<v'T'> = <vT> - <v> <T at the face> ("uT", "uS", "vT", "vS", "wT", "wS"), gb25_amd.averages.eddy_flux of the means."""
+        from .averages import eddy_flux
+        return eddy_flux({n: self.mean(n) for n in (name[0], name[1], name)}, name)
+
+    def eddy_kinetic_energy(self):
+        from .averages import eddy_kinetic_energy
+        return eddy_kinetic_energy({n: self.mean(n) for n in ("u", "v", "uu", "vv")})
+
+    def tracer_variance(self, name):
+        from .averages import tracer_variance
+        return tracer_variance({n: self.mean(n) for n in (name, name + name)}, name)
+
+    def close(self):
+        if self._dev:
+            if getattr(self._dev, "h", None):
+                self._dev.averages_end()
+        else:
+            self._host.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def averages(model, groups=("means", "squares", "fluxes"), levels=None):
+    """Start accumulating time averages of `groups` ("means" must be among them) over the cell levels levels = (k_first,
+    k_count), 0-based (None: all); returns the Averages handle: `a = averages(model); loop(model, 10); a.sample(); ...;
+    a.mean("T"); a.eddy_flux("vT"); a.close()`."""
+    return Averages(model, groups, levels)
+
+
+def run_averaged(model, steps, every, **kw):
+    """loop(model, every) then sample(), repeated until `steps` steps are done (a remainder shorter than `every` is stepped and
+    sampled last); returns the Averages handle.  kw: groups, levels of averages()."""
+    a = averages(model, **kw)
+    done = 0
+    while done < steps:
+        n = min(int(every), steps - done)
+        loop(model, n)
+        a.sample()
+        done += n
+    return a
+
+
 def state_monitor(model):
     """What the progress callback of simulations/ocean_climate_simulation.jl:95-116 prints -- max|u|, |v|, |w|, extrema(T), ...
     plus the advective CFL rate and the number of non-finite values -- reduced on the device: `print(state_monitor(model))`.

@@ -660,6 +660,63 @@ int32_t gb25_transport_bytes(void);     /* sizeof the struct as THIS library was
 gb25_status gb25_get_transport(gb25_model *m, gb25_transport_faces faces, gb25_transport_shape shape, int32_t along_first,
                                int32_t along_count, gb25_transport *out, int64_t count);
 
+/* ---- time averages and eddy fluxes accumulated on the device (csrc/averages_kernels.hpp, k_averages_accumulate): what the other
+ *      diagnostics cannot do -- remember something between two calls.  The time-mean state, eddy kinetic energy and tracer
+ *      variance, the eddy heat and salt fluxes <v'T'>, <u'T'>, <w'T'>: Oceananigans' AveragedTimeInterval, without five parent arrays
+ *      crossing PCIe per sample.  A sample is taken by an explicit call between two composite calls.  Same contract as the
+ *      diagnostics above: the state gb25_get_field would return, READ-ONLY for the schedule (nothing pinned, every look-ahead alive;
+ *      the only memory written is the accumulators' own), LOCAL on a rank (a rank's interior; gather by global_offset:
+ *      gb-25_amd/averages.py gather_averages), bitwise repeatable, launches under GB25_K_DIAGNOSTICS on the model's stream.
+ *
+ *      DEFINITIONS.  Values are read from the parent arrays as gb25_get_field(f, host, 1) returns them at that moment, halo cells
+ *      included.  Every operation in fp64 on (double) of the stored values, in the written order, NO fused multiply-adds
+ *      (gb-25_amd/averages.py restates them with numpy bit for bit).  Indices are 0-based interior; i-1, j-1 reach one halo column
+ *      or row (and the wall row of v the halo row of tracers beyond it).  THE TERM of a quantity at a point:
+ *        MEANS    GB25_A_U, _V, _W, _T, _S, _ETA   x, at the field's own location, with the interior dims of that field
+ *        SQUARES  GB25_A_UU, _VV, _TT, _SS, _ETAETA   x * x
+ *        FLUXES   GB25_A_UT, _US at (f,c,c), dims of u:  u(i,j,k) * (0.5 * (T(i-1,j,k) + T(i,j,k)))
+ *                 GB25_A_VT, _VS at (c,f,c), dims of v:  v(i,j,k) * (0.5 * (T(i,j-1,k) + T(i,j,k)))
+ *                 GB25_A_WT, _WS at (c,c,f), dims of w:  w(i,j,k) * (0.5 * (T(i,j,k-1) + T(i,j,k))) at the faces 1 .. Nz-1; exactly 0
+ *                 at the bottom face 0 and at the top face Nz: no halo level is ever read
+ *      ACCUMULATION: one sample adds acc = acc + weight * term (two roundings); weight_sum = weight_sum + weight on the host.
+ *      NO MASK AND NO MEASURE: immersed cells hold what the model stores there.  A value that is not finite poisons the accumulator
+ *      cells whose term reads it and nothing else.
+ *      LEVEL WINDOW: k_first, k_count select CELL levels, 0-based; k_count = -1: all from k_first on (as for the derived fields).  A
+ *      (c,c,f) quantity covers the k_count + 1 faces that bound them; the 2-D quantities ignore the window.  The window is what
+ *      makes the accumulators of a very large model fit: 8 bytes per point and quantity.
+ *      READ-OUT: gb25_get_average copies exactly the accumulator; normalized != 0: acc / weight_sum, one IEEE fp64 division per
+ *      element done on the device.  PACKED, i fastest, dims as gb25_average_dims reports for the active window (before
+ *      gb25_averages_begin: for the whole column); one device-to-host copy; any other count is GB25_ERR_INVALID_ARGUMENT.
+ *
+ *      gb25_averages_begin allocates and zeroes the accumulators of the requested groups only; GB25_AVG_MEANS must be among them
+ *      (the eddy parts need the means).  The size is checked against the free device memory BEFORE anything is allocated:
+ *      GB25_ERR_OUT_OF_MEMORY leaves nothing allocated.  On a model that already has averages it starts over.
+ *      gb25_averages_accumulate: GB25_ERR_STATE before gb25_averages_begin; a weight that is not finite and > 0 is
+ *      GB25_ERR_INVALID_ARGUMENT and touches nothing.  ONE launch per sample whatever the groups; complete when the call returns.
+ *      A quantity of a group that was not asked for is GB25_ERR_INVALID_ARGUMENT.  gb25_average_device_ptr: the accumulator where
+ *      it lives, read-only, valid until gb25_averages_begin / gb25_averages_end / gb25_destroy, which free the accumulators. */
+typedef enum { GB25_AVG_MEANS = 1, GB25_AVG_SQUARES = 2, GB25_AVG_FLUXES = 4 } gb25_average_group;
+typedef enum {
+  GB25_A_U = 0, GB25_A_V, GB25_A_W, GB25_A_T, GB25_A_S, GB25_A_ETA,          /* MEANS   */
+  GB25_A_UU, GB25_A_VV, GB25_A_TT, GB25_A_SS, GB25_A_ETAETA,                 /* SQUARES */
+  GB25_A_UT, GB25_A_US, GB25_A_VT, GB25_A_VS, GB25_A_WT, GB25_A_WS,          /* FLUXES  */
+  GB25_A_COUNT
+} gb25_average;
+/* groups, k_first, k_count (resolved: never -1): as begun; samples, weight_sum: so far; the clock at the first and the last sample */
+typedef struct {
+  int32_t groups, k_first, k_count, reserved;
+  int64_t samples, first_iteration, last_iteration;
+  double weight_sum, first_time, last_time;
+} gb25_averages_info;
+int32_t     gb25_averages_info_bytes(void);   /* sizeof the struct as THIS library was built */
+gb25_status gb25_averages_begin(gb25_model *m, int32_t groups, int32_t k_first, int32_t k_count);
+gb25_status gb25_averages_accumulate(gb25_model *m, double weight);
+gb25_status gb25_averages_get_info(const gb25_model *m, gb25_averages_info *info);
+gb25_status gb25_average_dims(const gb25_model *m, gb25_average a, int32_t dims[3]);
+gb25_status gb25_get_average(gb25_model *m, gb25_average a, int32_t normalized, double *host, int64_t count);
+gb25_status gb25_average_device_ptr(gb25_model *m, gb25_average a, const double **dev, int32_t device_dims[3]);
+gb25_status gb25_averages_end(gb25_model *m);
+
 /* ---- built-in per-kernel HIP-event timing (bench.py's roofline numbers) */
 gb25_status gb25_profile_enable(gb25_model *m, int on); /* 0: off, 1: every kernel, 2 + k: kernel k alone */
 gb25_status gb25_profile_reset(gb25_model *m);

@@ -20,7 +20,9 @@ export Config, Model, create, destroy!, first_time_step!, time_step!, loop!, ini
        FieldStats, FieldDiff, StateMonitor, field_stats, compare_field, state_monitor, device_pointer_readonly,
        Moments, Budget, integrate_field, budget, SUM_ROWS, SUM_LEVELS, SUM_TOTAL,
        Transport, transport, overturning, ACROSS_Y, ACROSS_X, TR_LINES, TR_PROFILE, TR_STREAMFUNCTION,
-       DERIVED, derived_dims, compute_derived, get_derived, derived_stats, field_levels
+       DERIVED, derived_dims, compute_derived, get_derived, derived_stats, field_levels,
+       AVG_MEANS, AVG_SQUARES, AVG_FLUXES, AVERAGE, AveragesInfo, averages_begin, averages_accumulate, averages_info, average_dims,
+       get_average, averages_end
 
 # One library per Oceananigans float type (src/arg_parsing.jl:12-16): Float32 -> libgb25hip.so, Float64 ->
 # libgb25hip_f64.so; same symbols, gb25_real_bytes() tells them apart.
@@ -482,5 +484,43 @@ function transport(m::Model, faces::Integer, shape::Integer = TR_LINES; along_fi
 end
 "the meridional overturning streamfunction [j, kf] in m^3/s"
 overturning(m::Model; kw...) = map(r -> r.volume, transport(m, ACROSS_Y, TR_STREAMFUNCTION; kw...))
+
+# ---- time averages accumulated on the device (gb25_averages_*): definitions in include/gb25.h.  k_first is 0-based like the ABI;
+#      k_count = -1: all levels from k_first on.
+const AVG_MEANS, AVG_SQUARES, AVG_FLUXES = Int32(1), Int32(2), Int32(4)
+const AVERAGE = (u = 0, v = 1, w = 2, T = 3, S = 4, eta = 5, uu = 6, vv = 7, TT = 8, SS = 9, etaeta = 10,
+                 uT = 11, uS = 12, vT = 13, vS = 14, wT = 15, wS = 16)
+struct AveragesInfo
+    groups::Int32; k_first::Int32; k_count::Int32; reserved::Int32
+    samples::Int64; first_iteration::Int64; last_iteration::Int64
+    weight_sum::Float64; first_time::Float64; last_time::Float64
+end
+"allocate and zero the accumulators of `groups` (AVG_MEANS must be among them) over the cell levels k_first .. k_first + k_count - 1"
+function averages_begin(m::Model, groups::Integer = AVG_MEANS | AVG_SQUARES | AVG_FLUXES; k_first::Integer = 0, k_count::Integer = -1)
+    ccall((:gb25_averages_info_bytes, m.lib), Int32, ()) == sizeof(AveragesInfo) ||
+        error("gb25_averages_info has another size in the library than in GB25HIP.jl: different versions")
+    check(m, ccall((:gb25_averages_begin, m.lib), Cint, (Ptr{Cvoid}, Int32, Int32, Int32), m.ptr, groups, k_first, k_count), "gb25_averages_begin")
+end
+"acc = acc + weight * term for every quantity of the active groups: one launch, between two composite calls"
+averages_accumulate(m::Model, weight::Real = 1.0) =
+    check(m, ccall((:gb25_averages_accumulate, m.lib), Cint, (Ptr{Cvoid}, Float64), m.ptr, weight), "gb25_averages_accumulate")
+function averages_info(m::Model)
+    out = Ref{AveragesInfo}()
+    check(m, ccall((:gb25_averages_get_info, m.lib), Cint, (Ptr{Cvoid}, Ptr{AveragesInfo}), m.ptr, out), "gb25_averages_get_info")
+    return out[]
+end
+function average_dims(m::Model, a::Integer)
+    d = zeros(Int32, 3)
+    check(m, ccall((:gb25_average_dims, m.lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Int32}), m.ptr, a, d), "gb25_average_dims")
+    return (Int(d[1]), Int(d[2]), Int(d[3]))
+end
+"the accumulator of AVERAGE.x over the active window, or (normalized) accumulator / weight_sum: a Float64 array (i, j, k)"
+function get_average(m::Model, a::Integer; normalized::Bool = true)
+    out = Array{Float64}(undef, average_dims(m, a)...)
+    check(m, ccall((:gb25_get_average, m.lib), Cint, (Ptr{Cvoid}, Cint, Int32, Ptr{Float64}, Int64), m.ptr, a, normalized ? 1 : 0, out, length(out)),
+          "gb25_get_average")
+    return out
+end
+averages_end(m::Model) = check(m, ccall((:gb25_averages_end, m.lib), Cint, (Ptr{Cvoid},), m.ptr), "gb25_averages_end")
 
 end # module

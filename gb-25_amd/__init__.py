@@ -14,6 +14,7 @@ from .model import (CATKEVerticalDiffusivity, default_ocean_closure, Field, Hydr
                     baroclinic_instability_model, budget, density_anomaly, first_time_step, initialize, kinetic_energy,
                     mixed_layer_depth, potential_density, vorticity,
                     heat_transport, meridional_transport, overturning, section_transport,
+                    overturning_in_classes, water_mass_census,
                     Averages, averages, run_averaged,
                     loop, resolution_to_points, state_monitor, set_baroclinic_instability, set_top_flux, time_step, update_state,
                     tupled_fill_halo_regions_workload, compute_tendencies_workload,
@@ -24,6 +25,8 @@ from .model import (CATKEVerticalDiffusivity, default_ocean_closure, Field, Hydr
 from .derived import (gather_derived, kinetic_energy_host, mixed_layer_depth_host, mixed_layer_depth_of_profiles,
                       vorticity_host)
 from .transports import combine_transports, face_area, fold_transports, transport_host, transport_terms
+from .classes import (class_bins, class_edges, class_sums_host, class_terms, class_values, combine_class_sums, fold_classes,
+                      total_classes)
 from .data_free import (PrescribedAtmosphere, analytic_atmosphere, data_free_ocean_climate_model_init,
                         set_prescribed_atmosphere, set_data_free_state, zonal_wind, sunlight, Tatm)
 from .sharding import factors

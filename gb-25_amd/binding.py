@@ -59,6 +59,7 @@ ABI_SYMBOLS = [
     "gb25_integrate_field", "gb25_get_budget", "gb25_moments_bytes", "gb25_budget_bytes",
     "gb25_derived_dims", "gb25_compute_derived", "gb25_get_derived", "gb25_get_derived_stats", "gb25_get_field_levels",
     "gb25_transport_bytes", "gb25_get_transport",
+    "gb25_class_sum_bytes", "gb25_get_class_sums",
     "gb25_averages_info_bytes", "gb25_averages_begin", "gb25_averages_accumulate", "gb25_averages_get_info", "gb25_average_dims",
     "gb25_get_average", "gb25_average_device_ptr", "gb25_averages_end",
 ]
@@ -67,6 +68,10 @@ DERIVED_IDS = {"vorticity": 0, "kinetic_energy": 1, "density_anomaly": 2, "poten
 SUM_SHAPES = {"rows": 0, "levels": 1, "total": 2}   # gb25_sum_shape
 TRANSPORT_FACES = {"across_y": 0, "across_x": 1}                         # gb25_transport_faces
 TRANSPORT_SHAPES = {"lines": 0, "profile": 1, "streamfunction": 2}      # gb25_transport_shape
+CLASS_WHAT = {"faces_y": 0, "cells": 1}                                   # gb25_class_what
+CLASS_VARIABLES = {"T": 0, "S": 1, "potential_density": 2}                # gb25_class_variable
+CLASS_SHAPES = {"rows": 0, "cumulative": 1, "total": 2}                   # gb25_class_shape
+CLASS_MAX_BINS = 256                                                      # GB25_CLASS_MAX_BINS
 AVERAGE_GROUPS = {"means": 1, "squares": 2, "fluxes": 4}              # gb25_average_group
 # gb25_average: name -> id; the first six are the MEANS, the next five the SQUARES, the last six the FLUXES
 AVERAGE_IDS = {n: q for q, n in enumerate(["u", "v", "w", "T", "S", "eta", "uu", "vv", "TT", "SS", "etaeta",
@@ -181,6 +186,17 @@ class Transport(_Record):
 
 TRANSPORT_DTYPE = np.dtype([("area", np.float64), ("volume", np.float64), ("heat", np.float64), ("salt", np.float64),
                             ("faces", np.int64), ("nonfinite", np.int64)])
+
+
+class ClassSum(_Record):
+    """gb25_class_sum (include/gb25.h): the sums of one class (bin) -- FACES_Y: a, a v, a v T, a v S of the wet faces; CELLS: V, 0,
+    V T, V S of the wet cells --, how many contributed, and (bin 0 of a row only) how many were skipped as not finite."""
+    _fields_ = [("measure", C.c_double), ("flow", C.c_double), ("heat", C.c_double), ("salt", C.c_double),
+                ("count", C.c_int64), ("nonfinite", C.c_int64)]
+
+
+CLASS_SUM_DTYPE = np.dtype([("measure", np.float64), ("flow", np.float64), ("heat", np.float64), ("salt", np.float64),
+                            ("count", np.int64), ("nonfinite", np.int64)])
 
 
 class Budget(_Record):
@@ -350,6 +366,7 @@ def load_library(float_type="Float32"):
     lib.gb25_get_derived_stats.argtypes = [P, C.c_int, C.c_double, C.POINTER(FieldStats)]
     lib.gb25_get_field_levels.argtypes = [P, C.c_int, C.c_int32, C.c_int32, P]
     lib.gb25_get_transport.argtypes = [P, C.c_int, C.c_int, C.c_int32, C.c_int32, P, C.c_int64]
+    lib.gb25_get_class_sums.argtypes = [P, C.c_int, C.c_int, P, C.c_int32, C.c_int, C.c_int32, C.c_int32, P, C.c_int64]
     lib.gb25_averages_begin.argtypes = [P, C.c_int32, C.c_int32, C.c_int32]
     lib.gb25_averages_accumulate.argtypes = [P, C.c_double]
     lib.gb25_averages_get_info.argtypes = [P, C.POINTER(AveragesInfo)]
@@ -377,6 +394,7 @@ def load_library(float_type="Float32"):
     for fn, struct in (("gb25_field_stats_bytes", FieldStats), ("gb25_field_diff_bytes", FieldDiff),
                        ("gb25_state_monitor_bytes", StateMonitor), ("gb25_moments_bytes", Moments),
                        ("gb25_budget_bytes", Budget), ("gb25_transport_bytes", Transport),
+                       ("gb25_class_sum_bytes", ClassSum),
                        ("gb25_averages_info_bytes", AveragesInfo)):
         getattr(lib, fn).restype = C.c_int32
         if getattr(lib, fn)() != C.sizeof(struct):
@@ -582,6 +600,22 @@ class HipBackend:
         self._call("gb25_get_transport", TRANSPORT_FACES[faces], TRANSPORT_SHAPES[shape], int(first), int(count),
                    out.ctypes.data_as(C.c_void_p), out.size)
         return out if shape == "profile" else out.reshape(nk, N).T
+
+    def class_sums(self, what, variable, edges, shape="rows", window=None):
+        """gb25_get_class_sums: sums in the B = len(edges) + 1 classes of `variable` ("T", "S", "potential_density") over the
+        faces of v ("faces_y": area, volume, heat and salt transport) or the cells of T ("cells": volume, 0, heat and salt
+        content), as numpy records of CLASS_SUM_DTYPE -- shape "rows": [n, b], one per row j and bin; "cumulative": [n, e], the
+        running sums over the bins from 0 (B + 1 of them); "total": [b], the rows added south to north.  window = (first,
+        count) of i, 0-based local interior, count = -1: to the end; None: all."""
+        N = self.field_dims("v" if what == "faces_y" else "T", False)[1]
+        edges = np.ascontiguousarray(edges, np.float64).reshape(-1)
+        B = edges.size + 1
+        first, count = (0, -1) if window is None else window
+        records = {"rows": N * B, "cumulative": N * (B + 1), "total": B}[shape]
+        out = np.zeros(records, CLASS_SUM_DTYPE)
+        self._call("gb25_get_class_sums", CLASS_WHAT[what], CLASS_VARIABLES[variable], edges.ctypes.data_as(C.c_void_p),
+                   edges.size, CLASS_SHAPES[shape], int(first), int(count), out.ctypes.data_as(C.c_void_p), out.size)
+        return out if shape == "total" else out.reshape(N, -1)
 
     # ---- time averages accumulated on the device (include/gb25.h: "time averages and eddy fluxes"); names: AVERAGE_IDS
     def averages_begin(self, groups=("means", "squares", "fluxes"), levels=None):

@@ -475,6 +475,13 @@ __global__ __launch_bounds__(256) void k_derived_kinetic_energy(Grid g, const re
   }
 }
 
+// rho - rho0 of one cell from the table `c` of its level: teos10_level on s, t formed as k_compute_p forms them.  Shared by
+// k_derived_density and the class sums (class_kernels.hpp), which must bin the very bits the former stores.
+__device__ __forceinline__ double derived_density_value(const double* __restrict__ c, real t, real s) {
+  const double sc = 0.875 / 35.16504;
+  return teos10_level(c, sqrt_pos(((double)s + 32.0) * sc), (double)t * 0.025);
+}
+
 // rho(T, S, z_k) - rho0 (POT: rho(T, S, 0) - rho0, one table `eos0` folded at Z = 0) at (c,c,c); 0 in the immersed cells
 // (first_wet: diagnostics' table of the (c,c) columns, null on a grid without a bottom table)
 template <bool POT>
@@ -486,14 +493,13 @@ __global__ __launch_bounds__(256) void k_derived_density(Grid g, const real* __r
   if (j >= d.by) return;
   const bool in = i < d.bx;
   const int ii = in ? i : d.bx - 1;
-  const double sc = 0.875 / 35.16504;
   const int kb = first_wet ? (int)first_wet[i2(g, ii, j)] : 0;
   const int kk0 = blockIdx.z * DER_LEVELS;
   for (int q = 0; q < DER_LEVELS && kk0 + q < d.k_count; q++) {
     const int k = d.k_first + kk0 + q;
     const double* c = POT ? eos0 : g.eos + 28 * k;
     const long long o = der_off(g, g.pl_c, ii, j, k);
-    const double rho = teos10_level(c, sqrt_pos(((double)S[o] + 32.0) * sc), (double)T[o] * 0.025);
+    const double rho = derived_density_value(c, T[o], S[o]);
     if (in) d.out[der_out(d, i, j, kk0 + q)] = k < kb ? real(0) : (real)rho;
   }
 }

@@ -10,6 +10,7 @@
 #include "tendency_kernels.hpp"
 #include "diagnostics_kernels.hpp"
 #include "averages_kernels.hpp"
+#include "class_kernels.hpp"
 
 #include <cmath>
 #include <cstdarg>
@@ -257,6 +258,10 @@ struct gb25_model {
   void* diag_transport = nullptr;
   size_t diag_transport_lines = 0;
   real* diag_face_length[2] = {nullptr, nullptr};
+  // class sums (gb25_get_class_sums, classes_host.hpp): the padded edges, then the ROWS, CUMULATIVE and TOTAL records of one call;
+  // made by the first call, made anew when a call needs more bins.  No stepping kernel reads or writes them.
+  void* diag_class = nullptr;
+  size_t diag_class_rows = 0, diag_class_bins = 0;
   // time averages (gb25_averages_*, averages_host.hpp): the accumulators of the active groups and the array a normalized read-out
   // is divided into -- ONE allocation, made by gb25_averages_begin, freed by gb25_averages_end and gb25_destroy --, the window,
   // the sample count and weight_sum (avg_info).  No stepping kernel reads or writes them.
@@ -2734,6 +2739,7 @@ void gb25_destroy(gb25_model* m) {
   if (m->diag_azff) hipFree(m->diag_azff);
   if (m->diag_zt) hipFree(m->diag_zt);
   if (m->diag_transport) hipFree(m->diag_transport);
+  if (m->diag_class) hipFree(m->diag_class);
   if (m->avg_acc[0]) hipFree(m->avg_acc[0]);
   for (int q = 0; q < 2; q++)
     if (m->diag_face_length[q]) hipFree(m->diag_face_length[q]);
@@ -3770,3 +3776,4 @@ gb25_status gb25_profile_get(gb25_model* m, gb25_kernel k, int64_t* launches, do
 
 #include "diagnostics_host.hpp"
 #include "averages_host.hpp"
+#include "classes_host.hpp"

@@ -237,6 +237,20 @@ class LocalSlabEnsemble:
                 offsets.append((i0, j0))
         return combine_transports(parts, faces, offsets, shape)
 
+    # sums in classes: likewise (gb-25_amd/classes.py); window = (first, count) of the GLOBAL i, clipped to every rank's interior
+    def class_sums(self, what, variable, edges, shape="rows", window=None):
+        from .classes import combine_class_sums
+        from .transports import _window
+        w = _window(window, self.Nx_loc * self.Rx)
+        parts, offsets = [], []
+        for b in self.backends:
+            i0, j0 = b.rx * self.Nx_loc, b.ry * self.Ny_loc
+            lo, hi = max(w.start, i0), min(w.stop, i0 + self.Nx_loc)
+            if lo < hi:
+                parts.append(b.class_sums(what, variable, edges, "rows", (lo - i0, hi - lo)))
+                offsets.append((i0, j0))
+        return combine_class_sums(parts, what, offsets, shape)
+
     # time averages: likewise (gb-25_amd/averages.py); every slab accumulates its own interior, the read-out is placed by
     # global offset
     def averages_begin(self, groups=("means", "squares", "fluxes"), levels=None):

@@ -284,6 +284,28 @@ def section_transport(model, i, j_range=None):
     return _transport(model, "across_x", "profile", j_range)[i]
 
 
+def _class_sums(model, what, variable, edges, shape, window=None):
+    b = model.backend
+    if hasattr(b, "class_sums"):
+        return b.class_sums(what, variable, edges, shape, window)
+    from .classes import class_sums_host             # (a backend without the device reduction)
+    return class_sums_host(b, what, variable, edges, shape, window)
+
+
+def overturning_in_classes(model, edges, variable="potential_density", window=None):
+    """The meridional overturning streamfunction in classes of `variable` ("potential_density", "T", "S"), psi [j, e] in m^3/s
+    for every row of y faces and e = 0 .. len(edges) + 1: the northward volume transport of the water lighter (colder, fresher)
+    than edge e - 1, accumulated from the first class, 0 at e = 0 -- the residual overturning of a run with eddies, binned and
+    reduced on the device (include/gb25.h, gb25_get_class_sums).  edges: class_edges(lo, hi, n) or any increasing vector."""
+    return _class_sums(model, "faces_y", variable, edges, "cumulative", window)["flow"]
+
+
+def water_mass_census(model, edges, variable="potential_density", by_row=False):
+    """How much water sits in each class of `variable`: records [b] (by_row: [j, b]) with measure = volume [m^3], heat = the
+    volume integral of T, salt = that of S, count = the wet cells, reduced on the device (gb25_get_class_sums)."""
+    return _class_sums(model, "cells", variable, edges, "rows" if by_row else "total")
+
+
 class Averages:
     """The handle `averages(model, ...)` returns: time averages accumulated where the fields live (include/gb25.h, "time
     averages and eddy fluxes accumulated on the device").  sample() between two composite calls adds the state, weighted, to

@@ -660,6 +660,57 @@ int32_t gb25_transport_bytes(void);     /* sizeof the struct as THIS library was
 gb25_status gb25_get_transport(gb25_model *m, gb25_transport_faces faces, gb25_transport_shape shape, int32_t along_first,
                                int32_t along_count, gb25_transport *out, int64_t count);
 
+/* ---- sums in classes on the device: the overturning in density (or temperature, or salinity) classes and the water-mass census
+ *      (csrc/class_kernels.hpp, k_class_rows / k_class_fold).  The transport through every row of y faces sorted by the class of
+ *      the water that crosses -- the residual overturning psi(y, sigma) that a run with eddies is read by --, and how much volume,
+ *      heat and salt sits in each class at each latitude, without v, T, S and a density array crossing PCIe.  Same contract as the
+ *      diagnostics above: the state gb25_get_field would return, halo cells included, READ-ONLY for the schedule (nothing pinned,
+ *      every look-ahead alive), LOCAL on a rank (combine on the host: gb-25_amd/classes.py combine_class_sums), bitwise
+ *      repeatable, launches under GB25_K_DIAGNOSTICS on the model's stream.
+ *
+ *      CLASSES: edges holds n_edges finite, strictly increasing doubles, 1 <= n_edges <= GB25_CLASS_MAX_BINS - 1; B = n_edges + 1
+ *      bins, the first and the last open-ended.  The bin of a class value c is the number of edges e with e <= c
+ *      (np.searchsorted(edges, c, side="right")).  Anything else is GB25_ERR_INVALID_ARGUMENT.
+ *      THE CLASS VALUE of a cell: GB25_CLASS_T, GB25_CLASS_S: (double) of the stored T or S.  GB25_CLASS_POTENTIAL_DENSITY:
+ *      (double) of rho(T, S, 0) - rho0 rounded to the library's float type: the bits gb25_get_derived(GB25_D_POTENTIAL_DENSITY)
+ *      hands out for a wet cell, evaluated by the same device function (also in the tracer halo row a rank of a mesh reads; no
+ *      density array is made).  The class of a y face: 0.5 * (c(i,j-1,k) + c(i,j,k)) in fp64, no fused multiply-add.
+ *      THE TERMS, fp64, in the written order, NO fused multiply-adds (gb-25_amd/classes.py restates them with numpy bit for bit):
+ *        GB25_CL_FACES_Y  the faces of v; rows and levels of gb25_field_dims(GB25_V, 0); a, q, qT, qS of
+ *                         gb25_get_transport(GB25_ACROSS_Y) with their wetness and wall rows:
+ *                         measure += a, flow += q, heat += qT, salt += qS
+ *        GB25_CL_CELLS    the cells of T; V = the measure mu of gb25_integrate_field for a (c,c,c) field (area, thickness, 1/2 on
+ *                         the pivot row, wet mask): measure += V, flow += exactly 0, heat += V * T, salt += V * S
+ *      A wet face (cell) contributes to the bin of its class and to count.  If one of its values -- the velocity, the two T, the
+ *      two S of a face, T and S of a cell, or the class value -- is not finite it is skipped whole and counted in nonfinite of
+ *      BIN 0 of its row.  A dry face (cell) contributes nothing: a value in an immersed cell is invisible.
+ *      WINDOW: i_first, i_count select the columns that are summed, 0-based local interior indices; i_count = -1: to the end.  An
+ *      empty or out-of-range window is GB25_ERR_INVALID_ARGUMENT.
+ *
+ *      SHAPES AND THE ORDER OF EVERY SUM.  N rows: by of GB25_V for GB25_CL_FACES_Y, by of GB25_T for GB25_CL_CELLS; Nz levels.
+ *      The level partial p(n, k, b) is the SEQUENTIAL sum, starting from +0.0, of the terms of bin b over i ascending in the
+ *      window, every member on its own.
+ *        GB25_CL_ROWS             [n B + b] = ((0 + p(n, 0, b)) + p(n, 1, b)) + ..., left to right in k.
+ *        GB25_CL_ROWS_CUMULATIVE  [n (B + 1) + e], e = 0 .. B: psi[n, 0] = 0, psi[n, e + 1] = psi[n, e] + ROWS[n, e], member by
+ *                                 member.  With GB25_CLASS_POTENTIAL_DENSITY and GB25_CL_FACES_Y, `flow` is the overturning
+ *                                 streamfunction in density classes in m^3/s, accumulated from the lightest class.
+ *        GB25_CL_TOTAL            [b] = the sequential sum of ROWS[n, b] over n ascending, member by member, starting from 0.
+ *      count: N B, N (B + 1) or B records; any other count is GB25_ERR_INVALID_ARGUMENT.  The records live in a buffer the model
+ *      owns (made by the first call, made anew when a call asks for more bins, freed by gb25_destroy); a call makes one
+ *      device-to-host copy of exactly the records asked for. */
+#define GB25_CLASS_MAX_BINS 256
+typedef enum { GB25_CLASS_T = 0, GB25_CLASS_S = 1, GB25_CLASS_POTENTIAL_DENSITY = 2 } gb25_class_variable;
+typedef enum { GB25_CL_FACES_Y = 0, GB25_CL_CELLS = 1 } gb25_class_what;
+typedef enum { GB25_CL_ROWS = 0, GB25_CL_ROWS_CUMULATIVE = 1, GB25_CL_TOTAL = 2 } gb25_class_shape;
+typedef struct {
+  double measure, flow, heat, salt;
+  int64_t count, nonfinite;
+} gb25_class_sum;
+int32_t     gb25_class_sum_bytes(void);   /* sizeof the struct as THIS library was built */
+gb25_status gb25_get_class_sums(gb25_model *m, gb25_class_what what, gb25_class_variable variable, const double *edges,
+                                int32_t n_edges, gb25_class_shape shape, int32_t i_first, int32_t i_count, gb25_class_sum *out,
+                                int64_t count);
+
 /* ---- time averages and eddy fluxes accumulated on the device (csrc/averages_kernels.hpp, k_averages_accumulate): what the other
  *      diagnostics cannot do -- remember something between two calls.  The time-mean state, eddy kinetic energy and tracer
  *      variance, the eddy heat and salt fluxes <v'T'>, <u'T'>, <w'T'>: Oceananigans' AveragedTimeInterval, without five parent arrays

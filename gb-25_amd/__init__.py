@@ -27,6 +27,9 @@ from .derived import (gather_derived, kinetic_energy_host, mixed_layer_depth_hos
 from .transports import combine_transports, face_area, fold_transports, transport_host, transport_terms
 from .classes import (class_bins, class_edges, class_sums_host, class_terms, class_values, combine_class_sums, fold_classes,
                       total_classes)
+# (the submodule first, as for the averages: the name `particles` of the package is the function)
+from .particles import (Particles, ParticlesHost, advance_host, exchange_particles, particle_rates, particles, run_with_particles,
+                        sample_host, seed_particles, seed_positions)
 from .data_free import (PrescribedAtmosphere, analytic_atmosphere, data_free_ocean_climate_model_init,
                         set_prescribed_atmosphere, set_data_free_state, zonal_wind, sunlight, Tatm)
 from .sharding import factors

@@ -62,6 +62,8 @@ ABI_SYMBOLS = [
     "gb25_class_sum_bytes", "gb25_get_class_sums",
     "gb25_averages_info_bytes", "gb25_averages_begin", "gb25_averages_accumulate", "gb25_averages_get_info", "gb25_average_dims",
     "gb25_get_average", "gb25_average_device_ptr", "gb25_averages_end",
+    "gb25_particles_info_bytes", "gb25_particles_begin", "gb25_particles_set", "gb25_particles_get", "gb25_particles_advance",
+    "gb25_particles_sample", "gb25_particles_get_info", "gb25_particles_end",
 ]
 # gb25_derived (include/gb25.h)
 DERIVED_IDS = {"vorticity": 0, "kinetic_energy": 1, "density_anomaly": 2, "potential_density": 3, "mixed_layer_depth": 4}
@@ -76,6 +78,9 @@ AVERAGE_GROUPS = {"means": 1, "squares": 2, "fluxes": 4}              # gb25_ave
 # gb25_average: name -> id; the first six are the MEANS, the next five the SQUARES, the last six the FLUXES
 AVERAGE_IDS = {n: q for q, n in enumerate(["u", "v", "w", "T", "S", "eta", "uu", "vv", "TT", "SS", "etaeta",
                                            "uT", "uS", "vT", "vS", "wT", "wS"])}
+# gb25_particle_status, gb25_particle_counter
+PARTICLE_STATUS = {"active": 0, "at_fold": 1, "outside": 2, "nonfinite": 3}
+PARTICLE_COUNTERS = ("blocked", "clamped_y", "clamped_z", "at_fold", "outside", "nonfinite", "too_far")
 # gb25_option (include/gb25.h)
 OPTION_IDS = {"kernels": 0, "ab2_lookahead": 1, "subcycle_lookahead": 2, "subcycle_block": 3, "fill_fused": 4,
               "two_streams": 5, "store_pressure": 6, "split_tendencies": 7, "pressure_precision": 8, "immersed_kernels": 9, "fold_fills": 10,
@@ -219,6 +224,17 @@ class AveragesInfo(_Record):
     _fields_ = [("groups", C.c_int32), ("k_first", C.c_int32), ("k_count", C.c_int32), ("reserved", C.c_int32),
                 ("samples", C.c_int64), ("first_iteration", C.c_int64), ("last_iteration", C.c_int64),
                 ("weight_sum", C.c_double), ("first_time", C.c_double), ("last_time", C.c_double)]
+
+
+class ParticlesInfo(_Record):
+    """gb25_particles_info (include/gb25.h): how many particles and how much room; the accepted advance calls, their substeps and
+    the model time they covered; the counters (PARTICLE_COUNTERS, then one reserved) of the last advance call and of all."""
+    _fields_ = [("count", C.c_int64), ("capacity", C.c_int64), ("calls", C.c_int64), ("substeps", C.c_int64),
+                ("time_advanced", C.c_double), ("last", C.c_int64 * 8), ("total", C.c_int64 * 8)]
+
+    def counters(self, which="last"):
+        """{name: count} of the last advance call (which = "last") or of all calls ("total")."""
+        return dict(zip(PARTICLE_COUNTERS, getattr(self, which)))
 
 
 def average_group_of(name):
@@ -374,6 +390,13 @@ def load_library(float_type="Float32"):
     lib.gb25_get_average.argtypes = [P, C.c_int, C.c_int32, P, C.c_int64]
     lib.gb25_average_device_ptr.argtypes = [P, C.c_int, C.POINTER(P), C.POINTER(C.c_int32)]
     lib.gb25_averages_end.argtypes = [P]
+    lib.gb25_particles_begin.argtypes = [P, C.c_int64]
+    lib.gb25_particles_set.argtypes = [P, C.c_int64, C.c_int64, P, P, P, P, P, P]
+    lib.gb25_particles_get.argtypes = [P, C.c_int64, C.c_int64, P, P, P, P, P, P, P]
+    lib.gb25_particles_advance.argtypes = [P, C.c_double, C.c_int32]
+    lib.gb25_particles_sample.argtypes = [P, C.c_int, P, C.c_int64]
+    lib.gb25_particles_get_info.argtypes = [P, C.POINTER(ParticlesInfo)]
+    lib.gb25_particles_end.argtypes = [P]
     lib.gb25_profile_enable.argtypes = [P, C.c_int]
     lib.gb25_profile_get.argtypes = [P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     for name in ["gb25_use_own_stream", "gb25_synchronize", "gb25_set_baroclinic_instability", "gb25_initialize",
@@ -395,7 +418,7 @@ def load_library(float_type="Float32"):
                        ("gb25_state_monitor_bytes", StateMonitor), ("gb25_moments_bytes", Moments),
                        ("gb25_budget_bytes", Budget), ("gb25_transport_bytes", Transport),
                        ("gb25_class_sum_bytes", ClassSum),
-                       ("gb25_averages_info_bytes", AveragesInfo)):
+                       ("gb25_averages_info_bytes", AveragesInfo), ("gb25_particles_info_bytes", ParticlesInfo)):
         getattr(lib, fn).restype = C.c_int32
         if getattr(lib, fn)() != C.sizeof(struct):
             raise GB25Error(f"{path}: {fn}() = {getattr(lib, fn)()} there, {C.sizeof(struct)} bytes in this binding: "
@@ -653,6 +676,47 @@ class HipBackend:
 
     def averages_end(self):
         self._call("gb25_averages_end")
+
+    # ---- Lagrangian particles on the device (include/gb25.h: "Lagrangian particles advected and sampled on the device")
+    def particles_begin(self, capacity):
+        """gb25_particles_begin: room for `capacity` particles; starts over if the model has particles."""
+        self._call("gb25_particles_begin", int(capacity))
+
+    def particles_set(self, i, j, k, a, b, c, first=0):
+        """gb25_particles_set: particles [first, first + len(i)) from host arrays, ACTIVE; first + len(i) becomes the count."""
+        ints = [np.ascontiguousarray(x, np.int32).reshape(-1) for x in (i, j, k)]
+        dbl = [np.ascontiguousarray(x, np.float64).reshape(-1) for x in (a, b, c)]
+        n = ints[0].size
+        if any(x.size != n for x in ints + dbl):
+            raise ValueError("particles_set: i, j, k, a, b, c must have the same length")
+        self._call("gb25_particles_set", int(first), n, *[x.ctypes.data_as(C.c_void_p) for x in ints + dbl])
+
+    def particles_get(self, first=0, count=None):
+        """gb25_particles_get: {"i", "j", "k" (int32), "a", "b", "c" (float64), "status" (int32)} of particles [first, first + count)."""
+        n = self.particles_info().count - first if count is None else int(count)
+        out = {q: np.zeros(max(n, 0), np.int32) for q in ("i", "j", "k")}
+        out.update({q: np.zeros(max(n, 0), np.float64) for q in ("a", "b", "c")})
+        out["status"] = np.zeros(max(n, 0), np.int32)
+        self._call("gb25_particles_get", int(first), n, *[out[q].ctypes.data_as(C.c_void_p) for q in ("i", "j", "k", "a", "b", "c", "status")])
+        return out
+
+    def particles_advance(self, dt, substeps=1):
+        """gb25_particles_advance: `substeps` midpoint substeps of dt / substeps on the fields as they are now; one launch."""
+        self._call("gb25_particles_advance", float(dt), int(substeps))
+
+    def particles_sample(self, name):
+        """gb25_particles_sample: the value of the (c,c,c) field `name` in every particle's cell, float64 [n]."""
+        out = np.zeros(self.particles_info().count, np.float64)
+        self._call("gb25_particles_sample", FIELD_IDS[name], out.ctypes.data_as(C.c_void_p), out.size)
+        return out
+
+    def particles_info(self):
+        out = ParticlesInfo()
+        self._call("gb25_particles_get_info", C.byref(out))
+        return out
+
+    def particles_end(self):
+        self._call("gb25_particles_end")
 
     def metric(self, name, index=1):
         v = C.c_double()

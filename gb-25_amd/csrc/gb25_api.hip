@@ -11,6 +11,7 @@
 #include "diagnostics_kernels.hpp"
 #include "averages_kernels.hpp"
 #include "class_kernels.hpp"
+#include "particle_kernels.hpp"
 
 #include <cmath>
 #include <cstdarg>
@@ -269,6 +270,19 @@ struct gb25_model {
   double* avg_out = nullptr;
   gb25_averages_info avg_info = {};
   bool avg_on = false;
+  // Lagrangian particles (gb25_particles_*, particles_host.hpp): ONE allocation made by gb25_particles_begin, freed by
+  // gb25_particles_end and gb25_destroy -- two copies of the state (an advance reads part_state[part_cur] and writes the other),
+  // the sample array, the per-wave counter slots and their totals, the kbot table of every column the parents hold (made anew
+  // when the bottom is rebuilt).  No stepping kernel reads or writes them.
+  void* part_base = nullptr;
+  PartState part_state[2] = {};
+  int part_cur = 0;
+  double* part_sample = nullptr;
+  unsigned* part_slots = nullptr;
+  unsigned long long* part_totals = nullptr;
+  int* part_kbot = nullptr;
+  bool part_on = false, part_tables_valid = false;
+  gb25_particles_info part_info = {};
 };
 
 namespace {
@@ -411,6 +425,7 @@ gb25_status upload_table(gb25_model* m, const std::vector<double>& h, int off, c
 
 gb25_status build_grid(gb25_model* m) {
   m->diag_tables_valid = false;   // (the integrals' own tables follow the grid: rebuilt by the next call that needs them)
+  m->part_tables_valid = false;   // (likewise the particles' kbot table)
   const gb25_config& c = m->cfg;
   const int H = c.halo, Ny = m->Ny, Nz = c.Nz;
   // (the row tables of a rank of a 2-D decomposition also cover the rows its sub-cycle is widened by)
@@ -649,6 +664,7 @@ void curv_metrics_at(const gb25_model* m, int ig, int j, double out[GB25_M2_COUN
 // (device_common.hpp, Curv).
 gb25_status build_curv_grid(gb25_model* m) {
   m->diag_tables_valid = false;   // (the integrals' own tables follow the grid: rebuilt by the next call that needs them)
+  m->part_tables_valid = false;   // (likewise the particles' kbot table)
   const gb25_config& c = m->cfg;
   const int Nx = m->Nx, Ny = m->Ny, H = c.halo, sx = Nx + 2 * H, sy = Ny + 2 * H + 1;
   const size_t n2 = (size_t)sx * sy;
@@ -813,6 +829,7 @@ void build_substeps(gb25_model* m) {
 template <class ZB>
 gb25_status build_bottom(gb25_model* m, ZB zb) {
   m->diag_tables_valid = false;   // (the integrals' own tables follow the grid: rebuilt by the next call that needs them)
+  m->part_tables_valid = false;   // (likewise the particles' kbot table)
   const gb25_config& c = m->cfg;
   const int Nx = m->Nx, Ny = m->Ny, Nz = c.Nz, H = c.halo, offk = m->metric_off_k, j0 = m->j0;
   const int E = std::max(H, m->W) + 4, ksx = Nx + 2 * E;
@@ -2741,6 +2758,7 @@ void gb25_destroy(gb25_model* m) {
   if (m->diag_transport) hipFree(m->diag_transport);
   if (m->diag_class) hipFree(m->diag_class);
   if (m->avg_acc[0]) hipFree(m->avg_acc[0]);
+  if (m->part_base) hipFree(m->part_base);
   for (int q = 0; q < 2; q++)
     if (m->diag_face_length[q]) hipFree(m->diag_face_length[q]);
   for (int q = 0; q < 3; q++) {
@@ -3777,3 +3795,4 @@ gb25_status gb25_profile_get(gb25_model* m, gb25_kernel k, int64_t* launches, do
 #include "diagnostics_host.hpp"
 #include "averages_host.hpp"
 #include "classes_host.hpp"
+#include "particles_host.hpp"

@@ -20,7 +20,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from .binding import HipBackend, StateMonitor
+from .binding import GB25Error, HipBackend, StateMonitor
 from .correctness import combine_diffs, combine_stats, _best   # noqa: F401  (combine_*: the host arithmetic over ranks)
 from .model import HydrostaticFreeSurfaceModel
 from .sharding import mesh_neighbours, slab_neighbours
@@ -269,6 +269,80 @@ class LocalSlabEnsemble:
     def averages_end(self):
         for b in self.backends:
             b.averages_end()
+
+    # Lagrangian particles: every slab advances its own on the device; the hand-over of the particles that left a slab runs on
+    # the host after each advance (gb-25_amd/particles.py exchange_particles).  Cells are GLOBAL here; x slabs and the 2-D mesh.
+    def _offsets(self):
+        return [(b.rx * self.Nx_loc, b.ry * self.Ny_loc) for b in self.backends]
+
+    def _particles_put(self, parts):
+        for b, p in zip(self.backends, parts):
+            b.particles_set(p["i"], p["j"], p["k"], p["a"], p["b"], p["c"], 0)
+        self._parts = parts
+
+    def particles_begin(self, i, j, k, a=0.5, b=0.5, c=0.5):
+        """Start particles in the GLOBAL cells (i, j, k); each goes to the slab that owns its cell."""
+        from .particles import make_state
+        s = make_state(i, j, k, a, b, c)
+        s["id"] = np.arange(s["i"].size)
+        parts = []
+        for be, (i0, j0) in zip(self.backends, self._offsets()):
+            own = (s["i"] >= i0) & (s["i"] < i0 + self.Nx_loc) & (s["j"] >= j0) & (s["j"] < j0 + self.Ny_loc)
+            p = {q: x[own] for q, x in s.items()}
+            p["i"], p["j"] = (p["i"] - i0).astype(np.int32), (p["j"] - j0).astype(np.int32)
+            parts.append(p)
+            be.particles_begin(s["i"].size)
+        self._particles_put(parts)
+        self.particles_moved = 0
+
+    def particles_advance(self, dt, substeps=1):
+        """Advance the particles of every slab over dt in `substeps` midpoint substeps and hand over those that left their slab
+        after EVERY substep (a particle that has left waits for the hand-over, so a slab makes one substep per call; advance(dt, n)
+        equals n calls of advance(dt / n, 1) bit for bit, which makes this the single domain's advance(dt, substeps)).  A slab
+        that refuses (more than one cell per call) leaves every slab's particles where they were before the call."""
+        from .particles import exchange_particles
+        saved = self._parts
+        for _ in range(int(substeps)):
+            for b in self.backends:
+                try:
+                    b.particles_advance(float(dt) / float(int(substeps)), 1)
+                except GB25Error:
+                    self._particles_put(saved)     # (the slabs before it, and the substeps before this one, had moved theirs)
+                    raise
+            parts = []
+            for b, old in zip(self.backends, self._parts):
+                p = b.particles_get()
+                p["id"] = old["id"]
+                parts.append(p)
+            parts, moved = exchange_particles(parts, self._offsets(), (self.Nx_loc, self.Ny_loc))
+            self.particles_moved += moved
+            if moved:
+                self._particles_put(parts)
+            else:
+                self._parts = parts
+
+    def _by_id(self, arrays):
+        ids = np.concatenate([p["id"] for p in self._parts])
+        out = np.concatenate(arrays)
+        res = np.empty_like(out)
+        res[ids] = out
+        return res
+
+    def particles_positions(self):
+        """{"i", "j", "k" (GLOBAL cells), "a", "b", "c", "status", "rank"} in the order the particles were given."""
+        Nx = self.Nx_loc * self.Rx
+        out = {q: self._by_id([p[q] for p in self._parts]) for q in ("k", "a", "b", "c", "status")}
+        out["i"] = self._by_id([(p["i"] + i0) % Nx for p, (i0, _) in zip(self._parts, self._offsets())]).astype(np.int32)
+        out["j"] = self._by_id([p["j"] + j0 for p, (_, j0) in zip(self._parts, self._offsets())]).astype(np.int32)
+        out["rank"] = self._by_id([np.full(p["i"].size, r) for r, p in enumerate(self._parts)])
+        return out
+
+    def particles_sample(self, name):
+        return self._by_id([b.particles_sample(name) for b in self.backends])
+
+    def particles_end(self):
+        for b in self.backends:
+            b.particles_end()
 
     def set_option(self, name, value):
         for b in self.backends:

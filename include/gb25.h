@@ -768,6 +768,88 @@ gb25_status gb25_get_average(gb25_model *m, gb25_average a, int32_t normalized, 
 gb25_status gb25_average_device_ptr(gb25_model *m, gb25_average a, const double **dev, int32_t device_dims[3]);
 gb25_status gb25_averages_end(gb25_model *m);
 
+/* ---- Lagrangian particles advected and sampled on the device (csrc/particle_kernels.hpp, k_particles_advance / k_particles_sample):
+ *      where the water goes and what T and S it carries on the way -- Oceananigans' LagrangianParticles -- without u, v, w crossing
+ *      PCIe after every step.  Same contract as the diagnostics above: the state gb25_get_field would return, halo cells included,
+ *      READ-ONLY for the schedule (nothing pinned, every look-ahead alive; the only memory written is the particles' own
+ *      allocation), LOCAL on a rank (the host hands particles over: gb-25_amd/particles.py exchange_particles), bitwise repeatable,
+ *      launches under GB25_K_DIAGNOSTICS on the model's stream.
+ *
+ *      A PARTICLE is a cell (i, j, k), int32, 0-based in the rank's interior, the fractions (a, b, c), doubles in [0, 1), from the
+ *      cell's western x face, southern y face and lower z face, and a status.  It sits at the index coordinates xi = i + a,
+ *      eta = j + b, zeta = k + c.  A cell plus a fraction, not one double: the arithmetic does not depend on where the cell lies,
+ *      so the ranks of a decomposition compute the bits of the single domain.
+ *
+ *      THE RATE of a position in cell (i, j, k), in cells per second: each component linear between the cell's own two faces in its
+ *      own direction (the C-grid form whose normal rate vanishes on a wall or an immersed face).  fp64 on (double) of the stored
+ *      values, IEEE divisions, NO fused multiply-adds, in the written order (gb-25_amd/particles.py restates all of this section
+ *      with numpy bit for bit):
+ *          dxi   = (1 - a) * (u(i, j, k) / dxu(i, j)) + a * (u(i+1, j, k) / dxu(i+1, j))
+ *          deta  = (1 - b) * (v(i, j, k) / dyv(i, j)) + b * (v(i, j+1, k) / dyv(i, j+1))
+ *          dzeta = ((1 - c) * w(i, j, k) + c * w(i, j, k+1)) / dzc(k)
+ *      dxu = DXFC(i, j) on the grids with 2-D metrics, GB25_M_DXC(j) on the LatitudeLongitudeGrid; dyv = DYCF(i, j), GB25_M_DY there;
+ *      dzc = GB25_M_DZC(k): the numbers gb25_get_metric / gb25_get_metric2 return.  Before a cell index enters an address it is
+ *      clamped to [-halo, N + halo - 2] in its direction: no position reads outside an allocation.
+ *      ONE SUBSTEP of length h = dt / substeps, a midpoint step on frozen fields, for an ACTIVE particle at p:
+ *          r0 = rate(p);  pm = move(p, (0.5 * h) * r0);  r1 = rate(pm);  p <- move(p, h * r1)
+ *      A displacement with a component that is not finite or not below 2^30 cells in magnitude freezes the particle where it is
+ *      (at p) with GB25_PARTICLE_NONFINITE: a NaN in the fields stays where it is.
+ *      move(p, d), component by component: a' = a + d; n = floor(a'); i += n; a' -= n; if a' >= 1 (a tiny negative d added to
+ *      a = 1 - ulp rounds to 1) then i += 1, a' = 0.  Then, in this order:
+ *        x     on a single periodic domain i wraps modulo Nx;
+ *        y     below the GLOBAL southern wall: j = its row, b = 0; at or beyond the northern wall (on a folded grid: beyond the
+ *              pivot row): j = the last row, b = the largest double below 1;
+ *        z     below the first wet level kbot of the column the SUBSTEP STARTED IN: k = kbot, c = 0; at or above Nz: k = Nz - 1,
+ *              c = the largest double below 1;
+ *        dry   if kbot of the column it ends in (a halo column included) is above k: i, j, a, b return to their values at p
+ *              (the horizontal move is undone, the vertical move is kept).
+ *      The events of the SECOND move of a substep -- the one the particle makes -- are counted: clamped_y, clamped_z, blocked.
+ *      After it:  folded grid: a particle with eta >= Ny - 0.5 (the centres of the pivot row) gets GB25_PARTICLE_AT_FOLD (also
+ *      one found there when a substep starts) and is never advanced again; carrying particles through the zipper is not done.
+ *      A rank with a neighbour on a side (x slabs, 2-D mesh): i may become -1 or Nx (j likewise) -- the particle keeps its
+ *      rank-local position, gets GB25_PARTICLE_OUTSIDE and waits for the host to hand it over.  Either move of a substep ending
+ *      more than one cell beyond the interior refuses the WHOLE CALL: GB25_ERR_STATE, "more than one cell per call: more substeps
+ *      or a shorter dt", no particle is moved, last[GB25_PC_TOO_FAR] says how many particles asked for it.  A particle that leaves
+ *      in one substep of a call sits out the rest of it: a rank makes ONE substep per call and the host hands over in between
+ *      (gb-25_amd/distributed.py does), which by the next sentence is the single domain's advance(dt, substeps) bit for bit.
+ *      Particles that are not GB25_PARTICLE_ACTIVE are not advanced; all are sampled.  advance(dt, n) equals n calls of
+ *      advance(dt / n, 1) bit for bit.
+ *
+ *      gb25_particles_begin allocates room for `capacity` particles (two copies of the state -- a call writes the copy it does not
+ *      read, which is how a refused call moves nothing --, the sample array, the per-wave counter slots, the kbot table); the size
+ *      is checked against the free device memory BEFORE anything is allocated (GB25_ERR_OUT_OF_MEMORY leaves nothing allocated).
+ *      On a model that already has particles it starts over.  gb25_particles_set writes particles [first, first + count) from
+ *      host arrays as ACTIVE and makes first + count the number of particles (first <= the number so far: append, overwrite or
+ *      truncate); a cell outside the interior, a fraction outside [0, 1) and a dry cell are refused, naming the first offender.
+ *      gb25_particles_get: any of the seven arrays may be NULL.  gb25_particles_advance: ONE advance launch whatever the number
+ *      of particles, complete when the call returns.  gb25_particles_sample: the value of a (c,c,c) field (T, S, e, pHY, ...) in
+ *      each particle's cell as double -- a copy, hence exact; halo cells for OUTSIDE particles.  Every refused call names its
+ *      argument and touches nothing; before gb25_particles_begin everything but gb25_particles_get_info is GB25_ERR_STATE. */
+typedef enum {
+  GB25_PARTICLE_ACTIVE = 0, GB25_PARTICLE_AT_FOLD = 1, GB25_PARTICLE_OUTSIDE = 2, GB25_PARTICLE_NONFINITE = 3
+} gb25_particle_status;
+typedef enum {
+  GB25_PC_BLOCKED = 0, GB25_PC_CLAMPED_Y, GB25_PC_CLAMPED_Z, GB25_PC_AT_FOLD, GB25_PC_OUTSIDE, GB25_PC_NONFINITE, GB25_PC_TOO_FAR,
+  GB25_PC_RESERVED, GB25_PC_COUNT
+} gb25_particle_counter;
+/* count, capacity; the accepted advance calls, their substeps and the model time they covered; the counters of the last advance
+ * call (a too-far refusal included) and of all calls */
+typedef struct {
+  int64_t count, capacity, calls, substeps;
+  double time_advanced;
+  int64_t last[GB25_PC_COUNT], total[GB25_PC_COUNT];
+} gb25_particles_info;
+int32_t     gb25_particles_info_bytes(void);   /* sizeof the struct as THIS library was built */
+gb25_status gb25_particles_begin(gb25_model *m, int64_t capacity);
+gb25_status gb25_particles_set(gb25_model *m, int64_t first, int64_t count, const int32_t *i, const int32_t *j, const int32_t *k,
+                               const double *a, const double *b, const double *c);
+gb25_status gb25_particles_get(gb25_model *m, int64_t first, int64_t count, int32_t *i, int32_t *j, int32_t *k, double *a, double *b,
+                               double *c, int32_t *status);
+gb25_status gb25_particles_advance(gb25_model *m, double dt, int32_t substeps);
+gb25_status gb25_particles_sample(gb25_model *m, gb25_field f, double *out, int64_t count);
+gb25_status gb25_particles_get_info(const gb25_model *m, gb25_particles_info *info);
+gb25_status gb25_particles_end(gb25_model *m);
+
 /* ---- built-in per-kernel HIP-event timing (bench.py's roofline numbers) */
 gb25_status gb25_profile_enable(gb25_model *m, int on); /* 0: off, 1: every kernel, 2 + k: kernel k alone */
 gb25_status gb25_profile_reset(gb25_model *m);

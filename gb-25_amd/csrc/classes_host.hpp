@@ -1,6 +1,7 @@
 // classes_host.hpp -- host side of gb25_get_class_sums / gb25_class_sum_bytes (include/gb25.h); included by gb25_api.hip behind
-// diagnostics_host.hpp, whose helpers it uses.  Kernels: class_kernels.hpp.  Like the other diagnostics nothing here writes model
-// memory or a schedule flag: the only memory written is the records' own buffer.
+// diagnostics_host.hpp, whose shared helpers (diag_*) and tables (moments_tables) it uses.  Kernels: class_kernels.hpp; the memory:
+// class_sums of DiagState (diagnostics_state.hpp).  Like the other diagnostics nothing here writes model memory or a schedule
+// flag: the only memory written is the records' own buffer.
 #pragma once
 
 namespace {
@@ -11,19 +12,19 @@ static_assert(CLASS_MAX_BINS == GB25_CLASS_MAX_BINS, "the kernels' cap is the he
 // the edges (CLASS_MAX_BINS doubles), then ROWS [rows B], CUMULATIVE [rows (B + 1)] and TOTAL [B] for the tallest set of rows a
 // call can ask for (v below a wall: Ny + 1) and at least B bins
 gb25_status class_buffer(gb25_model* m, int B) {
-  if (m->diag_class && (size_t)B <= m->diag_class_bins) return GB25_OK;
-  if (m->diag_class) HIPCHK(hipFree(m->diag_class));
-  m->diag_class = nullptr;
+  if (m->diag.class_sums && (size_t)B <= m->diag.class_bins) return GB25_OK;
+  if (m->diag.class_sums) HIPCHK(hipFree(m->diag.class_sums));
+  m->diag.class_sums = nullptr;
   const size_t rows = (size_t)m->Ny + 1, records = rows * (2 * (size_t)B + 1) + (size_t)B;
-  HIPCHK(hipMalloc(&m->diag_class, CLASS_MAX_BINS * sizeof(double) + records * sizeof(ClassPartial)));
-  m->diag_class_rows = rows;
-  m->diag_class_bins = (size_t)B;
+  HIPCHK(hipMalloc(&m->diag.class_sums, CLASS_MAX_BINS * sizeof(double) + records * sizeof(ClassPartial)));
+  m->diag.class_rows = rows;
+  m->diag.class_bins = (size_t)B;
   return GB25_OK;
 }
-inline double* class_edges(gb25_model* m) { return (double*)m->diag_class; }
+inline double* class_edges(gb25_model* m) { return (double*)m->diag.class_sums; }
 inline ClassPartial* class_rows(gb25_model* m) { return (ClassPartial*)(class_edges(m) + CLASS_MAX_BINS); }
-inline ClassPartial* class_psi(gb25_model* m) { return class_rows(m) + m->diag_class_rows * m->diag_class_bins; }
-inline ClassPartial* class_total(gb25_model* m) { return class_psi(m) + m->diag_class_rows * (m->diag_class_bins + 1); }
+inline ClassPartial* class_psi(gb25_model* m) { return class_rows(m) + m->diag.class_rows * m->diag.class_bins; }
+inline ClassPartial* class_total(gb25_model* m) { return class_psi(m) + m->diag.class_rows * (m->diag.class_bins + 1); }
 
 struct ClassLaunch {
   const real *v, *T, *S;
@@ -72,33 +73,31 @@ gb25_status gb25_get_class_sums(gb25_model* m, gb25_class_what what, gb25_class_
   int32_t d[3];
   if (gb25_field_dims(m, faces ? GB25_V : GB25_T, 0, d)) return GB25_ERR_INVALID_ARGUMENT;
   const int N = d[1], along = d[0], B = n_edges + 1;
-  const long long n = i_count == -1 ? (long long)along - i_first : (long long)i_count;
-  if (i_first < 0 || i_first >= along || i_count < -1 || i_count == 0 || i_first + n > along)
-    return fail(m, GB25_ERR_INVALID_ARGUMENT, "gb25_get_class_sums: window i_first = %d, i_count = %d of %d columns (0-based local interior indices; i_count = -1: to the end)",
-                (int)i_first, (int)i_count, along);
+  int n = 0;
+  if (gb25_status s = diag_window(m, "gb25_get_class_sums", i_first, i_count, along, "columns (i_first, i_count)", &n)) return s;
   const int64_t want = shape == GB25_CL_ROWS ? (int64_t)N * B : shape == GB25_CL_ROWS_CUMULATIVE ? (int64_t)N * (B + 1) : (int64_t)B;
   if (count != want)
     return fail(m, GB25_ERR_INVALID_ARGUMENT, "gb25_get_class_sums: this shape has %lld records (rows %d, bins %d), count is %lld",
                 (long long)want, N, B, (long long)count);
-  if (gb25_status s = derived_need_device(m, "gb25_get_class_sums")) return s;
-  ClassLaunch a = {nullptr, nullptr, nullptr, (int)i_first, (int)n, N, B};
+  if (gb25_status s = diag_need_device(m, "gb25_get_class_sums")) return s;
+  ClassLaunch a = {nullptr, nullptr, nullptr, (int)i_first, n, N, B};
   if (faces)
     if (gb25_status s = diag_source(m, GB25_V, &a.v)) return s;
   if (gb25_status s = diag_source(m, GB25_T, &a.T)) return s;
   if (gb25_status s = diag_source(m, GB25_S, &a.S)) return s;
   if (gb25_status s = class_buffer(m, B)) return s;
-  if ((size_t)N > m->diag_class_rows) return fail(m, GB25_ERR_STATE, "gb25_get_class_sums: more rows than the model's buffer holds");
+  if ((size_t)N > m->diag.class_rows) return fail(m, GB25_ERR_STATE, "gb25_get_class_sums: more rows than the model's buffer holds");
   if (gb25_status s = diag_wait_for_model(m)) return s;
   if (gb25_status s = moments_tables(m)) return s;
   double padded[CLASS_MAX_BINS];   // (alive until the stream is synchronised below)
   for (int e = 0; e < CLASS_MAX_BINS; e++) padded[e] = e < n_edges ? edges[e] : HUGE_VAL;
   HIPCHK(hipMemcpyAsync(class_edges(m), padded, sizeof padded, hipMemcpyHostToDevice, m->stream));
   ClassTables tab;
-  tab.metric = faces ? m->diag_face_length[0] : m->diag_area[0];
-  tab.first = m->diag_first_wet[faces ? 2 : 0];
-  tab.eos0 = m->diag_eos0;
+  tab.metric = faces ? m->diag.face_length[0] : m->diag.area[0];
+  tab.first = m->diag.first_wet[faces ? 2 : 0];
+  tab.eos0 = m->diag.eos0;
   tab.edges = class_edges(m);
-  tab.pivot_row = (!faces && m->cfg.grid_type >= GB25_GRID_TRIPOLAR && !m->yn_open) ? m->Ny - 1 : -1;
+  tab.pivot_row = (!faces && is_folded(m)) ? m->Ny - 1 : -1;
   {
     Timed t(m, GB25_K_DIAGNOSTICS);
     if (faces) {
@@ -117,9 +116,7 @@ gb25_status gb25_get_class_sums(gb25_model* m, gb25_class_what what, gb25_class_
     }
   }
   const ClassPartial* from = shape == GB25_CL_ROWS ? class_rows(m) : shape == GB25_CL_ROWS_CUMULATIVE ? class_psi(m) : class_total(m);
-  HIPCHK(hipMemcpyAsync(out, from, (size_t)count * sizeof(gb25_class_sum), hipMemcpyDeviceToHost, m->stream));
-  HIPCHK(hipStreamSynchronize(m->stream));
-  return GB25_OK;
+  return diag_download(m, out, from, (size_t)count * sizeof(gb25_class_sum));
 }
 
 }  // extern "C"

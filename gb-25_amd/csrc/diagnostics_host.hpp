@@ -1,10 +1,67 @@
 // diagnostics_host.hpp -- host side of gb25_get_field_stats / gb25_compare_field / gb25_get_state_monitor /
 // gb25_field_device_ptr_readonly / gb25_integrate_field / gb25_get_budget / gb25_compute_derived / gb25_get_derived /
 // gb25_get_derived_stats / gb25_get_field_levels / gb25_get_transport (include/gb25.h); the last part of gb25_api.hip, which includes it.  Kernels:
-// diagnostics_kernels.hpp.  Nothing here writes model memory or a schedule flag: the calls may sit between any two steps.
+// diagnostics_kernels.hpp; the memory: DiagState (diagnostics_state.hpp), m->diag.  Nothing here writes model memory or a schedule
+// flag: the calls may sit between any two steps.  The first section holds what every diagnostic shares, averages_host.hpp,
+// classes_host.hpp and particles_host.hpp included: diag_need_device, diag_window, diag_download, diag_upload, diag_room_for /
+// diag_alloc_zeroed, diag_wait_for_model, diag_source (is_folded, has_north_wall and first_wet_level: gb25_api.hip, beside is_2d).
 #pragma once
 
 namespace {
+
+// ---- shared by every diagnostic
+gb25_status diag_need_device(gb25_model* m, const char* what) {
+  if (!m->own_stream) return fail(m, GB25_ERR_NO_DEVICE, "%s: this model has no device (gb25_create failed); libgb25hip has no CPU fallback", what);
+  return GB25_OK;
+}
+// the window [first, first + count) of 0-based local interior indices of an extent; count = -1: all from first on.  noun: what
+// the extent counts and what the caller names the two arguments
+gb25_status diag_window(gb25_model* m, const char* what, int32_t first, int32_t count, int extent, const char* noun, int* n) {
+  const long long c = count == -1 ? (long long)extent - first : (long long)count;
+  if (first < 0 || first >= extent || count < -1 || count == 0 || first + c > extent)
+    return fail(m, GB25_ERR_INVALID_ARGUMENT, "%s: window first = %d, count = %d of %d %s; 0-based local interior indices, count = -1: to the end",
+                what, (int)first, (int)count, extent, noun);
+  *n = (int)c;
+  return GB25_OK;
+}
+// the tail of most entry points: the result to the host behind the launches, then the stream is quiet
+gb25_status diag_download(gb25_model* m, void* host, const void* dev, size_t bytes) {
+  HIPCHK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, m->stream));
+  HIPCHK(hipStreamSynchronize(m->stream));
+  return GB25_OK;
+}
+// one of diagnostics' own tables: the values of h as T in a new allocation (*dst holds nothing: DiagState::release_tables)
+template <class T, class S>
+gb25_status diag_upload(gb25_model* m, const std::vector<S>& h, T** dst) {
+  std::vector<T> a(h.size());
+  for (size_t o = 0; o < h.size(); o++) a[o] = (T)h[o];
+  HIPCHK(hipMalloc(dst, a.size() * sizeof(T)));
+  HIPCHK(hipMemcpy(*dst, a.data(), a.size() * sizeof(T), hipMemcpyHostToDevice));
+  return GB25_OK;
+}
+// An allocation that grows with what the caller asks for (gb25_averages_begin, gb25_particles_begin) is refused BEFORE hipMalloc
+// when the device has fewer bytes free: nothing is allocated, nothing is evicted.  of: what the bytes are for.
+gb25_status diag_room_for(gb25_model* m, const char* what, const char* of, double need) {
+  size_t free_bytes = 0, device_bytes = 0;
+  HIPCHK(hipMemGetInfo(&free_bytes, &device_bytes));
+  if (need > (double)free_bytes) return fail(m, GB25_ERR_OUT_OF_MEMORY, "%s: %s need %.0f bytes, the device has %zu free", what, of, need, free_bytes);
+  return GB25_OK;
+}
+// ... and then made and zeroed; a failure leaves nothing allocated
+gb25_status diag_alloc_zeroed(gb25_model* m, const char* what, const char* of, size_t bytes, void** base) {
+  const hipError_t e = hipMalloc(base, bytes);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    *base = nullptr;
+    return fail(m, GB25_ERR_OUT_OF_MEMORY, "%s: hipMalloc of %zu bytes for %s failed: %s", what, bytes, of, hipGetErrorString(e));
+  }
+  if (hipMemsetAsync(*base, 0, bytes, m->stream) != hipSuccess || hipStreamSynchronize(m->stream) != hipSuccess) {
+    (void)hipFree(*base);
+    *base = nullptr;
+    return fail(m, GB25_ERR_HIP, "%s: zeroing %s failed: %s", what, of, hipGetErrorString(hipGetLastError()));
+  }
+  return GB25_OK;
+}
 
 constexpr size_t DIAG_RECORD = 64;   // bytes of a slot of the scratch buffer: the largest per-block record
 constexpr int DIAG_RESULTS = 8;      // result slots behind the per-block records (a state monitor fills seven)
@@ -14,15 +71,15 @@ inline long long diag_blocks(const DiagBox& b) { return ((long long)b.by * b.bz 
 
 // once per model: per-block records for the tallest box a field of this model has (w's parent), plus the result slots
 gb25_status diag_scratch(gb25_model* m) {
-  if (m->diag_scratch) return GB25_OK;
+  if (m->diag.scratch) return GB25_OK;
   const int H = m->cfg.halo;
   const long long rows = (long long)(m->Ny + 2 * H + 1) * (m->cfg.Nz + 2 * H + 1);
   const size_t records = (size_t)((rows + DIAG_ROWS - 1) / DIAG_ROWS);
-  HIPCHK(hipMalloc(&m->diag_scratch, (records + DIAG_RESULTS) * DIAG_RECORD));
-  m->diag_scratch_records = records;
+  HIPCHK(hipMalloc(&m->diag.scratch, (records + DIAG_RESULTS) * DIAG_RECORD));
+  m->diag.scratch_records = records;
   return GB25_OK;
 }
-inline void* diag_result_slot(gb25_model* m, int q) { return (char*)m->diag_scratch + (m->diag_scratch_records + q) * DIAG_RECORD; }
+inline void* diag_result_slot(gb25_model* m, int q) { return (char*)m->diag.scratch + (m->diag.scratch_records + q) * DIAG_RECORD; }
 
 // the whole model is quiet (what gb25_synchronize waits for)
 gb25_status diag_wait_for_model(gb25_model* m) {
@@ -84,14 +141,14 @@ void diag_position(long long at, const DiagBox& b, int32_t pos[3]) {
 
 template <class P>
 gb25_status diag_finish(gb25_model* m, long long nblocks, int slot) {
-  hipLaunchKernelGGL(k_diag_finish<P>, dim3(1), dim3(DIAG_THREADS), 0, m->stream, (const P*)m->diag_scratch, (int)nblocks,
+  hipLaunchKernelGGL(k_diag_finish<P>, dim3(1), dim3(DIAG_THREADS), 0, m->stream, (const P*)m->diag.scratch, (int)nblocks,
                      (P*)diag_result_slot(m, slot));
   LAUNCHCHK();
   return GB25_OK;
 }
 gb25_status diag_launch_stats(gb25_model* m, const real* src, const DiagBox& b, int slot) {
   const long long nb = diag_blocks(b);
-  hipLaunchKernelGGL(k_field_stats<real>, dim3((unsigned)nb), dim3(DIAG_THREADS), 0, m->stream, src, b, (StatsPartial*)m->diag_scratch);
+  hipLaunchKernelGGL(k_field_stats<real>, dim3((unsigned)nb), dim3(DIAG_THREADS), 0, m->stream, src, b, (StatsPartial*)m->diag.scratch);
   LAUNCHCHK();
   return diag_finish<StatsPartial>(m, nb, slot);
 }
@@ -108,7 +165,19 @@ void diag_fill_stats(const gb25_model* m, gb25_field id, const StatsPartial& p, 
 }
 gb25_status diag_check_box(gb25_model* m, const DiagBox& b) {
   if (b.bx <= 0 || b.by <= 0 || b.bz <= 0) return fail(m, GB25_ERR_INVALID_ARGUMENT, "the field has an empty box");
-  if ((size_t)diag_blocks(b) > m->diag_scratch_records) return fail(m, GB25_ERR_STATE, "diagnostics: the box needs more per-block records than the model's scratch buffer holds");
+  if ((size_t)diag_blocks(b) > m->diag.scratch_records) return fail(m, GB25_ERR_STATE, "diagnostics: the box needs more per-block records than the model's scratch buffer holds");
+  return GB25_OK;
+}
+
+// launch, finish, download and fill: the statistics of the box b of src (gb25_get_field_stats, gb25_get_derived_stats)
+gb25_status diag_stats_of(gb25_model* m, gb25_field id, const real* src, const DiagBox& b, int include_halos, gb25_field_stats* out) {
+  {
+    Timed t(m, GB25_K_DIAGNOSTICS);
+    if (gb25_status s = diag_launch_stats(m, src, b, 0)) return s;
+  }
+  StatsPartial p;
+  if (gb25_status s = diag_download(m, &p, diag_result_slot(m, 0), sizeof p)) return s;
+  diag_fill_stats(m, id, p, b, include_halos, out);
   return GB25_OK;
 }
 
@@ -129,68 +198,29 @@ MomentLoc moments_loc(int id) {
 // areas by location as `real` (what gb25_get_metric2 returns, rounded back: exact) and the first wet level per column and
 // location, from the host's tables; parent layout of a (c,f) field
 gb25_status moments_tables(gb25_model* m) {
-  if (m->diag_tables_valid) return GB25_OK;
+  if (m->diag.tables_valid) return GB25_OK;
   const int Nx = m->Nx, Ny = m->Ny, Nz = m->cfg.Nz, H = m->cfg.halo, sx = Nx + 2 * H, sy = Ny + 2 * H + 1;
   const size_t n2 = (size_t)sx * sy;
-  for (int q = 0; q < 3; q++) {
-    if (m->diag_area[q]) HIPCHK(hipFree(m->diag_area[q]));
-    if (m->diag_first_wet[q]) HIPCHK(hipFree(m->diag_first_wet[q]));
-    m->diag_area[q] = nullptr;
-    m->diag_first_wet[q] = nullptr;
-  }
-  if (m->diag_azff) HIPCHK(hipFree(m->diag_azff));
-  if (m->diag_zt) HIPCHK(hipFree(m->diag_zt));
-  m->diag_azff = nullptr;
-  m->diag_zt = nullptr;
-  for (int q = 0; q < 2; q++) {
-    if (m->diag_face_length[q]) HIPCHK(hipFree(m->diag_face_length[q]));
-    m->diag_face_length[q] = nullptr;
-  }
-  {
-    // the derived fields' own: (double) of zc[0 .. Nz) | zf[0 .. Nz] as gb25_get_metric returns them, AZFF of a curvilinear grid
-    std::vector<double> zt((size_t)2 * Nz + 1);
-    for (int k = 0; k < Nz; k++) zt[k] = (double)(real)m->h_metric[GB25_M_ZC][m->metric_off_k + k];
-    for (int k = 0; k <= Nz; k++) zt[Nz + k] = (double)(real)m->h_metric[GB25_M_ZF][m->metric_off_k + k];
-    HIPCHK(hipMalloc(&m->diag_zt, zt.size() * sizeof(double)));
-    HIPCHK(hipMemcpy(m->diag_zt, zt.data(), zt.size() * sizeof(double), hipMemcpyHostToDevice));
-    if (m->g.cv.on) {
-      const std::vector<double>& h = m->h_curv[GB25_M2_AZFF];
-      if (h.size() != n2) return fail(m, GB25_ERR_STATE, "derived fields: the curvilinear metrics are not built");
-      std::vector<real> a(n2);
-      for (size_t o = 0; o < n2; o++) a[o] = (real)h[o];
-      HIPCHK(hipMalloc(&m->diag_azff, n2 * sizeof(real)));
-      HIPCHK(hipMemcpy(m->diag_azff, a.data(), n2 * sizeof(real), hipMemcpyHostToDevice));
-    }
-  }
+  DiagState& D = m->diag;
+  D.release_tables();
+  // the derived fields' own: (double) of zc[0 .. Nz) | zf[0 .. Nz] as gb25_get_metric returns them
+  std::vector<double> zt((size_t)2 * Nz + 1);
+  for (int k = 0; k < Nz; k++) zt[k] = (double)(real)m->h_metric[GB25_M_ZC][m->metric_off_k + k];
+  for (int k = 0; k <= Nz; k++) zt[Nz + k] = (double)(real)m->h_metric[GB25_M_ZF][m->metric_off_k + k];
+  if (gb25_status s = diag_upload(m, zt, &D.zt)) return s;
   if (m->g.cv.on) {
-    static const int ids[3] = {GB25_M2_AZCC, GB25_M2_AZFC, GB25_M2_AZCF};
-    std::vector<real> a(n2);
-    for (int q = 0; q < 3; q++) {
-      const std::vector<double>& h = m->h_curv[ids[q]];
-      if (h.size() != n2) return fail(m, GB25_ERR_STATE, "integrals: the curvilinear metrics are not built");
-      for (size_t o = 0; o < n2; o++) a[o] = (real)h[o];
-      HIPCHK(hipMalloc(&m->diag_area[q], n2 * sizeof(real)));
-      HIPCHK(hipMemcpy(m->diag_area[q], a.data(), n2 * sizeof(real), hipMemcpyHostToDevice));
-    }
-  }
-  if (m->g.cv.on) {
-    // the transports' own: the lengths of the y faces (DXCF) and of the x faces (DYFC)
-    static const int ids[2] = {GB25_M2_DXCF, GB25_M2_DYFC};
-    std::vector<real> a(n2);
-    for (int q = 0; q < 2; q++) {
-      const std::vector<double>& h = m->h_curv[ids[q]];
-      if (h.size() != n2) return fail(m, GB25_ERR_STATE, "transports: the curvilinear metrics are not built");
-      for (size_t o = 0; o < n2; o++) a[o] = (real)h[o];
-      HIPCHK(hipMalloc(&m->diag_face_length[q], n2 * sizeof(real)));
-      HIPCHK(hipMemcpy(m->diag_face_length[q], a.data(), n2 * sizeof(real), hipMemcpyHostToDevice));
+    // of a curvilinear grid: the derived fields' AZFF, the integrals' areas by location, the transports' lengths of the y faces
+    // (DXCF) and of the x faces (DYFC)
+    const struct { int id; const char* name; real** dst; } metrics[] = {
+        {GB25_M2_AZFF, "AZFF", &D.azff},    {GB25_M2_AZCC, "AZCC", &D.area[0]},        {GB25_M2_AZFC, "AZFC", &D.area[1]},
+        {GB25_M2_AZCF, "AZCF", &D.area[2]}, {GB25_M2_DXCF, "DXCF", &D.face_length[0]}, {GB25_M2_DYFC, "DYFC", &D.face_length[1]}};
+    for (const auto& c : metrics) {
+      if (m->h_curv[c.id].size() != n2) return fail(m, GB25_ERR_STATE, "diagnostics: the curvilinear metric %s is not built", c.name);
+      if (gb25_status s = diag_upload(m, m->h_curv[c.id], c.dst)) return s;
     }
   }
   if (!m->kbot.empty()) {
-    const int E = m->kb_E, ksx = Nx + 2 * E;
-    auto kb = [&](int ii, int jj) {   // (gb25_get_bottom_info's: clamped at the walls, a neighbour's row otherwise)
-      const int jl = std::min(std::max(jj + m->j0, 0), m->cfg.Ny - 1) - m->j0;
-      return m->kbot[(size_t)(ii + E) + (size_t)ksx * (std::min(std::max(jl, -m->kb_Ey), Ny + m->kb_Ey - 1) + m->kb_Ey)];
-    };
+    auto kb = [&](int ii, int jj) { return first_wet_level(m, ii, jj); };
     std::vector<unsigned short> f(n2);
     for (int q = 0; q < 3; q++) {
       std::fill(f.begin(), f.end(), MOMENTS_DRY);
@@ -201,34 +231,33 @@ gb25_status moments_tables(gb25_model* m) {
           f[(size_t)(i + H) + (size_t)sx * (j + H)] = k < Nz ? (unsigned short)k : MOMENTS_DRY;
         }
       }
-      HIPCHK(hipMalloc(&m->diag_first_wet[q], n2 * sizeof(unsigned short)));
-      HIPCHK(hipMemcpy(m->diag_first_wet[q], f.data(), n2 * sizeof(unsigned short), hipMemcpyHostToDevice));
+      if (gb25_status s = diag_upload(m, f, &D.first_wet[q])) return s;
     }
   }
-  m->diag_tables_valid = true;
+  D.tables_valid = true;
   return GB25_OK;
 }
 
 // once per model: MOMENTS_SLOTS sets of row records for the tallest interior a field of this model has, their level records,
 // their totals
 gb25_status moments_buffer(gb25_model* m) {
-  if (m->diag_moments) return GB25_OK;
+  if (m->diag.moments) return GB25_OK;
   const size_t levels = (size_t)m->cfg.Nz + 1, rows = (size_t)(m->Ny + 1) * levels;
-  HIPCHK(hipMalloc(&m->diag_moments, (size_t)MOMENTS_SLOTS * (rows + levels + 1) * sizeof(MomentsPartial)));
-  m->diag_moments_rows = rows;
-  m->diag_moments_levels = levels;
+  HIPCHK(hipMalloc(&m->diag.moments, (size_t)MOMENTS_SLOTS * (rows + levels + 1) * sizeof(MomentsPartial)));
+  m->diag.moments_rows = rows;
+  m->diag.moments_levels = levels;
   return GB25_OK;
 }
-inline MomentsPartial* moments_rows(gb25_model* m, int slot) { return (MomentsPartial*)m->diag_moments + m->diag_moments_rows * slot; }
+inline MomentsPartial* moments_rows(gb25_model* m, int slot) { return (MomentsPartial*)m->diag.moments + m->diag.moments_rows * slot; }
 inline MomentsPartial* moments_levels(gb25_model* m, int slot) {
-  return (MomentsPartial*)m->diag_moments + m->diag_moments_rows * MOMENTS_SLOTS + m->diag_moments_levels * slot;
+  return (MomentsPartial*)m->diag.moments + m->diag.moments_rows * MOMENTS_SLOTS + m->diag.moments_levels * slot;
 }
 inline MomentsPartial* moments_totals(gb25_model* m) {
-  return (MomentsPartial*)m->diag_moments + (m->diag_moments_rows + m->diag_moments_levels) * MOMENTS_SLOTS;
+  return (MomentsPartial*)m->diag.moments + (m->diag.moments_rows + m->diag.moments_levels) * MOMENTS_SLOTS;
 }
 gb25_status moments_check_box(gb25_model* m, const DiagBox& b) {
   if (b.bx <= 0 || b.by <= 0 || b.bz <= 0) return fail(m, GB25_ERR_INVALID_ARGUMENT, "the field has an empty box");
-  if ((size_t)b.by * b.bz > m->diag_moments_rows || (size_t)b.bz > m->diag_moments_levels)
+  if ((size_t)b.by * b.bz > m->diag.moments_rows || (size_t)b.bz > m->diag.moments_levels)
     return fail(m, GB25_ERR_STATE, "integrals: the box needs more row records than the model's buffer holds");
   return GB25_OK;
 }
@@ -242,10 +271,10 @@ void moments_launch_loc(gb25_model* m, const MomentsTables& tab, const real* src
 gb25_status moments_launch(gb25_model* m, gb25_field id, const real* src, const DiagBox& b, int slot) {
   MomentsTables tab;
   for (int q = 0; q < 3; q++) {
-    tab.area[q] = m->diag_area[q];
-    tab.first[q] = m->diag_first_wet[q];
+    tab.area[q] = m->diag.area[q];
+    tab.first[q] = m->diag.first_wet[q];
   }
-  tab.pivot_row = (m->cfg.grid_type >= GB25_GRID_TRIPOLAR && !m->yn_open) ? m->Ny - 1 : -1;
+  tab.pivot_row = is_folded(m) ? m->Ny - 1 : -1;
   MomentsPartial* rows = moments_rows(m, slot);
   switch (moments_loc(id)) {
     case LOC_CCC: moments_launch_loc<LOC_CCC>(m, tab, src, b, rows); break;
@@ -269,10 +298,10 @@ gb25_status moments_fold(gb25_model* m, const DiagBox* b, int n) {
     most = std::max(most, b[s].bz);
   }
   hipLaunchKernelGGL(k_moments_fold, dim3(most, n), dim3(64), 0, m->stream, (const MomentsPartial*)moments_rows(m, 0),
-                     (long long)m->diag_moments_rows, f, moments_levels(m, 0), (long long)m->diag_moments_levels);
+                     (long long)m->diag.moments_rows, f, moments_levels(m, 0), (long long)m->diag.moments_levels);
   LAUNCHCHK();
   hipLaunchKernelGGL(k_moments_fold, dim3(1, n), dim3(64), 0, m->stream, (const MomentsPartial*)moments_levels(m, 0),
-                     (long long)m->diag_moments_levels, t, moments_totals(m), 1LL);
+                     (long long)m->diag.moments_levels, t, moments_totals(m), 1LL);
   LAUNCHCHK();
   return GB25_OK;
 }
@@ -282,19 +311,9 @@ gb25_status moments_fold(gb25_model* m, const DiagBox* b, int n) {
 // interior extents of a derived field, from the configuration alone (no device): zeta has the rows of v -- one more than the
 // cells below a wall, as many on a folded grid and below a northern neighbour rank
 void derived_extents(const gb25_model* m, gb25_derived q, int32_t d[3]) {
-  const bool no_wall = m->cfg.grid_type >= GB25_GRID_TRIPOLAR || m->yn_open;
   d[0] = m->Nx;
-  d[1] = m->Ny + ((q == GB25_D_VORTICITY && !no_wall) ? 1 : 0);
+  d[1] = m->Ny + ((q == GB25_D_VORTICITY && has_north_wall(m)) ? 1 : 0);
   d[2] = q == GB25_D_MIXED_LAYER_DEPTH ? 1 : m->cfg.Nz;
-}
-// interior levels [k_first, k_first + k_count) of nz; k_count = -1: all from k_first on
-gb25_status derived_levels(gb25_model* m, const char* what, int nz, int32_t k_first, int32_t k_count, int* kc) {
-  const long long n = k_count == -1 ? (long long)nz - k_first : (long long)k_count;
-  if (k_first < 0 || k_first >= nz || k_count < -1 || k_count == 0 || k_first + n > nz)
-    return fail(m, GB25_ERR_INVALID_ARGUMENT, "%s: levels k_first = %d, k_count = %d of a result with %d level%s (0-based interior levels; k_count = -1: all)",
-                what, (int)k_first, (int)k_count, nz, nz == 1 ? "" : "s");
-  *kc = (int)n;
-  return GB25_OK;
 }
 gb25_status derived_check(gb25_model* m, const char* what, gb25_derived q, double param) {
   if (q < 0 || q >= GB25_D_COUNT) return fail(m, GB25_ERR_INVALID_ARGUMENT, "%s: no derived field %d (0 .. %d)", what, (int)q, GB25_D_COUNT - 1);
@@ -302,17 +321,13 @@ gb25_status derived_check(gb25_model* m, const char* what, gb25_derived q, doubl
     return fail(m, GB25_ERR_INVALID_ARGUMENT, "%s: the mixed-layer depth needs a density threshold > 0 kg/m^3 as param, got %g", what, param);
   return GB25_OK;
 }
-gb25_status derived_need_device(gb25_model* m, const char* what) {
-  if (!m->own_stream) return fail(m, GB25_ERR_NO_DEVICE, "%s: this model has no device (gb25_create failed); libgb25hip has no CPU fallback", what);
-  return GB25_OK;
-}
 // once per model: one 2-D plane, then room for the largest interior a field has (w: Nz + 1 levels; v: Ny + 1 rows)
 gb25_status derived_scratch(gb25_model* m) {
-  if (m->diag_derived) return GB25_OK;
+  if (m->diag.derived) return GB25_OK;
   const size_t plane = (size_t)m->Nx * (m->Ny + 1);
-  m->diag_derived_plane = (plane + 3) & ~(size_t)3;   // (the 3-D part starts on a 16-byte boundary)
-  m->diag_derived_elems = m->diag_derived_plane + plane * ((size_t)m->cfg.Nz + 1);
-  HIPCHK(hipMalloc(&m->diag_derived, m->diag_derived_elems * sizeof(real)));
+  m->diag.derived_plane = (plane + 3) & ~(size_t)3;   // (the 3-D part starts on a 16-byte boundary)
+  m->diag.derived_elems = m->diag.derived_plane + plane * ((size_t)m->cfg.Nz + 1);
+  HIPCHK(hipMalloc(&m->diag.derived, m->diag.derived_elems * sizeof(real)));
   return GB25_OK;
 }
 inline dim3 derived_grid(int bx, int by, int kc) { return dim3((bx + 63) / 64, (by + 3) / 4, (kc + DER_LEVELS - 1) / DER_LEVELS); }
@@ -333,34 +348,48 @@ gb25_status derived_run(gb25_model* m, gb25_derived q, double param, int k0, int
   Timed t(m, GB25_K_DIAGNOSTICS);
   if (q == GB25_D_MIXED_LAYER_DEPTH) {
     // sigma of every level into the 3-D part (the very values gb25_get_derived(GB25_D_POTENTIAL_DENSITY) hands out), then the march
-    real* sigma = m->diag_derived + m->diag_derived_plane;
+    real* sigma = m->diag.derived + m->diag.derived_plane;
     const DerivedOut d{sigma, e[0], e[1], 0, g.Nz};
-    hipLaunchKernelGGL(k_derived_density<true>, derived_grid(e[0], e[1], g.Nz), blk, 0, m->stream, g, a, b, m->diag_eos0, m->diag_first_wet[0], d);
+    hipLaunchKernelGGL(k_derived_density<true>, derived_grid(e[0], e[1], g.Nz), blk, 0, m->stream, g, a, b, m->diag.eos0, m->diag.first_wet[0], d);
     LAUNCHCHK();
     hipLaunchKernelGGL(k_derived_mixed_layer, dim3((e[0] + 63) / 64, (e[1] + 3) / 4), blk, 0, m->stream, g, (const real*)sigma,
-                       m->diag_first_wet[0], (const double*)m->diag_zt, param, m->diag_derived, e[0], e[1]);
+                       m->diag.first_wet[0], (const double*)m->diag.zt, param, m->diag.derived, e[0], e[1]);
     LAUNCHCHK();
-    *result = m->diag_derived;
+    *result = m->diag.derived;
     return GB25_OK;
   }
-  real* out = m->diag_derived + m->diag_derived_plane;
+  real* out = m->diag.derived + m->diag.derived_plane;
   const DerivedOut d{out, e[0], e[1], k0, kc};
   const dim3 grd = derived_grid(e[0], e[1], kc);
   switch (q) {
     case GB25_D_VORTICITY:
-      if (g.cv.on) hipLaunchKernelGGL(k_derived_vorticity<true>, grd, blk, 0, m->stream, g, a, b, (const real*)m->diag_azff, d);
+      if (g.cv.on) hipLaunchKernelGGL(k_derived_vorticity<true>, grd, blk, 0, m->stream, g, a, b, (const real*)m->diag.azff, d);
       else hipLaunchKernelGGL(k_derived_vorticity<false>, grd, blk, 0, m->stream, g, a, b, (const real*)nullptr, d);
       break;
     case GB25_D_KINETIC_ENERGY: hipLaunchKernelGGL(k_derived_kinetic_energy, grd, blk, 0, m->stream, g, a, b, d); break;
     case GB25_D_DENSITY_ANOMALY:
-      hipLaunchKernelGGL(k_derived_density<false>, grd, blk, 0, m->stream, g, a, b, m->diag_eos0, m->diag_first_wet[0], d);
+      hipLaunchKernelGGL(k_derived_density<false>, grd, blk, 0, m->stream, g, a, b, m->diag.eos0, m->diag.first_wet[0], d);
       break;
     default:
-      hipLaunchKernelGGL(k_derived_density<true>, grd, blk, 0, m->stream, g, a, b, m->diag_eos0, m->diag_first_wet[0], d);
+      hipLaunchKernelGGL(k_derived_density<true>, grd, blk, 0, m->stream, g, a, b, m->diag.eos0, m->diag.first_wet[0], d);
       break;
   }
   LAUNCHCHK();
   *result = out;
+  return GB25_OK;
+}
+
+// What gb25_compute_derived and gb25_get_derived share: the checks, the window of levels, the launches.  e: the packed dims of
+// the result (e[2]: the levels of the window).
+gb25_status derived_window_run(gb25_model* m, const char* what, gb25_derived q, double param, int32_t k_first, int32_t k_count, int32_t e[3],
+                               const real** result) {
+  if (gb25_status s = derived_check(m, what, q, param)) return s;
+  int kc = 0;
+  derived_extents(m, q, e);
+  if (gb25_status s = diag_window(m, what, k_first, k_count, e[2], "levels (k_first, k_count)", &kc)) return s;
+  if (gb25_status s = diag_need_device(m, what)) return s;
+  if (gb25_status s = derived_run(m, q, param, k_first, kc, result)) return s;
+  e[2] = kc;
   return GB25_OK;
 }
 
@@ -370,15 +399,15 @@ static_assert(sizeof(TransportPartial) == sizeof(gb25_transport), "a line record
 // once per model: LINES [N Nz], the running sums [N (Nz + 1)] and PROFILE [N] for the longest set of lines a call can ask for
 // (N = by of v for the y faces, Nx for the x faces); the three parts start at multiples of that longest N
 gb25_status transport_buffer(gb25_model* m) {
-  if (m->diag_transport) return GB25_OK;
+  if (m->diag.transport) return GB25_OK;
   const size_t lines = (size_t)std::max(m->Nx, m->Ny + 1);
-  HIPCHK(hipMalloc(&m->diag_transport, lines * (2 * (size_t)m->cfg.Nz + 2) * sizeof(TransportPartial)));
-  m->diag_transport_lines = lines;
+  HIPCHK(hipMalloc(&m->diag.transport, lines * (2 * (size_t)m->cfg.Nz + 2) * sizeof(TransportPartial)));
+  m->diag.transport_lines = lines;
   return GB25_OK;
 }
-inline TransportPartial* transport_lines(gb25_model* m) { return (TransportPartial*)m->diag_transport; }
-inline TransportPartial* transport_psi(gb25_model* m) { return transport_lines(m) + m->diag_transport_lines * m->cfg.Nz; }
-inline TransportPartial* transport_profile(gb25_model* m) { return transport_psi(m) + m->diag_transport_lines * (m->cfg.Nz + 1); }
+inline TransportPartial* transport_lines(gb25_model* m) { return (TransportPartial*)m->diag.transport; }
+inline TransportPartial* transport_psi(gb25_model* m) { return transport_lines(m) + m->diag.transport_lines * m->cfg.Nz; }
+inline TransportPartial* transport_profile(gb25_model* m) { return transport_psi(m) + m->diag.transport_lines * (m->cfg.Nz + 1); }
 
 }  // namespace
 
@@ -397,39 +426,39 @@ gb25_status gb25_get_transport(gb25_model* m, gb25_transport_faces faces, gb25_t
   int32_t d[3];
   if (gb25_field_dims(m, ay ? GB25_V : GB25_U, 0, d)) return GB25_ERR_INVALID_ARGUMENT;
   const int Nz = d[2], N = ay ? d[1] : d[0], along = ay ? d[0] : d[1];   // lines; the extent of the summed index
-  const long long n = along_count == -1 ? (long long)along - along_first : (long long)along_count;
-  if (along_first < 0 || along_first >= along || along_count < -1 || along_count == 0 || along_first + n > along)
-    return fail(m, GB25_ERR_INVALID_ARGUMENT, "gb25_get_transport: window along_first = %d, along_count = %d of %d %s (0-based local interior indices; along_count = -1: to the end)",
-                (int)along_first, (int)along_count, along, ay ? "columns" : "rows");
+  int n = 0;
+  if (gb25_status s = diag_window(m, "gb25_get_transport", along_first, along_count, along,
+                                  ay ? "columns (along_first, along_count)" : "rows (along_first, along_count)", &n))
+    return s;
   const int64_t want = shape == GB25_TR_LINES ? (int64_t)N * Nz : shape == GB25_TR_PROFILE ? (int64_t)N : (int64_t)N * (Nz + 1);
   if (count != want)
     return fail(m, GB25_ERR_INVALID_ARGUMENT, "gb25_get_transport: this shape has %lld records (lines %d, levels %d), count is %lld",
                 (long long)want, N, Nz, (long long)count);
-  if (gb25_status s = derived_need_device(m, "gb25_get_transport")) return s;
+  if (gb25_status s = diag_need_device(m, "gb25_get_transport")) return s;
   const real *vel = nullptr, *T = nullptr, *S = nullptr;
   if (gb25_status s = diag_source(m, ay ? GB25_V : GB25_U, &vel)) return s;
   if (gb25_status s = diag_source(m, GB25_T, &T)) return s;
   if (gb25_status s = diag_source(m, GB25_S, &S)) return s;
   if (gb25_status s = transport_buffer(m)) return s;
-  if ((size_t)N > m->diag_transport_lines) return fail(m, GB25_ERR_STATE, "gb25_get_transport: more lines than the model's buffer holds");
+  if ((size_t)N > m->diag.transport_lines) return fail(m, GB25_ERR_STATE, "gb25_get_transport: more lines than the model's buffer holds");
   if (gb25_status s = diag_wait_for_model(m)) return s;
   if (gb25_status s = moments_tables(m)) return s;
   const Grid& g = m->g;
   TransportTables tab;
-  tab.length = m->diag_face_length[ay ? 0 : 1];
-  tab.first = m->diag_first_wet[ay ? 2 : 1];
-  tab.pivot_row = (!ay && m->cfg.grid_type >= GB25_GRID_TRIPOLAR && !m->yn_open) ? m->Ny - 1 : -1;
+  tab.length = m->diag.face_length[ay ? 0 : 1];
+  tab.first = m->diag.first_wet[ay ? 2 : 1];
+  tab.pivot_row = (!ay && is_folded(m)) ? m->Ny - 1 : -1;
   TransportPartial* lines = transport_lines(m);
   {
     Timed t(m, GB25_K_DIAGNOSTICS);
     if (ay) {
       const long long nb = ((long long)N * Nz + DIAG_THREADS / 64 - 1) / (DIAG_THREADS / 64);
-      if (g.cv.on) hipLaunchKernelGGL(k_transport_rows<true>, dim3((unsigned)nb), dim3(DIAG_THREADS), 0, m->stream, g, tab, vel, T, S, (int)along_first, (int)n, N, lines);
-      else hipLaunchKernelGGL(k_transport_rows<false>, dim3((unsigned)nb), dim3(DIAG_THREADS), 0, m->stream, g, tab, vel, T, S, (int)along_first, (int)n, N, lines);
+      if (g.cv.on) hipLaunchKernelGGL(k_transport_rows<true>, dim3((unsigned)nb), dim3(DIAG_THREADS), 0, m->stream, g, tab, vel, T, S, (int)along_first, n, N, lines);
+      else hipLaunchKernelGGL(k_transport_rows<false>, dim3((unsigned)nb), dim3(DIAG_THREADS), 0, m->stream, g, tab, vel, T, S, (int)along_first, n, N, lines);
     } else {
       const dim3 grd((N + 63) / 64, (Nz + 3) / 4), blk(64, 4);
-      if (g.cv.on) hipLaunchKernelGGL(k_transport_columns<true>, grd, blk, 0, m->stream, g, tab, vel, T, S, (int)along_first, (int)n, lines);
-      else hipLaunchKernelGGL(k_transport_columns<false>, grd, blk, 0, m->stream, g, tab, vel, T, S, (int)along_first, (int)n, lines);
+      if (g.cv.on) hipLaunchKernelGGL(k_transport_columns<true>, grd, blk, 0, m->stream, g, tab, vel, T, S, (int)along_first, n, lines);
+      else hipLaunchKernelGGL(k_transport_columns<false>, grd, blk, 0, m->stream, g, tab, vel, T, S, (int)along_first, n, lines);
     }
     LAUNCHCHK();
     if (shape != GB25_TR_LINES) {
@@ -439,9 +468,7 @@ gb25_status gb25_get_transport(gb25_model* m, gb25_transport_faces faces, gb25_t
     }
   }
   const TransportPartial* from = shape == GB25_TR_LINES ? lines : shape == GB25_TR_PROFILE ? transport_profile(m) : transport_psi(m);
-  HIPCHK(hipMemcpyAsync(out, from, (size_t)count * sizeof(gb25_transport), hipMemcpyDeviceToHost, m->stream));
-  HIPCHK(hipStreamSynchronize(m->stream));
-  return GB25_OK;
+  return diag_download(m, out, from, (size_t)count * sizeof(gb25_transport));
 }
 
 gb25_status gb25_derived_dims(const gb25_model* m, gb25_derived q, int32_t dims[3]) {
@@ -454,43 +481,29 @@ gb25_status gb25_compute_derived(gb25_model* m, gb25_derived q, double param, in
                                  int32_t device_dims[3]) {
   if (!m) return GB25_ERR_INVALID_ARGUMENT;
   if (!dev) return fail(m, GB25_ERR_INVALID_ARGUMENT, "gb25_compute_derived: dev is NULL");
-  if (gb25_status s = derived_check(m, "gb25_compute_derived", q, param)) return s;
   int32_t e[3];
-  int kc = 0;
-  derived_extents(m, q, e);
-  if (gb25_status s = derived_levels(m, "gb25_compute_derived", e[2], k_first, k_count, &kc)) return s;
-  if (gb25_status s = derived_need_device(m, "gb25_compute_derived")) return s;
   const real* out = nullptr;
-  if (gb25_status s = derived_run(m, q, param, k_first, kc, &out)) return s;
+  if (gb25_status s = derived_window_run(m, "gb25_compute_derived", q, param, k_first, k_count, e, &out)) return s;
   HIPCHK(hipStreamSynchronize(m->stream));
   *dev = out;
-  if (device_dims) {
-    device_dims[0] = e[0]; device_dims[1] = e[1]; device_dims[2] = kc;
-  }
+  if (device_dims) memcpy(device_dims, e, sizeof e);
   return GB25_OK;
 }
 
 gb25_status gb25_get_derived(gb25_model* m, gb25_derived q, double param, int32_t k_first, int32_t k_count, void* host) {
   if (!m) return GB25_ERR_INVALID_ARGUMENT;
   if (!host) return fail(m, GB25_ERR_INVALID_ARGUMENT, "gb25_get_derived: host is NULL");
-  if (gb25_status s = derived_check(m, "gb25_get_derived", q, param)) return s;
   int32_t e[3];
-  int kc = 0;
-  derived_extents(m, q, e);
-  if (gb25_status s = derived_levels(m, "gb25_get_derived", e[2], k_first, k_count, &kc)) return s;
-  if (gb25_status s = derived_need_device(m, "gb25_get_derived")) return s;
   const real* out = nullptr;
-  if (gb25_status s = derived_run(m, q, param, k_first, kc, &out)) return s;
-  HIPCHK(hipMemcpyAsync(host, out, (size_t)e[0] * e[1] * kc * sizeof(real), hipMemcpyDeviceToHost, m->stream));
-  HIPCHK(hipStreamSynchronize(m->stream));
-  return GB25_OK;
+  if (gb25_status s = derived_window_run(m, "gb25_get_derived", q, param, k_first, k_count, e, &out)) return s;
+  return diag_download(m, host, out, (size_t)e[0] * e[1] * e[2] * sizeof(real));
 }
 
 gb25_status gb25_get_derived_stats(gb25_model* m, gb25_derived q, double param, gb25_field_stats* out) {
   if (!m) return GB25_ERR_INVALID_ARGUMENT;
   if (!out) return fail(m, GB25_ERR_INVALID_ARGUMENT, "gb25_get_derived_stats: out is NULL");
   if (gb25_status s = derived_check(m, "gb25_get_derived_stats", q, param)) return s;
-  if (gb25_status s = derived_need_device(m, "gb25_get_derived_stats")) return s;
+  if (gb25_status s = diag_need_device(m, "gb25_get_derived_stats")) return s;
   int32_t e[3];
   derived_extents(m, q, e);
   const DiagBox b{e[0], e[1], e[2], (long long)e[0], (long long)e[0] * e[1], 0};
@@ -498,38 +511,30 @@ gb25_status gb25_get_derived_stats(gb25_model* m, gb25_derived q, double param, 
   if (gb25_status s = diag_check_box(m, b)) return s;
   const real* src = nullptr;
   if (gb25_status s = derived_run(m, q, param, 0, e[2], &src)) return s;
-  {
-    Timed t(m, GB25_K_DIAGNOSTICS);
-    if (gb25_status s = diag_launch_stats(m, src, b, 0)) return s;
-  }
-  StatsPartial p;
-  HIPCHK(hipMemcpyAsync(&p, diag_result_slot(m, 0), sizeof p, hipMemcpyDeviceToHost, m->stream));
-  HIPCHK(hipStreamSynchronize(m->stream));
-  diag_fill_stats(m, GB25_T, p, b, 0, out);   // (interior: the offsets are those of any field of the rank, 0 in k)
-  return GB25_OK;
+  return diag_stats_of(m, GB25_T, src, b, 0, out);   // (interior: the offsets are those of any field of the rank, 0 in k)
 }
 
 gb25_status gb25_get_field_levels(gb25_model* m, gb25_field f, int32_t k_first, int32_t k_count, void* host) {
   if (!m) return GB25_ERR_INVALID_ARGUMENT;
   if (f < 0 || f >= GB25_FIELD_COUNT) return fail(m, GB25_ERR_INVALID_ARGUMENT, "gb25_get_field_levels: no field %d", (int)f);
   if (!host) return fail(m, GB25_ERR_INVALID_ARGUMENT, "gb25_get_field_levels: host is NULL");
-  if (k_first < 0 || k_count < -1 || k_count == 0)
+  if (k_first < 0 || k_count < -1 || k_count == 0)   // (what no extent can make right: refused before the device is asked for, a stale pHY' recomputed)
     return fail(m, GB25_ERR_INVALID_ARGUMENT, "gb25_get_field_levels: levels k_first = %d, k_count = %d (0-based interior levels; k_count = -1: all)",
                 (int)k_first, (int)k_count);
-  if (gb25_status s = derived_need_device(m, "gb25_get_field_levels")) return s;
+  if (gb25_status s = diag_need_device(m, "gb25_get_field_levels")) return s;
   const real* src = nullptr;
   DiagBox b;
   int kc = 0;
   if (gb25_status s = diag_source(m, f, &src)) return s;
   if (gb25_status s = diag_box(m, f, 0, &b)) return s;
-  if (gb25_status s = derived_levels(m, "gb25_get_field_levels", b.bz, k_first, k_count, &kc)) return s;
+  if (gb25_status s = diag_window(m, "gb25_get_field_levels", k_first, k_count, b.bz, "levels (k_first, k_count)", &kc)) return s;
   if (gb25_status s = derived_scratch(m)) return s;
   const size_t n = (size_t)b.bx * b.by * kc;
-  if (n > m->diag_derived_elems - m->diag_derived_plane) return fail(m, GB25_ERR_STATE, "gb25_get_field_levels: the levels need more room than the model's result array has");
+  if (n > m->diag.derived_elems - m->diag.derived_plane) return fail(m, GB25_ERR_STATE, "gb25_get_field_levels: the levels need more room than the model's result array has");
   if (gb25_status s = diag_wait_for_model(m)) return s;
   b.origin += b.plane * k_first;
   b.bz = kc;
-  real* out = m->diag_derived + m->diag_derived_plane;
+  real* out = m->diag.derived + m->diag.derived_plane;
   {
     Timed t(m, GB25_K_DIAGNOSTICS);
     constexpr int VW = 16 / sizeof(real);
@@ -537,9 +542,7 @@ gb25_status gb25_get_field_levels(gb25_model* m, gb25_field f, int32_t k_first, 
     hipLaunchKernelGGL(k_gather_levels<real>, dim3((chunks + 63) / 64, (b.by + 3) / 4, kc), dim3(64, 4), 0, m->stream, src, b, out);
     LAUNCHCHK();
   }
-  HIPCHK(hipMemcpyAsync(host, out, n * sizeof(real), hipMemcpyDeviceToHost, m->stream));
-  HIPCHK(hipStreamSynchronize(m->stream));
-  return GB25_OK;
+  return diag_download(m, host, out, n * sizeof(real));
 }
 
 int32_t gb25_field_stats_bytes(void) { return (int32_t)sizeof(gb25_field_stats); }
@@ -555,15 +558,7 @@ gb25_status gb25_get_field_stats(gb25_model* m, gb25_field f, int include_halos,
   if (gb25_status s = diag_box(m, f, include_halos, &b)) return s;
   if (gb25_status s = diag_check_box(m, b)) return s;
   if (gb25_status s = diag_wait_for_model(m)) return s;
-  {
-    Timed t(m, GB25_K_DIAGNOSTICS);
-    if (gb25_status s = diag_launch_stats(m, src, b, 0)) return s;
-  }
-  StatsPartial p;
-  HIPCHK(hipMemcpyAsync(&p, diag_result_slot(m, 0), sizeof p, hipMemcpyDeviceToHost, m->stream));
-  HIPCHK(hipStreamSynchronize(m->stream));
-  diag_fill_stats(m, f, p, b, include_halos, out);
-  return GB25_OK;
+  return diag_stats_of(m, f, src, b, include_halos, out);
 }
 
 gb25_status gb25_compare_field(gb25_model* m, gb25_field f, int include_halos, const void* other_dev, int32_t other_real_bytes,
@@ -592,7 +587,7 @@ gb25_status gb25_compare_field(gb25_model* m, gb25_field f, int include_halos, c
   const long long nb = diag_blocks(b);
   {
     Timed t(m, GB25_K_DIAGNOSTICS);
-    DiffPartial* part = (DiffPartial*)m->diag_scratch;
+    DiffPartial* part = (DiffPartial*)m->diag.scratch;
     if (other_real_bytes == 4)
       hipLaunchKernelGGL((k_field_diff<real, float>), dim3((unsigned)nb), dim3(DIAG_THREADS), 0, m->stream, src, b, (const float*)other_dev, ob, part);
     else
@@ -601,8 +596,7 @@ gb25_status gb25_compare_field(gb25_model* m, gb25_field f, int include_halos, c
     if (gb25_status s = diag_finish<DiffPartial>(m, nb, 0)) return s;
   }
   DiffPartial p;
-  HIPCHK(hipMemcpyAsync(&p, diag_result_slot(m, 0), sizeof p, hipMemcpyDeviceToHost, m->stream));
-  HIPCHK(hipStreamSynchronize(m->stream));
+  if (gb25_status s = diag_download(m, &p, diag_result_slot(m, 0), sizeof p)) return s;
   memset(out, 0, sizeof *out);
   out->max_abs_a = p.amax_a < 0 ? 0.0 : p.amax_a;
   out->max_abs_b = p.amax_b < 0 ? 0.0 : p.amax_b;
@@ -634,13 +628,12 @@ gb25_status gb25_get_state_monitor(gb25_model* m, gb25_state_monitor* out) {
       if (gb25_status s = diag_launch_stats(m, src[q], b[q], q)) return s;
     const long long nb = diag_blocks(b[0]);   // (the interior of u: Nx x Ny x Nz, the cells)
     hipLaunchKernelGGL(k_advective_cfl, dim3((unsigned)nb), dim3(DIAG_THREADS), 0, m->stream, m->g, src[0], src[1], src[2], b[0],
-                       (CflPartial*)m->diag_scratch);
+                       (CflPartial*)m->diag.scratch);
     LAUNCHCHK();
     if (gb25_status s = diag_finish<CflPartial>(m, nb, 6)) return s;
   }
   char host[7 * DIAG_RECORD];
-  HIPCHK(hipMemcpyAsync(host, diag_result_slot(m, 0), sizeof host, hipMemcpyDeviceToHost, m->stream));
-  HIPCHK(hipStreamSynchronize(m->stream));
+  if (gb25_status s = diag_download(m, host, diag_result_slot(m, 0), sizeof host)) return s;
   memset(out, 0, sizeof *out);
   gb25_field_stats* dst[6] = {&out->u, &out->v, &out->w, &out->eta, &out->T, &out->S};
   for (int q = 0; q < 6; q++) {
@@ -684,9 +677,7 @@ gb25_status gb25_integrate_field(gb25_model* m, gb25_field f, gb25_sum_shape sha
       if (gb25_status s = moments_fold(m, &b, 1)) return s;
   }
   const MomentsPartial* from = shape == GB25_SUM_ROWS ? moments_rows(m, 0) : shape == GB25_SUM_LEVELS ? moments_levels(m, 0) : moments_totals(m);
-  HIPCHK(hipMemcpyAsync(out, from, (size_t)count * sizeof(gb25_moments), hipMemcpyDeviceToHost, m->stream));
-  HIPCHK(hipStreamSynchronize(m->stream));
-  return GB25_OK;
+  return diag_download(m, out, from, (size_t)count * sizeof(gb25_moments));
 }
 
 gb25_status gb25_get_budget(gb25_model* m, gb25_budget* out) {
@@ -710,8 +701,7 @@ gb25_status gb25_get_budget(gb25_model* m, gb25_budget* out) {
     if (gb25_status s = moments_fold(m, b, MOMENTS_SLOTS)) return s;
   }
   gb25_moments tot[MOMENTS_SLOTS];
-  HIPCHK(hipMemcpyAsync(tot, moments_totals(m), sizeof tot, hipMemcpyDeviceToHost, m->stream));
-  HIPCHK(hipStreamSynchronize(m->stream));
+  if (gb25_status s = diag_download(m, tot, moments_totals(m), sizeof tot)) return s;
   memset(out, 0, sizeof *out);
   out->T = tot[0]; out->S = tot[1]; out->u = tot[2]; out->v = tot[3]; out->eta = tot[4];
   out->volume = out->T.measure;

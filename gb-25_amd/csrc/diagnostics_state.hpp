@@ -1,0 +1,110 @@
+// diagnostics_state.hpp -- every piece of memory and bookkeeping the read-only diagnostics own (diagnostics_host.hpp,
+// averages_host.hpp, classes_host.hpp, particles_host.hpp), as ONE member of gb25_model.  Host only; included by gb25_api.hip
+// behind the kernel headers (PartState: particle_kernels.hpp; GB25_A_COUNT and the info structs: include/gb25.h); like Field it is
+// local to that translation unit, so the libraries export nothing of it.
+// No stepping kernel reads or writes anything here.  release() is the one place that frees it (gb25_destroy), its two parts
+// serve gb25_averages_end and gb25_particles_end; invalidate_tables() is what a rebuild of the grid or of the bottom calls.
+#pragma once
+#include <cstring>
+
+namespace {
+
+struct DiagState {
+  // field statistics (gb25_get_field_stats, gb25_compare_field, gb25_get_state_monitor): the per-block records of the reduction
+  // kernels and the seven result records of a state monitor, one allocation made by the first call that needs it
+  void* scratch = nullptr;
+  size_t scratch_records = 0;
+  // integrals (gb25_integrate_field, gb25_get_budget): the row, level and total records of up to five fields, made by the first
+  // call that needs them
+  void* moments = nullptr;
+  size_t moments_rows = 0, moments_levels = 0;
+  // diagnostics' own tables, made by the first call that needs them (moments_tables), dropped whenever the grid or the bottom
+  // is rebuilt: by horizontal location the areas (curvilinear grids) and the first wet levels (grids with a bottom table); the
+  // derived fields' AZFF (curvilinear grids) and (double) zc | zf; the transports' DXCF and DYFC (curvilinear grids)
+  gb25::real* area[3] = {nullptr, nullptr, nullptr};
+  unsigned short* first_wet[3] = {nullptr, nullptr, nullptr};
+  gb25::real* azff = nullptr;
+  double* zt = nullptr;
+  gb25::real* face_length[2] = {nullptr, nullptr};
+  bool tables_valid = false;
+  // derived fields (gb25_compute_derived, gb25_get_field_levels): the packed result array -- one 2-D plane (the mixed-layer depth)
+  // followed by room for the largest interior a field of this model has --, made by the first call that needs it; the TEOS-10
+  // table folded at Z = 0 is part of the allocation of build_eos_tables, rebuilt with it and NOT freed here
+  gb25::real* derived = nullptr;
+  size_t derived_plane = 0, derived_elems = 0;
+  const double* eos0 = nullptr;
+  // transports (gb25_get_transport): the LINES, running sums and PROFILE records of one call, made by the first call
+  void* transport = nullptr;
+  size_t transport_lines = 0;
+  // class sums (gb25_get_class_sums): the padded edges, then the ROWS, CUMULATIVE and TOTAL records of one call; made by the
+  // first call, made anew when a call needs more bins
+  void* class_sums = nullptr;
+  size_t class_rows = 0, class_bins = 0;
+  // time averages (gb25_averages_*): the accumulators of the active groups and the array a normalized read-out is divided into
+  // -- ONE allocation (avg_acc[0] is its base: MEANS is always active), made by gb25_averages_begin, freed by gb25_averages_end
+  // and gb25_destroy --, the window, the sample count and weight_sum (avg_info)
+  double* avg_acc[GB25_A_COUNT] = {};
+  double* avg_out = nullptr;
+  gb25_averages_info avg_info = {};
+  bool avg_on = false;
+  // Lagrangian particles (gb25_particles_*): ONE allocation made by gb25_particles_begin, freed by gb25_particles_end and
+  // gb25_destroy -- two copies of the state (an advance reads part_state[part_cur] and writes the other), the sample array, the
+  // per-wave counter slots and their totals, the kbot table of every column the parents hold (made anew when the bottom is
+  // rebuilt: part_tables_valid)
+  void* part_base = nullptr;
+  gb25::PartState part_state[2] = {};
+  int part_cur = 0;
+  double* part_sample = nullptr;
+  unsigned* part_slots = nullptr;
+  unsigned long long* part_totals = nullptr;
+  int* part_kbot = nullptr;
+  bool part_on = false, part_tables_valid = false;
+  gb25_particles_info part_info = {};
+
+  // the grid or the bottom was rebuilt: the next call that needs a table makes it anew
+  void invalidate_tables() { tables_valid = part_tables_valid = false; }
+
+  template <class T>
+  static void drop(T*& p) {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+  }
+  void release_tables() {
+    for (auto& p : area) drop(p);
+    for (auto& p : first_wet) drop(p);
+    for (auto& p : face_length) drop(p);
+    drop(azff);
+    drop(zt);
+    tables_valid = false;
+  }
+  void release_averages() {
+    drop(avg_acc[0]);   // (one allocation: the accumulators, then the read-out array)
+    for (auto& p : avg_acc) p = nullptr;
+    avg_out = nullptr;
+    avg_on = false;
+    memset(&avg_info, 0, sizeof avg_info);
+  }
+  void release_particles() {
+    drop(part_base);   // (one allocation: every pointer below points into it)
+    for (auto& s : part_state) s = {};
+    part_sample = nullptr;
+    part_slots = nullptr;
+    part_totals = nullptr;
+    part_kbot = nullptr;
+    part_cur = 0;
+    part_on = part_tables_valid = false;
+    memset(&part_info, 0, sizeof part_info);
+  }
+  void release() {
+    drop(scratch);
+    drop(moments);
+    drop(derived);
+    drop(transport);
+    drop(class_sums);
+    release_tables();
+    release_averages();
+    release_particles();
+  }
+};
+
+}  // namespace

@@ -12,6 +12,7 @@
 #include "averages_kernels.hpp"
 #include "class_kernels.hpp"
 #include "particle_kernels.hpp"
+#include "diagnostics_state.hpp"
 
 #include <cmath>
 #include <cstdarg>
@@ -231,58 +232,11 @@ struct gb25_model {
   struct SlabGroup* group = nullptr; // exchange context (transport, buffers, comm stream) once gb25_comm_init_* was called
   int group_index = 0;               // this slab's position in group->slabs
   int fold_flip = 0;                 // folded slab: which of the two widened state sets the next substep reads
-  // diagnostics (diagnostics_host.hpp): the per-block records of the reduction kernels and the seven result records of a
-  // state monitor, one allocation made by the first call that needs it; prof_redirect >= 0: every timed launch is filed
-  // under that kernel id instead of its own (the pressure recomputed for the statistics of a stale pHY' is a diagnostic)
-  void* diag_scratch = nullptr;
-  size_t diag_scratch_records = 0;
+  // the read-only diagnostics' buffers, tables and bookkeeping (diagnostics_state.hpp: who makes and who frees each); prof_redirect
+  // >= 0: every timed launch is filed under that kernel id instead of its own (the pressure recomputed for the statistics of
+  // a stale pHY' is a diagnostic)
+  DiagState diag;
   int prof_redirect = -1;
-  // integrals (gb25_integrate_field, gb25_get_budget): the row, level and total records of up to five fields, and diagnostics'
-  // own tables by horizontal location -- areas (curvilinear grids) and first wet levels (grids with a bottom table) --, made by
-  // the first call that needs them, dropped whenever the grid or the bottom is rebuilt.  No stepping kernel reads them.
-  void* diag_moments = nullptr;
-  size_t diag_moments_rows = 0, diag_moments_levels = 0;
-  real* diag_area[3] = {nullptr, nullptr, nullptr};
-  unsigned short* diag_first_wet[3] = {nullptr, nullptr, nullptr};
-  bool diag_tables_valid = false;
-  // derived fields (gb25_compute_derived, gb25_get_field_levels): the packed result array -- one 2-D plane (the mixed-layer depth)
-  // followed by room for the largest interior a field of this model has --, made by the first call that needs it; diagnostics' own
-  // AZFF (curvilinear grids) and (double) zc | zf, rebuilt with the other tables; the TEOS-10 table folded at Z = 0, part of the
-  // allocation of build_eos_tables and rebuilt with it.  No stepping kernel reads or writes them.
-  real* diag_derived = nullptr;
-  size_t diag_derived_plane = 0, diag_derived_elems = 0;
-  real* diag_azff = nullptr;
-  double* diag_zt = nullptr;
-  const double* diag_eos0 = nullptr;
-  // transports (gb25_get_transport): the LINES, running sums and PROFILE records of one call, made by the first call; diagnostics'
-  // own DXCF and DYFC (curvilinear grids), rebuilt with the other tables.  No stepping kernel reads or writes them.
-  void* diag_transport = nullptr;
-  size_t diag_transport_lines = 0;
-  real* diag_face_length[2] = {nullptr, nullptr};
-  // class sums (gb25_get_class_sums, classes_host.hpp): the padded edges, then the ROWS, CUMULATIVE and TOTAL records of one call;
-  // made by the first call, made anew when a call needs more bins.  No stepping kernel reads or writes them.
-  void* diag_class = nullptr;
-  size_t diag_class_rows = 0, diag_class_bins = 0;
-  // time averages (gb25_averages_*, averages_host.hpp): the accumulators of the active groups and the array a normalized read-out
-  // is divided into -- ONE allocation, made by gb25_averages_begin, freed by gb25_averages_end and gb25_destroy --, the window,
-  // the sample count and weight_sum (avg_info).  No stepping kernel reads or writes them.
-  double* avg_acc[GB25_A_COUNT] = {};
-  double* avg_out = nullptr;
-  gb25_averages_info avg_info = {};
-  bool avg_on = false;
-  // Lagrangian particles (gb25_particles_*, particles_host.hpp): ONE allocation made by gb25_particles_begin, freed by
-  // gb25_particles_end and gb25_destroy -- two copies of the state (an advance reads part_state[part_cur] and writes the other),
-  // the sample array, the per-wave counter slots and their totals, the kbot table of every column the parents hold (made anew
-  // when the bottom is rebuilt).  No stepping kernel reads or writes them.
-  void* part_base = nullptr;
-  PartState part_state[2] = {};
-  int part_cur = 0;
-  double* part_sample = nullptr;
-  unsigned* part_slots = nullptr;
-  unsigned long long* part_totals = nullptr;
-  int* part_kbot = nullptr;
-  bool part_on = false, part_tables_valid = false;
-  gb25_particles_info part_info = {};
 };
 
 namespace {
@@ -313,6 +267,25 @@ bool is_v_shaped(int id) {
 }
 bool is_2d(int id) { return (id >= GB25_ETA && id <= GB25_GN_BT_V) || id == GB25_JB; }
 bool is_catke_field(int id) { return id >= GB25_E && id <= GB25_PREV_V; }
+// The northern edge of this rank: the fold of a tripolar grid (the top row of ranks only), a wall (v has a row Ny), or -- neither
+// of the two -- a neighbour rank.
+inline bool is_folded(const gb25_model* m) { return m->cfg.grid_type >= GB25_GRID_TRIPOLAR && !m->yn_open; }
+inline bool has_north_wall(const gb25_model* m) { return m->cfg.grid_type < GB25_GRID_TRIPOLAR && !m->yn_open; }
+// First wet level (= number of immersed cells) of LOCAL column (i, j) on the host; 0 without a bottom table.  Rows beyond a global
+// wall read the wall's row, rows beyond the rank read a neighbour's as far as the table holds them (kb_Ey).  The clamp of i and
+// the cap at Nz are there for safety and change no result: build_bottom stores the columns [-E, Nx + E) with E = kb_E >=
+// halo + 4, and the callers ask for i in [-1, Nx) (gb25_get_bottom_info, moments_tables: a cell and its western neighbour), [0, Nx)
+// (gb25_particles_set) and [-halo, Nx + halo) (particles_tables); every row the two row clamps can land on lies inside the global
+// grid, where build_bottom has stored level(), a count of at most Nz cells (its filler 255 stays in the rows beyond the walls,
+// which are never read here).
+inline int first_wet_level(const gb25_model* m, int i, int j) {
+  if (m->kbot.empty()) return 0;
+  const int E = m->kb_E, Ey = m->kb_Ey, ksx = m->Nx + 2 * E;
+  const int il = std::min(std::max(i, -E), m->Nx + E - 1);
+  const int jl = std::min(std::max(j + m->j0, 0), m->cfg.Ny - 1) - m->j0;
+  const int kb = m->kbot[(size_t)(il + E) + (size_t)ksx * (std::min(std::max(jl, -Ey), m->Ny + Ey - 1) + Ey)];
+  return std::min(kb, (int)m->cfg.Nz);
+}
 
 // --- profiling helpers -----------------------------------------------------------------------
 // Named ranges for a profiler's timeline, as the reference wraps its entry points in Reactant.Profiler.annotate("first_time_step" /
@@ -424,8 +397,7 @@ gb25_status upload_table(gb25_model* m, const std::vector<double>& h, int off, c
 }
 
 gb25_status build_grid(gb25_model* m) {
-  m->diag_tables_valid = false;   // (the integrals' own tables follow the grid: rebuilt by the next call that needs them)
-  m->part_tables_valid = false;   // (likewise the particles' kbot table)
+  m->diag.invalidate_tables();   // (the diagnostics' own tables follow the grid: rebuilt by the next call that needs them)
   const gb25_config& c = m->cfg;
   const int H = c.halo, Ny = m->Ny, Nz = c.Nz;
   // (the row tables of a rank of a 2-D decomposition also cover the rows its sub-cycle is widened by)
@@ -663,13 +635,12 @@ void curv_metrics_at(const gb25_model* m, int ig, int j, double out[GB25_M2_COUN
 // Fills m->h_curv (the local slab's columns, halo columns by their own global index) and uploads what the kernels read
 // (device_common.hpp, Curv).
 gb25_status build_curv_grid(gb25_model* m) {
-  m->diag_tables_valid = false;   // (the integrals' own tables follow the grid: rebuilt by the next call that needs them)
-  m->part_tables_valid = false;   // (likewise the particles' kbot table)
+  m->diag.invalidate_tables();   // (the diagnostics' own tables follow the grid: rebuilt by the next call that needs them)
   const gb25_config& c = m->cfg;
   const int Nx = m->Nx, Ny = m->Ny, H = c.halo, sx = Nx + 2 * H, sy = Ny + 2 * H + 1;
   const size_t n2 = (size_t)sx * sy;
   // (the fold is the northern edge of the top row of ranks only)
-  const bool tri = c.grid_type >= GB25_GRID_TRIPOLAR && !m->yn_open;
+  const bool tri = is_folded(m);
   for (auto& a : m->h_curv) a.assign(n2, 0.0);
   auto at = [&](int id) -> std::vector<double>& { return m->h_curv[id]; };
   parallel_rows(-H, Ny + H + 1, [&](int j) {
@@ -789,7 +760,7 @@ gb25_status build_eos_tables(gb25_model* m) {
   double* d = nullptr;
   HIPCHK(hipMalloc(&d, (tab.size() + dz.size() + surf.size()) * sizeof(double)));
   HIPCHK(hipMemcpy(d + tab.size() + dz.size(), surf.data(), surf.size() * sizeof(double), hipMemcpyHostToDevice));
-  m->diag_eos0 = d + tab.size() + dz.size();
+  m->diag.eos0 = d + tab.size() + dz.size();
   HIPCHK(hipMemcpy(d, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(d + tab.size(), dz.data(), dz.size() * sizeof(double), hipMemcpyHostToDevice));
   m->dev_tables.push_back(reinterpret_cast<real*>(d));
@@ -828,8 +799,7 @@ void build_substeps(gb25_model* m) {
 // by cell (inactive_cell / stencil_active) and tests/test_gpu_immersed.py compares the two.
 template <class ZB>
 gb25_status build_bottom(gb25_model* m, ZB zb) {
-  m->diag_tables_valid = false;   // (the integrals' own tables follow the grid: rebuilt by the next call that needs them)
-  m->part_tables_valid = false;   // (likewise the particles' kbot table)
+  m->diag.invalidate_tables();   // (the diagnostics' own tables follow the grid: rebuilt by the next call that needs them)
   const gb25_config& c = m->cfg;
   const int Nx = m->Nx, Ny = m->Ny, Nz = c.Nz, H = c.halo, offk = m->metric_off_k, j0 = m->j0;
   const int E = std::max(H, m->W) + 4, ksx = Nx + 2 * E;
@@ -2750,21 +2720,7 @@ void gb25_destroy(gb25_model* m) {
     for (Field* p : {&m->ahead[q], &m->ahead_uv[q], &m->ahead_G[q], &m->ahead_colsum[q]})
       if (p->d) hipFree(p->d);
   if (m->uv_partials) hipFree(m->uv_partials);
-  if (m->diag_scratch) hipFree(m->diag_scratch);
-  if (m->diag_moments) hipFree(m->diag_moments);
-  if (m->diag_derived) hipFree(m->diag_derived);
-  if (m->diag_azff) hipFree(m->diag_azff);
-  if (m->diag_zt) hipFree(m->diag_zt);
-  if (m->diag_transport) hipFree(m->diag_transport);
-  if (m->diag_class) hipFree(m->diag_class);
-  if (m->avg_acc[0]) hipFree(m->avg_acc[0]);
-  if (m->part_base) hipFree(m->part_base);
-  for (int q = 0; q < 2; q++)
-    if (m->diag_face_length[q]) hipFree(m->diag_face_length[q]);
-  for (int q = 0; q < 3; q++) {
-    if (m->diag_area[q]) hipFree(m->diag_area[q]);
-    if (m->diag_first_wet[q]) hipFree(m->diag_first_wet[q]);
-  }
+  m->diag.release();
   if (m->wbase) hipFree(m->wbase);
   for (auto p : m->d_ord)
     if (p) hipFree(p);
@@ -3182,13 +3138,9 @@ gb25_status gb25_set_vertical_faces(gb25_model* m, const double* zf, int32_t n) 
 gb25_status gb25_get_bottom_info(const gb25_model* m, int32_t which, int32_t i, int32_t j, double* value) {
   if (!m || !value || j < 0 || j >= m->Ny || i < 0 || i >= m->Nx || which < 0 || which > 2) return GB25_ERR_INVALID_ARGUMENT;
   if (m->kbot.empty()) { *value = which == 0 ? 0.0 : (double)m->g.Lz; return GB25_OK; }
-  const int E = m->kb_E, ksx = m->Nx + 2 * E, offk = m->metric_off_k, Nz = m->cfg.Nz;
-  auto kb = [&](int ii, int jj) {
-    const int jl = std::min(std::max(jj + m->j0, 0), m->cfg.Ny - 1) - m->j0;   // (clamped at the walls; a neighbour's row otherwise)
-    return m->kbot[(size_t)(ii + E) + (size_t)ksx * (std::min(std::max(jl, -m->kb_Ey), m->Ny + m->kb_Ey - 1) + m->kb_Ey)];
-  };
-  auto depth = [&](int ii, int jj) { return (double)(real)m->h_metric[GB25_M_ZF][offk + Nz] - (double)(real)m->h_metric[GB25_M_ZF][offk + kb(ii, jj)]; };
-  *value = which == 0 ? (double)kb(i, j) : which == 1 ? std::min(depth(i - 1, j), depth(i, j)) : std::min(depth(i, j - 1), depth(i, j));
+  const int offk = m->metric_off_k, Nz = m->cfg.Nz;
+  auto depth = [&](int ii, int jj) { return (double)(real)m->h_metric[GB25_M_ZF][offk + Nz] - (double)(real)m->h_metric[GB25_M_ZF][offk + first_wet_level(m, ii, jj)]; };
+  *value = which == 0 ? (double)first_wet_level(m, i, j) : which == 1 ? std::min(depth(i - 1, j), depth(i, j)) : std::min(depth(i, j - 1), depth(i, j));
   return GB25_OK;
 }
 gb25_status gb25_fill_halo_regions(gb25_model* m) {

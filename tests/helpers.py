@@ -2,6 +2,7 @@
 import numpy as np
 
 import gb25_amd as gb
+from gb25_amd.binding import FIELD_IDS
 from oracle_backend import CPU
 
 
@@ -26,6 +27,33 @@ def set_noisy_velocities(model, amplitude=1e-3, seed=42):
     dt = model.backend.dtype
     model.set(u=ui.astype(dt), v=vi.astype(dt))
     return ui, vi
+
+
+# What the GPU tests of the diagnostics (tests/test_gpu_{diagnostics,integrals,derived,transports,averages,classes,particles}.py) share
+EPS = float(np.finfo(np.float64).eps)
+GRID_NAMES = {0: "simple_lat_lon", 1: "gaussian_islands_lat_lon", 3: "tripolar", 4: "gaussian_islands"}
+CASES = [(ft, gt) for ft in ("Float32", "Float64") for gt in (0, 1, 4)]
+BASE_FIELDS = [n for n, i in FIELD_IDS.items() if i < FIELD_IDS["e"]]
+CATKE_FIELDS = [n for n, i in FIELD_IDS.items() if i >= FIELD_IDS["e"]]
+
+
+def size_of(grid_type):
+    return (48, 24, 6) if grid_type else (64, 32, 8)
+
+
+def stepped_model(float_type="Float32", grid_type=0, steps=3, size=None, seed=42, closure=None, dt=None, arch=None, **options):
+    """The baroclinic-instability state with noisy velocities after first_time_step and `steps` more; arch: another backend
+    factory (the CPU oracle) in place of GPU(float_type)."""
+    Nx, Ny, Nz = size or size_of(grid_type)
+    dt = dt or (60.0 if grid_type == 4 else 600.0)
+    m = gb.baroclinic_instability_model(arch or gb.GPU(float_type=float_type), Nx, Ny, Nz, dt=dt, grid_type=GRID_NAMES[grid_type],
+                                        closure=closure, options=options or None)
+    gb.set_baroclinic_instability(m)
+    set_noisy_velocities(m, seed=seed)
+    gb.first_time_step(m)
+    if steps:
+        gb.loop(m, steps)
+    return m
 
 
 def make_pair(Nx, Ny, Nz, dt, precision="f64", float_type="Float32", **kw):

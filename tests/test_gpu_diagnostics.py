@@ -12,31 +12,9 @@ import pytest
 import gb25_amd as gb
 from gb25_amd.binding import FIELD_IDS
 from gb25_amd.distributed import LocalSlabEnsemble
-from helpers import counter_rng, set_noisy_velocities
+from helpers import BASE_FIELDS, CASES, CATKE_FIELDS, EPS, GRID_NAMES, counter_rng, set_noisy_velocities, size_of, stepped_model
 
 pytestmark = pytest.mark.gpu
-EPS = float(np.finfo(np.float64).eps)
-GRID_NAMES = {0: "simple_lat_lon", 1: "gaussian_islands_lat_lon", 4: "gaussian_islands"}
-CASES = [(ft, gt) for ft in ("Float32", "Float64") for gt in (0, 1, 4)]
-BASE_FIELDS = [n for n, i in FIELD_IDS.items() if i < FIELD_IDS["e"]]
-CATKE_FIELDS = [n for n, i in FIELD_IDS.items() if i >= FIELD_IDS["e"]]
-
-
-def size_of(grid_type):
-    return (48, 24, 6) if grid_type else (64, 32, 8)
-
-
-def stepped_model(float_type="Float32", grid_type=0, steps=3, size=None, seed=42, closure=None, dt=None, **options):
-    Nx, Ny, Nz = size or size_of(grid_type)
-    dt = dt or (60.0 if grid_type == 4 else 600.0)
-    m = gb.baroclinic_instability_model(gb.GPU(float_type=float_type), Nx, Ny, Nz, dt=dt, grid_type=GRID_NAMES[grid_type],
-                                        closure=closure, options=options or None)
-    gb.set_baroclinic_instability(m)
-    set_noisy_velocities(m, seed=seed)
-    gb.first_time_step(m)
-    if steps:
-        gb.loop(m, steps)
-    return m
 
 
 def memory_order(a):

@@ -11,31 +11,11 @@ import gb25_amd as gb
 from gb25_amd.binding import FIELD_IDS, KERNEL_IDS, PARTICLE_STATUS
 from gb25_amd.distributed import LocalSlabEnsemble
 from gb25_amd.particles import (STATE_KEYS, advance_host, make_state, particle_fields, particle_tables, sample_host, seed_positions)
-from helpers import counter_rng, set_noisy_velocities
+from helpers import BASE_FIELDS, CASES, GRID_NAMES, counter_rng, size_of, stepped_model
 
 pytestmark = pytest.mark.gpu
-GRID_NAMES = {0: "simple_lat_lon", 1: "gaussian_islands_lat_lon", 3: "tripolar", 4: "gaussian_islands"}
-CASES = [(ft, gt) for ft in ("Float32", "Float64") for gt in (0, 1, 4)]
-BASE_FIELDS = [n for n, i in FIELD_IDS.items() if i < FIELD_IDS["e"]]
 INVALID, OUT_OF_MEMORY, STATE = 1, 3, 5
 N_MANY = 1000 + 193          # not a multiple of 64: the last wave is partly filled
-
-
-def size_of(grid_type):
-    return (48, 24, 6) if grid_type else (64, 32, 8)
-
-
-def stepped_model(float_type="Float32", grid_type=0, steps=0, size=None, closure=None, **options):
-    Nx, Ny, Nz = size or size_of(grid_type)
-    dt = 60.0 if grid_type >= 3 else 600.0
-    m = gb.baroclinic_instability_model(gb.GPU(float_type=float_type), Nx, Ny, Nz, dt=dt, grid_type=GRID_NAMES[grid_type],
-                                        closure=closure, **(dict(options=options) if options else {}))
-    gb.set_baroclinic_instability(m)
-    set_noisy_velocities(m)
-    gb.first_time_step(m)
-    if steps:
-        gb.loop(m, steps)
-    return m
 
 
 def same(got, want, what):
@@ -92,7 +72,7 @@ def check_against_the_restatement(m, n, what, samples=("T", "S")):
 @pytest.mark.parametrize("float_type,grid_type", CASES)
 @pytest.mark.parametrize("n", [1, N_MANY])
 def test_bit_for_bit_against_the_restatement(float_type, grid_type, n):
-    m = stepped_model(float_type, grid_type)
+    m = stepped_model(float_type, grid_type, steps=0)
     state, total = check_against_the_restatement(m, n, f"{float_type} grid {grid_type} n {n}")
     if n == N_MANY:
         start = seed_positions(m.backend, n, seed=7)
@@ -104,13 +84,13 @@ def test_bit_for_bit_against_the_restatement(float_type, grid_type, n):
 
 
 def test_against_the_restatement_with_catke():
-    m = stepped_model("Float32", 4, closure=gb.CATKEVerticalDiffusivity())
+    m = stepped_model("Float32", 4, steps=0, closure=gb.CATKEVerticalDiffusivity())
     check_against_the_restatement(m, N_MANY, "CATKE", samples=("T", "S", "e"))
     m.backend.close()
 
 
 def test_an_odd_width():
-    m = stepped_model("Float32", 0, size=(9, 8, 4))
+    m = stepped_model("Float32", 0, steps=0, size=(9, 8, 4))
     check_against_the_restatement(m, 200, "9 columns")
     m.backend.close()
 
@@ -119,7 +99,7 @@ def test_an_odd_width():
 def test_the_folded_grid(float_type, grid_type):
     """Particles in the two rows below the pivot row and a northward v planted everywhere: they reach the centres of the pivot
     row, get AT_FOLD, and stay where they are in both implementations."""
-    m = stepped_model(float_type, grid_type)
+    m = stepped_model(float_type, grid_type, steps=0, dt=60.0)
     b = m.backend
     Nx, Ny, Nz = size_of(grid_type)
     b.set_field("v", np.full(b.field_dims("v", True), 1.0), True)
@@ -150,6 +130,43 @@ def test_the_folded_grid(float_type, grid_type):
     b.close()
 
 
+@pytest.mark.parametrize("float_type,grid_type", [("Float32", 1), ("Float64", 0)])
+def test_the_tables_follow_the_host_grid_setters(float_type, grid_type):
+    """The device's kbot table is made by the first advance; set_bottom_height must drop it.  The particles that are there are set
+    anew into wet cells around the raised columns WITHOUT a new particles_begin (which would make the table anew by itself) and
+    advanced: bit for bit the restatement with the tables read afterwards, and not what the tables read before give."""
+    Nx, Ny, Nz = size = (48, 24, 6)
+    m = stepped_model(float_type, grid_type, steps=0, size=size)
+    b = m.backend
+    n, span = 300, 3.0e8 * 64 / Nx
+    state = seed_positions(b, n, seed=3)
+    b.particles_begin(n)
+    b.particles_set(*(state[q] for q in STATE_KEYS[:6]))
+    old = particle_tables(b)
+    advance_both(b, state, span, 1, old, "before set_bottom_height")       # (the device has made its table)
+    zc = np.array([b.metric("zc", k) for k in range(1, Nz + 1)])
+    zb = np.full((Nx, Ny), -1e30)
+    zb[5:9, 4:7] = 0.5 * (zc[1] + zc[2])          # two immersed cells
+    zb[20:22, 10] = 0.5 * (zc[3] + zc[4])         # four
+    zb[30, 12:15] = 10.0                          # land
+    b.set_bottom_height(zb)
+    assert b.bottom_info("kbot", 6, 5) == 2 and b.bottom_info("kbot", 31, 13) == Nz
+    new = particle_tables(b)
+    H = new["H"]
+    state = seed_positions(b, n, seed=9, rows=(3, 5))                      # (wet cells of the new bottom, rows 3 .. 7)
+    changed = old["kbot"][state["i"] + H, state["j"] + H] != new["kbot"][state["i"] + H, state["j"] + H]
+    print(f"  {int((old['kbot'] != new['kbot']).sum())} columns changed their first wet level, {int(changed.sum())} particles stand on one")
+    assert changed.any()
+    b.particles_set(*(state[q] for q in STATE_KEYS[:6]))
+    stale, _ = advance_host(b, state, span, 3, particle_fields(b), old)
+    got, cnt = advance_both(b, state, span, 3, new, "after set_bottom_height")
+    assert any(got[q].tobytes() != stale[q].tobytes() for q in STATE_KEYS), "a stale table would have passed"
+    assert cnt["nonfinite"] == 0 and cnt["too_far"] == 0
+    b.particles_end()
+    check_against_the_restatement(m, n, f"{float_type} grid {grid_type} on the new bottom")
+    b.close()
+
+
 LOOKAHEADS = dict(subcycle_lookahead=1, ab2_lookahead=1)
 
 
@@ -157,8 +174,8 @@ LOOKAHEADS = dict(subcycle_lookahead=1, ab2_lookahead=1)
 def test_advancing_is_read_only(float_type, grid_type):
     """Two identical models; one advances particles after every step.  Same bits, same look-ahead state, same launches of every
     phase of a step."""
-    watched = stepped_model(float_type, grid_type, **LOOKAHEADS)
-    alone = stepped_model(float_type, grid_type, **LOOKAHEADS)
+    watched = stepped_model(float_type, grid_type, steps=0, **LOOKAHEADS)
+    alone = stepped_model(float_type, grid_type, steps=0, **LOOKAHEADS)
     for m in (watched, alone):
         m.backend.profile_enable(True)
         m.backend.profile_reset()
@@ -239,7 +256,7 @@ def test_slabs_against_the_single_domain(P, grid_type):
 
 
 def test_refusals():
-    m = stepped_model("Float32", 1)
+    m = stepped_model("Float32", 1, steps=0)
     b = m.backend
     lib, h = b.lib, b.h
     Nx, Ny, Nz = size_of(1)

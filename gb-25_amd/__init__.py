@@ -14,7 +14,7 @@ from .model import (CATKEVerticalDiffusivity, default_ocean_closure, Field, Hydr
                     baroclinic_instability_model, budget, density_anomaly, first_time_step, initialize, kinetic_energy,
                     mixed_layer_depth, potential_density, vorticity,
                     heat_transport, meridional_transport, overturning, section_transport,
-                    overturning_in_classes, water_mass_census,
+                    overturning_in_classes, water_mass_census, zonal_power_spectrum, zonal_spectrum,
                     Averages, averages, run_averaged,
                     loop, resolution_to_points, state_monitor, set_baroclinic_instability, set_top_flux, time_step, update_state,
                     tupled_fill_halo_regions_workload, compute_tendencies_workload,
@@ -27,6 +27,8 @@ from .derived import (gather_derived, kinetic_energy_host, mixed_layer_depth_hos
 from .transports import combine_transports, face_area, fold_transports, transport_host, transport_terms
 from .classes import (class_bins, class_edges, class_sums_host, class_terms, class_values, combine_class_sums, fold_classes,
                       total_classes)
+from .spectra import (combine_spectra, cospectrum, dominant_wavenumber, host_table, power_spectrum, spectrum_host,
+                      zonal_coefficients)
 # (the submodule first, as for the averages: the name `particles` of the package is the function)
 from .particles import (Particles, ParticlesHost, advance_host, exchange_particles, particle_rates, particles, run_with_particles,
                         sample_host, seed_particles, seed_positions)

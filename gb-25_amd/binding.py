@@ -60,6 +60,7 @@ ABI_SYMBOLS = [
     "gb25_derived_dims", "gb25_compute_derived", "gb25_get_derived", "gb25_get_derived_stats", "gb25_get_field_levels",
     "gb25_transport_bytes", "gb25_get_transport",
     "gb25_class_sum_bytes", "gb25_get_class_sums",
+    "gb25_spectral_coefficient_bytes", "gb25_get_spectrum_table", "gb25_get_zonal_spectrum", "gb25_get_derived_zonal_spectrum",
     "gb25_averages_info_bytes", "gb25_averages_begin", "gb25_averages_accumulate", "gb25_averages_get_info", "gb25_average_dims",
     "gb25_get_average", "gb25_average_device_ptr", "gb25_averages_end",
     "gb25_particles_info_bytes", "gb25_particles_begin", "gb25_particles_set", "gb25_particles_get", "gb25_particles_advance",
@@ -85,7 +86,8 @@ PARTICLE_COUNTERS = ("blocked", "clamped_y", "clamped_z", "at_fold", "outside", 
 OPTION_IDS = {"kernels": 0, "ab2_lookahead": 1, "subcycle_lookahead": 2, "subcycle_block": 3, "fill_fused": 4,
               "two_streams": 5, "store_pressure": 6, "split_tendencies": 7, "pressure_precision": 8, "immersed_kernels": 9, "fold_fills": 10,
               "lazy_corrector": 11, "momentum_chunk_levels": 12, "tracer_chunk_levels": 13, "tracers_first": 14, "w_on_the_fly": 15, "sub_stream_priority": 16, "subcycle_whole": 17, "early_strips": 18,
-              "catke_stale_e_halos": 19, "comm_timeout_seconds": 20, "roctx_ranges": 21, "substep_order": 22, "fold_pivot_slaved": 23, "pressure_form": 24}
+              "catke_stale_e_halos": 19, "comm_timeout_seconds": 20, "roctx_ranges": 21, "substep_order": 22, "fold_pivot_slaved": 23, "pressure_form": 24,
+              "spectrum_table": 25}
 UNIQUE_ID_BYTES = 128
 # int32 fn(void *user, int32 buffer_set, const void *send_w, const void *send_e, void *recv_w, void *recv_e, int64 nbytes)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
@@ -198,6 +200,11 @@ class ClassSum(_Record):
     V T, V S of the wet cells --, how many contributed, and (bin 0 of a row only) how many were skipped as not finite."""
     _fields_ = [("measure", C.c_double), ("flow", C.c_double), ("heat", C.c_double), ("salt", C.c_double),
                 ("count", C.c_int64), ("nonfinite", C.c_int64)]
+
+
+class SpectralCoefficient(C.Structure):
+    """gb25_spectral_coefficient (include/gb25.h): X(m) = re + i im of one line, re = A, im = -B; a numpy complex128."""
+    _fields_ = [("re", C.c_double), ("im", C.c_double)]
 
 
 CLASS_SUM_DTYPE = np.dtype([("measure", np.float64), ("flow", np.float64), ("heat", np.float64), ("salt", np.float64),
@@ -383,6 +390,10 @@ def load_library(float_type="Float32"):
     lib.gb25_get_field_levels.argtypes = [P, C.c_int, C.c_int32, C.c_int32, P]
     lib.gb25_get_transport.argtypes = [P, C.c_int, C.c_int, C.c_int32, C.c_int32, P, C.c_int64]
     lib.gb25_get_class_sums.argtypes = [P, C.c_int, C.c_int, P, C.c_int32, C.c_int, C.c_int32, C.c_int32, P, C.c_int64]
+    lib.gb25_get_spectrum_table.argtypes = [P, P, P, C.c_int64]
+    lib.gb25_get_zonal_spectrum.argtypes = [P, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64, C.POINTER(C.c_int64)]
+    lib.gb25_get_derived_zonal_spectrum.argtypes = [P, C.c_int, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64,
+                                                    C.POINTER(C.c_int64)]
     lib.gb25_averages_begin.argtypes = [P, C.c_int32, C.c_int32, C.c_int32]
     lib.gb25_averages_accumulate.argtypes = [P, C.c_double]
     lib.gb25_averages_get_info.argtypes = [P, C.POINTER(AveragesInfo)]
@@ -417,7 +428,7 @@ def load_library(float_type="Float32"):
     for fn, struct in (("gb25_field_stats_bytes", FieldStats), ("gb25_field_diff_bytes", FieldDiff),
                        ("gb25_state_monitor_bytes", StateMonitor), ("gb25_moments_bytes", Moments),
                        ("gb25_budget_bytes", Budget), ("gb25_transport_bytes", Transport),
-                       ("gb25_class_sum_bytes", ClassSum),
+                       ("gb25_class_sum_bytes", ClassSum), ("gb25_spectral_coefficient_bytes", SpectralCoefficient),
                        ("gb25_averages_info_bytes", AveragesInfo), ("gb25_particles_info_bytes", ParticlesInfo)):
         getattr(lib, fn).restype = C.c_int32
         if getattr(lib, fn)() != C.sizeof(struct):
@@ -639,6 +650,37 @@ class HipBackend:
         self._call("gb25_get_class_sums", CLASS_WHAT[what], CLASS_VARIABLES[variable], edges.ctypes.data_as(C.c_void_p),
                    edges.size, CLASS_SHAPES[shape], int(first), int(count), out.ctypes.data_as(C.c_void_p), out.size)
         return out if shape == "total" else out.reshape(N, -1)
+
+    # ---- zonal wavenumber spectra on the device (include/gb25.h: "zonal wavenumber spectra"; gb-25_amd/spectra.py)
+    def spectrum_table(self):
+        """gb25_get_spectrum_table: (c, s), cos and sin of 2 pi r / N for the N columns of the global grid -- the table of the
+        definition, which the numpy restatement uses as it stands.  Needs no device."""
+        N = int(self.cfg.Nx)
+        c, s = np.empty(N, np.float64), np.empty(N, np.float64)
+        self._call("gb25_get_spectrum_table", c.ctypes.data_as(C.c_void_p), s.ctypes.data_as(C.c_void_p), N)
+        return c, s
+
+    def zonal_spectrum(self, source, wavenumbers=None, levels=None, param=None):
+        """gb25_get_zonal_spectrum / gb25_get_derived_zonal_spectrum: (X, nonfinite_lines), X complex128 [level, row, m], the
+        coefficients A - i B of the direct transform along i of every interior line of `source` -- a field name or a derived
+        name ("vorticity", "kinetic_energy", ..., "mixed_layer_depth" with param = the threshold).  wavenumbers = (m_first,
+        m_count), m_count = -1 or None: up to N/2; levels = (k_first, k_count) as in get_field_levels, None: all.  A line with
+        a value that is not finite has +0.0 coefficients and is counted in nonfinite_lines."""
+        derived = source in DERIVED_IDS
+        d = self.derived_dims(source) if derived else self.field_dims(source, False)
+        m_first, m_count = (0, -1) if wavenumbers is None else (int(wavenumbers[0]), int(wavenumbers[1]))
+        k_first, k_count = (0, -1) if levels is None else (int(levels[0]), int(levels[1]))
+        mc = max(int(self.cfg.Nx) // 2 + 1 - m_first if m_count == -1 else m_count, 0)
+        kc = max(d[2] - k_first if k_count == -1 else k_count, 0)
+        out = np.zeros((kc, d[1], mc), np.complex128)
+        bad = C.c_int64(0)
+        tail = (m_first, m_count, k_first, k_count, out.ctypes.data_as(C.c_void_p), out.size, C.byref(bad))
+        if derived:
+            q, param, _, _ = self._derived_args(source, param, None)
+            self._call("gb25_get_derived_zonal_spectrum", q, param, *tail)
+        else:
+            self._call("gb25_get_zonal_spectrum", FIELD_IDS[source], *tail)
+        return out, int(bad.value)
 
     # ---- time averages accumulated on the device (include/gb25.h: "time averages and eddy fluxes"); names: AVERAGE_IDS
     def averages_begin(self, groups=("means", "squares", "fluxes"), levels=None):

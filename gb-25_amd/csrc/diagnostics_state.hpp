@@ -40,6 +40,16 @@ struct DiagState {
   // first call, made anew when a call needs more bins
   void* class_sums = nullptr;
   size_t class_rows = 0, class_bins = 0;
+  // zonal spectra (gb25_get_zonal_spectrum, gb25_get_derived_zonal_spectrum): the count of skipped lines, then the coefficients of
+  // one call; made by the first call, made anew when a call needs more records.  The host word that count is copied into.  The
+  // interleaved copy of the table of the definition on the device (one of diagnostics' own tables: dropped with them, made anew
+  // after a rebuild of the grid); k_zonal_spectrum's dynamic-LDS attribute (only the instance with the table in LDS can pass
+  // 64 KB), per model as the others
+  void* spectrum = nullptr;
+  size_t spectrum_records = 0;
+  unsigned spec_skipped = 0;
+  double* spec_table = nullptr;
+  bool spec_valid = false, spec_lds_raised = false;
   // time averages (gb25_averages_*): the accumulators of the active groups and the array a normalized read-out is divided into
   // -- ONE allocation (avg_acc[0] is its base: MEANS is always active), made by gb25_averages_begin, freed by gb25_averages_end
   // and gb25_destroy --, the window, the sample count and weight_sum (avg_info)
@@ -62,7 +72,7 @@ struct DiagState {
   gb25_particles_info part_info = {};
 
   // the grid or the bottom was rebuilt: the next call that needs a table makes it anew
-  void invalidate_tables() { tables_valid = part_tables_valid = false; }
+  void invalidate_tables() { tables_valid = part_tables_valid = spec_valid = false; }
 
   template <class T>
   static void drop(T*& p) {
@@ -75,7 +85,8 @@ struct DiagState {
     for (auto& p : face_length) drop(p);
     drop(azff);
     drop(zt);
-    tables_valid = false;
+    drop(spec_table);
+    tables_valid = spec_valid = false;
   }
   void release_averages() {
     drop(avg_acc[0]);   // (one allocation: the accumulators, then the read-out array)
@@ -101,6 +112,7 @@ struct DiagState {
     drop(derived);
     drop(transport);
     drop(class_sums);
+    drop(spectrum);
     release_tables();
     release_averages();
     release_particles();

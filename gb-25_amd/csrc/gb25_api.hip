@@ -12,6 +12,7 @@
 #include "averages_kernels.hpp"
 #include "class_kernels.hpp"
 #include "particle_kernels.hpp"
+#include "spectrum_kernels.hpp"
 #include "diagnostics_state.hpp"
 
 #include <cmath>
@@ -145,6 +146,7 @@ struct gb25_model {
                                      // four blocks per CU, every block of a 1440 x 720 launch resident at once: 0.16 ms for 21 substeps against 0.21 with 7)
   int kernel_gen = 2;                // 2: LDS / flux-sharing tendency kernels (tendency_kernels.hpp); 1: direct-stencil kernels
   int pressure_form = 0;             // option PRESSURE_FORM: 0 = the rule of compute_p_impl; 1 tiles, 2 one row, 3 four rows per thread
+  int spectrum_table_where = 0;      // option SPECTRUM_TABLE: 0 = the rule of spectrum_run (LDS where it fits); 1 global memory
   int pressure_bits = 64;            // option PRESSURE_PRECISION: 64 = fp64 EOS + integral (default); 32 = the float type's own
   // single periodic domain: the last writers of u, v (corrector), T, S (tracer look-ahead) and eta, U, V (last barotropic
   // launch) also write the halo cells the fills derive from them, and the fill launches leave the step.  Halo cells
@@ -3337,6 +3339,10 @@ gb25_status gb25_set_option(gb25_model* m, gb25_option opt, int32_t v) {
       if (v < 0 || v > 3) return fail(m, GB25_ERR_INVALID_ARGUMENT, "GB25_OPT_PRESSURE_FORM: 0 (the library's rule), 1 (tiles), 2 (one row per thread) or 3 (four rows per thread)");
       m->pressure_form = v;
       return GB25_OK;
+    case GB25_OPT_SPECTRUM_TABLE:
+      if (v < 0 || v > 1) return fail(m, GB25_ERR_INVALID_ARGUMENT, "GB25_OPT_SPECTRUM_TABLE: 0 (the library's rule) or 1 (global memory)");
+      m->spectrum_table_where = v;
+      return GB25_OK;
     case GB25_OPT_FOLD_FILLS:
       m->fold_fills = v != 0;
       m->complete_fills_needed = 2;
@@ -3411,6 +3417,7 @@ gb25_status gb25_get_option(const gb25_model* m, gb25_option opt, int32_t* v) {
     case GB25_OPT_SPLIT_TENDENCIES: *v = m->split_tendencies; break;
     case GB25_OPT_PRESSURE_PRECISION: *v = m->pressure_bits; break;
     case GB25_OPT_PRESSURE_FORM: *v = m->pressure_form; break;
+    case GB25_OPT_SPECTRUM_TABLE: *v = m->spectrum_table_where; break;
     case GB25_OPT_IMMERSED_KERNELS: *v = m->immersed; break;
     case GB25_OPT_FOLD_FILLS: *v = m->fold_fills; break;
     case GB25_OPT_LAZY_CORRECTOR: *v = m->lazy_corrector; break;
@@ -3748,3 +3755,4 @@ gb25_status gb25_profile_get(gb25_model* m, gb25_kernel k, int64_t* launches, do
 #include "averages_host.hpp"
 #include "classes_host.hpp"
 #include "particles_host.hpp"
+#include "spectrum_host.hpp"

@@ -251,6 +251,14 @@ class LocalSlabEnsemble:
                 offsets.append((i0, j0))
         return combine_class_sums(parts, what, offsets, shape)
 
+    # zonal spectra: likewise (gb-25_amd/spectra.py); every slab transforms its own part of the lines with the global column and
+    # N, the parts add.  nonfinite_lines counts the skipped lines of the ranks (a line is skipped by the ranks that hold the value)
+    def zonal_spectrum(self, source, wavenumbers=None, levels=None, param=None):
+        from .spectra import combine_spectra
+        parts = [b.zonal_spectrum(source, wavenumbers, levels, param) for b in self.backends]
+        offsets = [(b.rx * self.Nx_loc, b.ry * self.Ny_loc) for b in self.backends]
+        return combine_spectra([p[0] for p in parts], offsets), sum(p[1] for p in parts)
+
     # time averages: likewise (gb-25_amd/averages.py); every slab accumulates its own interior, the read-out is placed by
     # global offset
     def averages_begin(self, groups=("means", "squares", "fluxes"), levels=None):

@@ -70,6 +70,11 @@ class Field:
         """The top interior level, [i, j, 1]: `indices = (:, :, Nz)` of the reference's surface writer."""
         return self.levels(self._b.field_dims(self.name, False)[2] - 1, 1)
 
+    def zonal_spectrum(self, wavenumbers=None, levels=None):
+        """(X [level, row, m] complex128, nonfinite_lines): the zonal wavenumber coefficients of every interior line, computed
+        where the field lives (zonal_spectrum of this module)."""
+        return _zonal_spectrum(self._b, self.name, wavenumbers, levels)
+
     def set(self, array, include_halos=False):
         a = np.asarray(array)
         if not include_halos and a.ndim >= 2:
@@ -304,6 +309,32 @@ def water_mass_census(model, edges, variable="potential_density", by_row=False):
     """How much water sits in each class of `variable`: records [b] (by_row: [j, b]) with measure = volume [m^3], heat = the
     volume integral of T, salt = that of S, count = the wet cells, reduced on the device (gb25_get_class_sums)."""
     return _class_sums(model, "cells", variable, edges, "rows" if by_row else "total")
+
+
+def _zonal_spectrum(b, source, wavenumbers=None, levels=None, param=None):
+    if hasattr(b, "zonal_spectrum"):
+        return b.zonal_spectrum(source, wavenumbers, levels, param)
+    from .spectra import spectrum_host               # (a backend without the kernel)
+    return spectrum_host(b, source, wavenumbers, levels, param)
+
+
+def zonal_spectrum(model, source, wavenumbers=None, levels=None, param=None):
+    """(X, nonfinite_lines): the zonal wavenumber coefficients X [level, row, m] (complex128, np.fft.rfft's sign) of every
+    interior line of `source` -- a field name ("u", "v", "T", "eta", ...) or a derived name ("vorticity", "kinetic_energy", ...;
+    "mixed_layer_depth" with param = the threshold) --, transformed on the device (include/gb25.h, gb25_get_zonal_spectrum): a few
+    kilobytes cross PCIe, not the field.  wavenumbers = (m_first, m_count), levels = (k_first, k_count), count = -1: to the end;
+    `zonal_spectrum(model, "v", levels=(Nz - 1, 1))` is the surface.  Along the grid's index i: a latitude circle only on the
+    LatitudeLongitudeGrid."""
+    return _zonal_spectrum(model.backend, source, wavenumbers, levels, param)
+
+
+def zonal_power_spectrum(model, source, wavenumbers=None, levels=None, param=None):
+    """The one-sided power spectrum P [level, row, m] of `source` (spectra.power_spectrum of zonal_spectrum): summed over all
+    wavenumbers it is the zonal mean of the square; of "v" the meridional kinetic-energy spectrum, of "vorticity" the enstrophy
+    spectrum."""
+    from .spectra import global_columns, power_spectrum
+    X, _ = _zonal_spectrum(model.backend, source, wavenumbers, levels, param)
+    return power_spectrum(X, global_columns(model.backend)[0], 0 if wavenumbers is None else int(wavenumbers[0]))
 
 
 class Averages:

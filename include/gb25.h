@@ -180,6 +180,9 @@ typedef enum {
                                     wide launches, one row per thread for narrow ones, 16 x 4 tiles for narrow lat-lon launches of
                                     at most 400 columns); 1 = tiles; 2 = one row per thread; 3 = four rows per thread, on any grid
                                     and for every launch.  PRESSURE_PRECISION = 32 ignores it */
+  GB25_OPT_SPECTRUM_TABLE,       /* [0] where the kernel of the zonal spectra reads its table of cosines and sines from (the same bits
+                                    from each; tests compare both): 0 = the library's rule (LDS where the table and the staged
+                                    lines fit 160 KB, else global memory); 1 = global memory */
   GB25_OPT_COUNT
 } gb25_option;
 
@@ -710,6 +713,49 @@ int32_t     gb25_class_sum_bytes(void);   /* sizeof the struct as THIS library w
 gb25_status gb25_get_class_sums(gb25_model *m, gb25_class_what what, gb25_class_variable variable, const double *edges,
                                 int32_t n_edges, gb25_class_shape shape, int32_t i_first, int32_t i_count, gb25_class_sum *out,
                                 int64_t count);
+
+/* ---- zonal wavenumber spectra on the device (csrc/spectrum_kernels.hpp, k_zonal_spectrum): which wavenumber grows, what the
+ *      kinetic-energy spectrum looks like, which scales carry the eddy heat flux -- a few kilobytes of coefficients instead of a
+ *      parent array crossing PCIe for np.fft.  Same contract as the diagnostics above: the state gb25_get_field would return,
+ *      READ-ONLY for the schedule (nothing pinned, every look-ahead alive; a stale GB25_PHY is recomputed as gb25_get_field_levels
+ *      does), LOCAL on a rank (combine on the host: gb-25_amd/spectra.py combine_spectra), bitwise repeatable, launches under
+ *      GB25_K_DIAGNOSTICS on the model's stream.
+ *
+ *      THE SOURCE.  A line is interior row j and interior level k of the source, local interior columns i = 0 .. nx-1; column i sits
+ *      at the global 0-based column g = i + global_offset_x of a grid of N columns.  The coefficients are taken ALONG THE GRID'S
+ *      INDEX i: on the curvilinear and folded grids that is the grid line, not a latitude circle.  x(i) = (double) of the value
+ *      gb25_get_field would return at that moment (gb25_get_derived for a derived source: (double) of the rounded derived value).
+ *      There is no masking of its own: masked cells hold what they hold.
+ *      THE TABLE.  c[r] = cos((2 pi r) / N), s[r] = sin((2 pi r) / N), r = 0 .. N-1, with 2 pi = 6.283185307179586, the product and
+ *      the quotient rounded to fp64: by the host's libm; the device's copy is made once per model (again after a rebuild of
+ *      the grid), the host's is handed out by gb25_get_spectrum_table (count must be N, else GB25_ERR_INVALID_ARGUMENT; needs no
+ *      device and writes nothing of the model, not even its error text).  The table the library returns
+ *      IS the table of the definition: a restatement takes it from there, as the others take metrics from gb25_get_metric.
+ *      THE COEFFICIENTS of wavenumber m, 0 <= m <= N/2, with r(i) = (m g) mod N in exact integer arithmetic:
+ *            A(m) = (((+0.0 + x(0) c[r(0)]) + x(1) c[r(1)]) + ...)   SEQUENTIAL over i ascending
+ *            B(m) = the same with s
+ *      every product and every sum rounded to fp64, NO fused multiply-adds (gb-25_amd/spectra.py restates them with numpy bit
+ *      for bit).  X(m) = A(m) - i B(m): the sign of np.fft.rfft, and its value when the rank holds the whole row; re = A, im = -B.
+ *      A line with any value that is not finite is skipped whole: every coefficient of it is exactly +0.0 (re and im), and the
+ *      line is counted once in *nonfinite_lines (may be NULL).
+ *
+ *      WINDOWS AND RECORDS.  m_first, m_count: the wavenumbers, m_count = -1: up to N/2.  k_first, k_count: the levels, as in
+ *      gb25_get_field_levels; a 2-D source (eta, the mixed-layer depth) takes 0, 1 or 0, -1.  rows = the interior by of the source.
+ *      The record of (m, row j, level k) is at ((k - k_first) rows + j) m_count + (m - m_first); count must be their number.  An
+ *      empty or out-of-range window, or another count, is GB25_ERR_INVALID_ARGUMENT.  gb25_get_derived_zonal_spectrum computes the
+ *      derived field as gb25_compute_derived does and transforms the packed array with the same kernel: the vorticity gives the
+ *      enstrophy spectrum, the kinetic energy its own.  The records live in a buffer the model owns (made by the first call, made
+ *      anew when a call asks for more records -- refused with GB25_ERR_OUT_OF_MEMORY before the allocation when the device has
+ *      less free --, freed by gb25_destroy); a call makes one device-to-host copy of exactly the records asked for, and one of the
+ *      count of skipped lines. */
+typedef struct { double re, im; } gb25_spectral_coefficient;   /* re = A, im = -B */
+int32_t     gb25_spectral_coefficient_bytes(void);   /* sizeof the struct as THIS library was built */
+gb25_status gb25_get_spectrum_table(const gb25_model *m, double *cos_out, double *sin_out, int64_t count);
+gb25_status gb25_get_zonal_spectrum(gb25_model *m, gb25_field f, int32_t m_first, int32_t m_count, int32_t k_first, int32_t k_count,
+                                    gb25_spectral_coefficient *out, int64_t count, int64_t *nonfinite_lines);
+gb25_status gb25_get_derived_zonal_spectrum(gb25_model *m, gb25_derived d, double param, int32_t m_first, int32_t m_count,
+                                            int32_t k_first, int32_t k_count, gb25_spectral_coefficient *out, int64_t count,
+                                            int64_t *nonfinite_lines);
 
 /* ---- time averages and eddy fluxes accumulated on the device (csrc/averages_kernels.hpp, k_averages_accumulate): what the other
  *      diagnostics cannot do -- remember something between two calls.  The time-mean state, eddy kinetic energy and tracer

@@ -43,7 +43,7 @@ const OPTION = (kernels = 0, ab2_lookahead = 1, subcycle_lookahead = 2, subcycle
                 immersed_kernels = 9, fold_fills = 10, lazy_corrector = 11, momentum_chunk_levels = 12, tracer_chunk_levels = 13,
                 tracers_first = 14, w_on_the_fly = 15, sub_stream_priority = 16, subcycle_whole = 17, early_strips = 18,
                 # restatement choices a Julia dump settles (DESIGN.md section 0), and two run-time knobs
-                catke_stale_e_halos = 19, comm_timeout_seconds = 20, roctx_ranges = 21, substep_order = 22, fold_pivot_slaved = 23, pressure_form = 24)
+                catke_stale_e_halos = 19, comm_timeout_seconds = 20, roctx_ranges = 21, substep_order = 22, fold_pivot_slaved = 23, pressure_form = 24, spectrum_table = 25)
 
 # mirror of gb25_config; isbits, passed by reference
 Base.@kwdef mutable struct Config

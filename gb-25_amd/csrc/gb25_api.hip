@@ -47,6 +47,32 @@ struct EventPair {
   hipEvent_t a, b;
 };
 
+// Every block of device memory a model allocates, remembered where it is made and freed by gb25_destroy in one loop: whichever
+// member holds a pointer by then (the look-aheads exchange them) and however many Fields share a block.  A block is remembered
+// before it is zeroed, so a failing hipMemset loses nothing.  (DiagState frees in mid-life and keeps its own memory.)
+struct DeviceBlocks {
+  std::vector<void*> blocks;
+  template <class T>
+  hipError_t alloc(T** p, size_t bytes, bool zero = false) {
+    void* d = nullptr;
+    const hipError_t e = hipMalloc(&d, bytes);
+    if (e != hipSuccess) return e;
+    blocks.push_back(d);
+    *p = static_cast<T*>(d);
+    return zero ? hipMemset(d, 0, bytes) : hipSuccess;
+  }
+  template <class T>
+  void release(T*& p) {   // one block before the end (a field of the prescribed atmosphere that is taken away again)
+    blocks.erase(std::remove(blocks.begin(), blocks.end(), static_cast<void*>(p)), blocks.end());
+    (void)hipFree(p);
+    p = nullptr;
+  }
+  void release_all() {
+    for (void* d : blocks) (void)hipFree(d);
+    blocks.clear();
+  }
+};
+
 }  // namespace
 
 struct gb25_model {
@@ -83,7 +109,8 @@ struct gb25_model {
   bool ahead_baro_valid = false;
   // pHY' is a diagnostic: inside a composite step only its differences are stored (4 of the kernel's 20 B/cell
   // saved) and the field is recomputed when the host asks for it; pinned to "always stored" once its pointer is out
-  bool phy_stale = false, phy_pinned = false;
+  bool phy_stale = false;
+  int phy_pinned = 0;                // option STORE_PRESSURE (0 or 1, as every option flag below)
   bool baro_inflight = false;        // a look-ahead sub-cycle is on the side stream and nobody has waited for it yet
   bool baro_adopted = false;         // staged path: stage 0 of this step adopted the sub-cycle look-ahead
   int baro_ahead = 1;                // option SUBCYCLE_LOOKAHEAD = 0: sub-cycle inside the step, on the critical path
@@ -91,7 +118,7 @@ struct gb25_model {
   int fill_fused = 1;                // y, z and periodic-x fills of a single slab in one launch (option FILL_FUSED = 0: two)
   int ab2_ahead = 1;                 // option AB2_LOOKAHEAD: 0 = stand-alone AB2 kernels, 1 = both look-aheads, 2 = tracers only
   real* bars = nullptr;         // contiguous etabar | Ubar | Vbar
-  std::vector<real*> dev_tables;
+  DeviceBlocks mem;             // owner of every device allocation below (not of DiagState's, not of the exchange context's)
   std::vector<double> h_metric[11];
   // orthogonal curvilinear grid (grid_type >= 2): the 14 horizontal metrics by location, fp64, parent layout of a (c,f)
   // field (gb25_get_metric2); cell-centre coordinates in degrees for analytic bottoms
@@ -129,11 +156,14 @@ struct gb25_model {
   // and their halo cells are complete (side stream); the tracer kernel waits for it, the momentum kernel for ev_join.
   hipEvent_t ev_ts = nullptr, ev_tend = nullptr;
   hipEvent_t ev_strips = nullptr;    // slab: the pressure strips next to the x halos are done (exchange stream, stage 33)
+  // the lists gb25_create and gb25_destroy loop over (baro_stream is created on demand: time_step_impl)
+  std::array<hipEvent_t*, 7> events() { return {&ev_fork, &ev_join, &ev_baro, &ev_mom, &ev_ts, &ev_tend, &ev_strips}; }
+  std::array<hipStream_t*, 3> streams() { return {&own_stream, &side_stream, &baro_stream}; }
   bool strips_issued = false;
   int early_strips = 1;              // option EARLY_STRIPS
   int tracers_first = 1;
   bool tend_forkable = false;       // the last tendency evaluation was a composite step's, tracers first: ev_tend covers both kernels
-  bool two_streams = true;          // option TWO_STREAMS = 0: strictly sequential phases on one stream
+  int two_streams = 1;              // option TWO_STREAMS = 0: strictly sequential phases on one stream
   bool profile = false;
   int profile_only = -1;             // >= 0: time this kernel id alone (keeps the event records out of the other launches)
   std::vector<EventPair> pending[GB25_K_COUNT];
@@ -163,7 +193,7 @@ struct gb25_model {
   int sub_priority = 0;              // slab: the stream of the look-ahead's substeps is a high-priority one (read when the exchange context is built)
   // immersed boundary (GridFittedBottom): first active level per column on the columns [-kb_E, Nx + kb_E) x [0, Ny)
   // (host), the folded tables of device_common.hpp (device), the depths of the wide barotropic arrays of a slab
-  bool immersed = false;             // some cell is immersed: the IMM kernel variants run
+  int immersed = 0;                  // some cell is immersed: the IMM kernel variants run
   int kb_E = 0, kb_Ey = 0;           // (kbot: pitch Nx + 2 kb_E, row of local row j: j + kb_Ey)
   std::vector<int> kbot;
   unsigned* d_ord[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -217,7 +247,7 @@ struct gb25_model {
   bool implicit_lds_raised[2] = {false, false};   // k_implicit_vertical's dynamic-LDS attribute (Nz > 128), likewise
   bool whole_attr_set[2][2] = {{false, false}, {false, false}};   // k_barotropic_whole's dynamic-LDS attribute, per instance, on THIS model's device
   int comm_timeout_s = 180;          // option COMM_TIMEOUT_SECONDS
-  bool roctx_ranges = true;          // option ROCTX_RANGES
+  int roctx_ranges = 1;              // option ROCTX_RANGES
   int substep_order = 0;             // option SUBSTEP_ORDER
   double catke_prev_time = 0;        // diffusivity_fields.previous_compute_time
   // where diffusivity_fields.previous_velocities live (single domain: no copies in the steady state).  0: in their fields
@@ -225,7 +255,7 @@ struct gb25_model {
   // look-ahead's partner buffers -- the AB2 step that followed adopted the look-ahead by exchanging pointers, and the buffers
   // it left hold u, v as they were at the last compute_diffusivities!, halos included.  materialize_prev_uv brings them home.
   int prev_uv_src = 0;
-  bool catke_stale_e_halos = false;  // option CATKE_STALE_E_HALOS
+  int catke_stale_e_halos = 0;       // option CATKE_STALE_E_HALOS
   bool n2_fresh = false;             // (unused since N^2 = g (alpha dzT - beta dzS) has a kernel of its own)
   Field catke_gam[2];                // Nz > 64: the elimination factors of the streamed implicit solve
   real* d_implicit[2] = {nullptr, nullptr};   // elimination tables of the implicit solve for (u, v) and (T, S): lo | 1/beta | gamma
@@ -391,9 +421,8 @@ gb25_status upload_table(gb25_model* m, const std::vector<double>& h, int off, c
   std::vector<real> f(h.size());
   for (size_t a = 0; a < h.size(); a++) f[a] = (real)h[a];
   real* d = nullptr;
-  HIPCHK(hipMalloc(&d, f.size() * sizeof(real)));
+  HIPCHK(m->mem.alloc(&d, f.size() * sizeof(real)));
   HIPCHK(hipMemcpy(d, f.data(), f.size() * sizeof(real), hipMemcpyHostToDevice));
-  m->dev_tables.push_back(d);
   *out = d + off;
   return GB25_OK;
 }
@@ -709,7 +738,7 @@ gb25_status build_curv_wide(gb25_model* m) {
     }
   });
   for (int q = 0; q < 5; q++) {
-    if (!m->d_wideM[q]) HIPCHK(hipMalloc(&m->d_wideM[q], t[q].size() * sizeof(real)));
+    if (!m->d_wideM[q]) HIPCHK(m->mem.alloc(&m->d_wideM[q], t[q].size() * sizeof(real)));
     HIPCHK(hipMemcpy(m->d_wideM[q], t[q].data(), t[q].size() * sizeof(real), hipMemcpyHostToDevice));
   }
   return GB25_OK;
@@ -760,12 +789,11 @@ gb25_status build_eos_tables(gb25_model* m) {
   }
   fold(0.0, surf.data());
   double* d = nullptr;
-  HIPCHK(hipMalloc(&d, (tab.size() + dz.size() + surf.size()) * sizeof(double)));
+  HIPCHK(m->mem.alloc(&d, (tab.size() + dz.size() + surf.size()) * sizeof(double)));
   HIPCHK(hipMemcpy(d + tab.size() + dz.size(), surf.data(), surf.size() * sizeof(double), hipMemcpyHostToDevice));
   m->diag.eos0 = d + tab.size() + dz.size();
   HIPCHK(hipMemcpy(d, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(d + tab.size(), dz.data(), dz.size() * sizeof(double), hipMemcpyHostToDevice));
-  m->dev_tables.push_back(reinterpret_cast<real*>(d));
   m->g.eos = d;
   m->g.eosf = d + (size_t)28 * (Nz + 1);
   m->g.dzf_d = d + tab.size();
@@ -881,7 +909,7 @@ gb25_status build_bottom(gb25_model* m, ZB zb) {
     }
   });
   auto upload = [&](const void* h, size_t bytes, void** d) -> gb25_status {
-    if (!*d) HIPCHK(hipMalloc(d, bytes));
+    if (!*d) HIPCHK(m->mem.alloc(d, bytes));
     HIPCHK(hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
     return GB25_OK;
   };
@@ -947,7 +975,7 @@ double gaussian_islands_bottom(const gb25_model* m, int i_local, int j) {
 
 gb25_status alloc_field(gb25_model* m, Field& F, int nx, int ny, int nz) {
   F.nx = nx; F.ny = ny; F.nz = nz;
-  hipError_t e = hipMalloc(&F.d, F.elems() * sizeof(real));
+  hipError_t e = m->mem.alloc(&F.d, F.elems() * sizeof(real));
   if (e != hipSuccess)
     return fail(m, GB25_ERR_OUT_OF_MEMORY, "hipMalloc of %zu bytes failed: %s", F.elems() * sizeof(real),
                 hipGetErrorString(e));
@@ -1448,7 +1476,7 @@ gb25_status implicit_tables(gb25_model* m, int kind, double dt, double K) {
   HIPCHK(hipStreamSynchronize(m->stream));   // (a solve with the old tables may still be running, on either stream)
   HIPCHK(hipStreamSynchronize(m->own_stream));
   HIPCHK(hipStreamSynchronize(m->side_stream));
-  if (!m->d_implicit[kind]) HIPCHK(hipMalloc(&m->d_implicit[kind], tab.size() * sizeof(real)));
+  if (!m->d_implicit[kind]) HIPCHK(m->mem.alloc(&m->d_implicit[kind], tab.size() * sizeof(real)));
   HIPCHK(hipMemcpy(m->d_implicit[kind], tab.data(), tab.size() * sizeof(real), hipMemcpyHostToDevice));
   m->implicit_key[kind][0] = dt;
   m->implicit_key[kind][1] = K;
@@ -2104,14 +2132,14 @@ gb25_status atmosphere_ocean_fluxes_impl(gb25_model* m) {
   const size_t n2 = (size_t)g.sx * g.sy_v;
   for (int q = 0; q < 4; q++) {
     if (!m->d_top_flux[q]) {
-      HIPCHK(hipMalloc(&m->d_top_flux[q], n2 * sizeof(real)));
+      HIPCHK(m->mem.alloc(&m->d_top_flux[q], n2 * sizeof(real)));
       HIPCHK(hipMemsetAsync(m->d_top_flux[q], 0, n2 * sizeof(real), m->stream));
     }
     m->g.top_flux[q] = m->d_top_flux[q];
   }
   for (int q = 0; q < 2; q++)
     if (!m->d_tau[q]) {
-      HIPCHK(hipMalloc(&m->d_tau[q], n2 * sizeof(double)));
+      HIPCHK(m->mem.alloc(&m->d_tau[q], n2 * sizeof(double)));
       HIPCHK(hipMemsetAsync(m->d_tau[q], 0, n2 * sizeof(double), m->stream));
     }
   Atmosphere A;
@@ -2554,27 +2582,23 @@ gb25_status gb25_create(const gb25_config* cfg, gb25_model** out) {
     HIPCHK(hipGetDeviceProperties(&prop, cfg->device));
     m->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   }
-  HIPCHK(hipStreamCreateWithFlags(&m->own_stream, hipStreamNonBlocking));
   // (few streams on purpose: HIP multiplexes streams onto a handful of hardware queues, and two streams that share one
   // run in order -- a rocprof trace of eight slabs in one process, 25 streams, shows the exchange stream and the main
   // stream taking turns.  A slab has three: own, side, and the exchange stream of its context; the stream of
   // SUBCYCLE_LOOKAHEAD = 2 is created on demand.)
+  for (hipStream_t* st : m->streams()) {
+    if (st == &m->baro_stream) continue;   // (on demand)
 #ifdef GB25_SIDE_PRIO
-  {   // (tools/build_variant.sh experiment: the side stream -- the pressure branch -- at the LOWEST / main at the highest priority)
-    int least = 0, greatest = 0;
-    HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    HIPCHK(hipStreamCreateWithPriority(&m->side_stream, hipStreamNonBlocking, GB25_SIDE_PRIO > 0 ? least : greatest));
-  }
-#else
-  HIPCHK(hipStreamCreateWithFlags(&m->side_stream, hipStreamNonBlocking));
+    if (st == &m->side_stream) {   // (tools/build_variant.sh experiment: the side stream -- the pressure branch -- at the LOWEST / main at the highest priority)
+      int least = 0, greatest = 0;
+      HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+      HIPCHK(hipStreamCreateWithPriority(st, hipStreamNonBlocking, GB25_SIDE_PRIO > 0 ? least : greatest));
+      continue;
+    }
 #endif
-  HIPCHK(hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&m->ev_join, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&m->ev_baro, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&m->ev_mom, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&m->ev_ts, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&m->ev_tend, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&m->ev_strips, hipEventDisableTiming));
+    HIPCHK(hipStreamCreateWithFlags(st, hipStreamNonBlocking));
+  }
+  for (hipEvent_t* ev : m->events()) HIPCHK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
 
   m->stream = m->own_stream;
   m->last_dt = cfg->dt;
@@ -2605,8 +2629,7 @@ gb25_status gb25_create(const gb25_config* cfg, gb25_model** out) {
   }
   {
     size_t nc = (size_t)sx * (m->Ny + 2 * H), nv = (size_t)sx * (m->Ny + 2 * H + 1);
-    HIPCHK(hipMalloc(&m->bars, (2 * nc + nv) * sizeof(real)));
-    HIPCHK(hipMemset(m->bars, 0, (2 * nc + nv) * sizeof(real)));
+    HIPCHK(m->mem.alloc(&m->bars, (2 * nc + nv) * sizeof(real), true));
     Field& e = m->f[GB25_ETA_BAR]; e.d = m->bars; e.nx = sx; e.ny = m->Ny + 2 * H; e.nz = 1;
     Field& u = m->f[GB25_U_BAR]; u.d = m->bars + nc; u.nx = sx; u.ny = m->Ny + 2 * H; u.nz = 1;
     Field& v = m->f[GB25_V_BAR]; v.d = m->bars + 2 * nc; v.nx = sx; v.ny = m->Ny + 2 * H + 1; v.nz = 1;
@@ -2619,8 +2642,7 @@ gb25_status gb25_create(const gb25_config* cfg, gb25_model** out) {
   {   // partners of the filtered state, laid out like `bars`
     size_t off = 0, tot = 0;
     for (int q = 0; q < 3; q++) tot += m->f[GB25_ETA_BAR + q].elems();
-    HIPCHK(hipMalloc(&m->bars_ahead, tot * sizeof(real)));
-    HIPCHK(hipMemset(m->bars_ahead, 0, tot * sizeof(real)));
+    HIPCHK(m->mem.alloc(&m->bars_ahead, tot * sizeof(real), true));
     for (int q = 0; q < 3; q++) {
       m->ahead_bar[q] = m->f[GB25_ETA_BAR + q];
       m->ahead_bar[q].d = m->bars_ahead + off;
@@ -2639,10 +2661,8 @@ gb25_status gb25_create(const gb25_config* cfg, gb25_model** out) {
   }
   {
     const size_t np = (size_t)4 * std::max(1, m->g.Nz / 6) * m->g.sx * m->g.sy_v;   // (room for chunks of 6 levels)
-    HIPCHK(hipMalloc(&m->uv_partials, np * sizeof(real)));
-    HIPCHK(hipMemset(m->uv_partials, 0, np * sizeof(real)));
-    HIPCHK(hipMalloc(&m->wbase, (np / 4) * sizeof(real)));
-    HIPCHK(hipMemset(m->wbase, 0, (np / 4) * sizeof(real)));
+    HIPCHK(m->mem.alloc(&m->uv_partials, np * sizeof(real), true));
+    HIPCHK(m->mem.alloc(&m->wbase, (np / 4) * sizeof(real), true));
   }
   if ((s = alloc_field(m, m->corr[0], sx, m->f[GB25_BT_V].ny, 1))) return s;
   if ((s = alloc_field(m, m->corr[1], sx, m->f[GB25_BT_V].ny, 1))) return s;
@@ -2682,8 +2702,7 @@ gb25_status gb25_create(const gb25_config* cfg, gb25_model** out) {
         tot += m->wideBar[q].elems();
       }
       real* base = nullptr;
-      HIPCHK(hipMalloc(&base, tot * sizeof(real)));
-      HIPCHK(hipMemset(base, 0, tot * sizeof(real)));
+      HIPCHK(m->mem.alloc(&base, tot * sizeof(real), true));
       for (int q = 0; q < 3; q++) {
         m->wideBar[q].d = base;
         base += m->wideBar[q].elems();
@@ -2692,7 +2711,7 @@ gb25_status gb25_create(const gb25_config* cfg, gb25_model** out) {
     if ((s = alloc_field(m, m->wideG[0], wsx, m->f[GB25_GN_BT_U].ny + wy, 1))) return s;
     if ((s = alloc_field(m, m->wideG[1], wsx, m->f[GB25_GN_BT_V].ny + wy, 1))) return s;
     if (m->g.cv.on && (s = build_curv_wide(m))) return s;
-    if (m->Wy && !m->slab) HIPCHK(hipMalloc(&m->tall_buf, (size_t)5 * (m->Wy + 1) * wsx * sizeof(real)));
+    if (m->Wy && !m->slab) HIPCHK(m->mem.alloc(&m->tall_buf, (size_t)5 * (m->Wy + 1) * wsx * sizeof(real)));
   }
   if ((s = rebuild_bottom(m))) return s;
   HIPCHK(hipDeviceSynchronize());
@@ -2703,78 +2722,20 @@ void gb25_destroy(gb25_model* m) {
   if (!m) return;
   if (m->group) group_destroy(m->group);   // (the exchange context of every slab it holds)
   if (m->own_stream) hipStreamSynchronize(m->own_stream);
-  for (int id = 0; id < GB25_FIELD_COUNT; id++)
-    if (!(id >= GB25_ETA_BAR && id <= GB25_V_BAR) && m->f[id].d) hipFree(m->f[id].d);
-  if (m->bars) hipFree(m->bars);
-  if (m->dpx.d) hipFree(m->dpx.d);
-  if (m->dpy.d) hipFree(m->dpy.d);
-
-  for (int q = 0; q < 3; q++)
-    for (Field* p : {&m->pp[q], &m->pp2[q], &m->ahead_eta[q]})
-      if (p->d) hipFree(p->d);
-  if (m->bars_ahead) hipFree(m->bars_ahead);
-  if (m->tall_buf) hipFree(m->tall_buf);
-  for (auto& p : m->colsum)
-    if (p.d) hipFree(p.d);
-  for (auto& p : m->corr)
-    if (p.d) hipFree(p.d);
-  for (int q = 0; q < 2; q++)
-    for (Field* p : {&m->ahead[q], &m->ahead_uv[q], &m->ahead_G[q], &m->ahead_colsum[q]})
-      if (p->d) hipFree(p->d);
-  if (m->uv_partials) hipFree(m->uv_partials);
   m->diag.release();
-  if (m->wbase) hipFree(m->wbase);
-  for (auto p : m->d_ord)
-    if (p) hipFree(p);
-  for (auto p : m->d_H)
-    if (p) hipFree(p);
-  for (auto p : m->d_wideH)
-    if (p) hipFree(p);
-  for (auto p : m->d_wideM)
-    if (p) hipFree(p);
-  for (auto p : m->d_bottom_flux)
-    if (p) hipFree(p);
-  for (auto p : m->d_atm)
-    if (p) hipFree(p);
-  for (auto p : m->d_tau)
-    if (p) hipFree(p);
-  for (auto p : m->d_top_flux)
-    if (p) hipFree(p);
-  for (auto p : m->d_implicit)
-    if (p) hipFree(p);
-  if (m->catke_b.d) hipFree(m->catke_b.d);
-  if (m->catke_scratch.d) hipFree(m->catke_scratch.d);
-  if (m->catke_src.d) hipFree(m->catke_src.d);
-  for (auto& F : m->uvc) if (F.d) hipFree(F.d);
-  for (auto& F : m->catke_gam) if (F.d) hipFree(F.d);
-  for (int a = 0; a < 2; a++) {
-    for (auto& w : m->wide[a])
-      if (w.d) hipFree(w.d);
-    if (m->wideG[a].d) hipFree(m->wideG[a].d);
-  }
-  if (m->wideBar[0].d) hipFree(m->wideBar[0].d);   // one allocation for all three
-  for (real* t : m->dev_tables) hipFree(t);
+  m->mem.release_all();
   resolve_profile(m);
   for (auto& ev : m->free_events) {
     hipEventDestroy(ev.a);
     hipEventDestroy(ev.b);
   }
-  if (m->side_stream) {
-    hipStreamSynchronize(m->side_stream);
-    hipStreamDestroy(m->side_stream);
-  }
-  if (m->baro_stream) {
-    hipStreamSynchronize(m->baro_stream);
-    hipStreamDestroy(m->baro_stream);
-  }
-  if (m->ev_fork) hipEventDestroy(m->ev_fork);
-  if (m->ev_join) hipEventDestroy(m->ev_join);
-  if (m->ev_baro) hipEventDestroy(m->ev_baro);
-  if (m->ev_mom) hipEventDestroy(m->ev_mom);
-  if (m->ev_ts) hipEventDestroy(m->ev_ts);
-  if (m->ev_tend) hipEventDestroy(m->ev_tend);
-  if (m->ev_strips) hipEventDestroy(m->ev_strips);
-  if (m->own_stream) hipStreamDestroy(m->own_stream);
+  for (hipStream_t* st : m->streams())
+    if (*st) {
+      hipStreamSynchronize(*st);
+      hipStreamDestroy(*st);
+    }
+  for (hipEvent_t* ev : m->events())
+    if (*ev) hipEventDestroy(*ev);
   delete m;
 }
 
@@ -3183,10 +3144,7 @@ gb25_status gb25_set_top_flux(gb25_model* m, gb25_field f, const void* host) {
     m->g.top_flux[q] = nullptr;   // (the array stays allocated for the next use)
     return GB25_OK;
   }
-  if (!m->d_top_flux[q]) {
-    HIPCHK(hipMalloc(&m->d_top_flux[q], n2 * sizeof(real)));
-    HIPCHK(hipMemset(m->d_top_flux[q], 0, n2 * sizeof(real)));
-  }
+  if (!m->d_top_flux[q]) HIPCHK(m->mem.alloc(&m->d_top_flux[q], n2 * sizeof(real), true));
   int32_t di[3];
   gb25_field_dims(m, f, 0, di);   // (the interior of the field's horizontal location: Ny rows of y faces on a folded grid)
   const int H = m->cfg.halo, nxi = di[0], nyi = di[1];
@@ -3203,10 +3161,7 @@ gb25_status gb25_set_bottom_drag(gb25_model* m, double Cd) {
   HIPCHK(hipStreamSynchronize(m->side_stream));
   const size_t n2 = (size_t)m->g.sx * m->g.sy_v;
   for (int q = 0; q < 2; q++) {
-    if (Cd != 0 && !m->d_bottom_flux[q]) {
-      HIPCHK(hipMalloc(&m->d_bottom_flux[q], n2 * sizeof(real)));
-      HIPCHK(hipMemset(m->d_bottom_flux[q], 0, n2 * sizeof(real)));
-    }
+    if (Cd != 0 && !m->d_bottom_flux[q]) HIPCHK(m->mem.alloc(&m->d_bottom_flux[q], n2 * sizeof(real), true));
     m->g.bottom_flux[q] = Cd != 0 ? m->d_bottom_flux[q] : nullptr;
   }
   m->bottom_drag = Cd;
@@ -3256,10 +3211,9 @@ gb25_status gb25_set_prescribed_atmosphere(gb25_model* m, gb25_atmosphere_field 
   HIPCHK(hipStreamSynchronize(m->side_stream));
   const size_t n2 = (size_t)m->g.sx * m->g.sy_c;
   if (!host) {
-    if (m->d_atm[f]) hipFree(m->d_atm[f]);
-    m->d_atm[f] = nullptr;
+    if (m->d_atm[f]) m->mem.release(m->d_atm[f]);
   } else {
-    if (!m->d_atm[f]) HIPCHK(hipMalloc(&m->d_atm[f], n2 * sizeof(double)));
+    if (!m->d_atm[f]) HIPCHK(m->mem.alloc(&m->d_atm[f], n2 * sizeof(double)));
     HIPCHK(hipMemcpy(m->d_atm[f], host, n2 * sizeof(double), hipMemcpyHostToDevice));
   }
   m->coupled = true;
@@ -3298,6 +3252,100 @@ gb25_status gb25_update_state(gb25_model* m) {
   return update_state_impl(m);
 }
 // ---- options: every switch of the library is a per-model option; nothing is read from the environment
+// One row per option: the member it reads and writes; the values it accepts -- lo <= v <= hi in steps of `step`, or with step 0 a
+// flag: any v, stored as v != 0 --; the message that refuses every other value; and, where setting it has a consequence, a hook
+// that runs between that check and the store.  A hook may refuse, and it may change what is stored.
+struct OptionRow {
+  gb25_option id;
+  int& (*at)(gb25_model*);
+  int lo, hi, step;
+  const char* refusal;
+  gb25_status (*hook)(gb25_model*, int32_t*);
+};
+static gb25_status opt_kernels(gb25_model* m, int32_t* v) {
+  if (*v == 1 && m->immersed) return fail(m, GB25_ERR_STATE, "the direct-stencil kernels know no immersed boundary");
+  return GB25_OK;
+}
+static gb25_status opt_pressure_precision(gb25_model*, int32_t* v) {
+  if (sizeof(real) == 8) *v = 64;   // (a Float64 model's own arithmetic IS fp64)
+  return GB25_OK;
+}
+static gb25_status opt_fold_fills(gb25_model* m, int32_t*) {
+  m->complete_fills_needed = 2;
+  return GB25_OK;
+}
+static gb25_status opt_substep_order(gb25_model* m, int32_t* v) {
+  if (*v == 1 && m->g.cv.on) return fail(m, GB25_ERR_STATE, "substep_order = 1 is built for the LatitudeLongitudeGrid kernels only (the oracle has it on every grid)");
+  return GB25_OK;
+}
+static gb25_status opt_fold_pivot_slaved(gb25_model* m, int32_t* v) {
+  if (*v != 0 && !m->g.cv.north_fold) return fail(m, GB25_ERR_STATE, "fold_pivot_slaved: this grid has no zipper fold");
+  if (*v != 0 && m->slab) return fail(m, GB25_ERR_STATE, "fold_pivot_slaved is built for the single domain only (a slab's eastern half of the pivot row belongs to its partner rank)");
+  return GB25_OK;
+}
+static gb25_status opt_catke_stale_e_halos(gb25_model* m, int32_t* v) {
+  if (*v != 0 && m->slab) return fail(m, GB25_ERR_STATE, "catke_stale_e_halos: a decomposition cannot leave the halos of e stale at its internal boundaries");
+  return GB25_OK;
+}
+static gb25_status opt_chunk_levels(gb25_model* m, int32_t* v) {
+  // the tendency kernels reach one chunk of levels plus its stencil planes with 32-bit byte offsets (gb25_create checks the
+  // default chunking): the chosen one must stay within that reach too
+  const double plane = (double)(m->Nx + 2 * m->cfg.halo) * (m->Ny + 2 * m->cfg.halo + 1);
+  const int kchunks = std::max(1, m->cfg.Nz / *v), klen = (m->cfg.Nz + kchunks - 1) / kchunks;
+  if (plane * (klen + 10) * sizeof(real) >= 2147483648.0)
+    return fail(m, GB25_ERR_INVALID_ARGUMENT, "chunks of %d levels (+ 10 stencil planes of %.3g elements) exceed the 2 GB the tendency "
+                "kernels address from one base: choose fewer levels per chunk", klen, plane);
+  m->colsum_valid = false;
+  return GB25_OK;
+}
+static gb25_status opt_immersed_kernels(gb25_model* m, int32_t* v) {
+  // 1: run the immersed-boundary kernel variants even where nothing is immersed (they must then give the bits of
+  // the plain ones: tests); 0: back to the choice the bottom makes
+  if (*v != 0 && m->kernel_gen == 1) return fail(m, GB25_ERR_STATE, "the direct-stencil kernels know no immersed boundary");
+  if (*v != 0 && !m->d_ord[0]) {
+    if (m->cfg.Nz > 254) return fail(m, GB25_ERR_INVALID_ARGUMENT, "an immersed boundary needs Nz <= 254");
+    if (gb25_status s = build_bottom(m, [](int, int) { return -1e30; })) return s;
+  }
+  for (int kb : m->kbot) *v = *v || (kb > 0 && kb < 255);
+  return GB25_OK;
+}
+#define OPT_AT(member) [](gb25_model* m) -> int& { return m->member; }
+#define OPT_FLAG 0, 0, 0, nullptr
+static const OptionRow kOptions[GB25_OPT_COUNT] = {
+    {GB25_OPT_KERNELS, OPT_AT(kernel_gen), 1, 2, 1, "GB25_OPT_KERNELS: 1 (direct stencil) or 2 (default)", opt_kernels},
+    {GB25_OPT_AB2_LOOKAHEAD, OPT_AT(ab2_ahead), 0, 2, 1, "GB25_OPT_AB2_LOOKAHEAD: 0, 1 or 2 (tracers only)", nullptr},
+    {GB25_OPT_SUBCYCLE_LOOKAHEAD, OPT_AT(baro_ahead), 0, 2, 1, "GB25_OPT_SUBCYCLE_LOOKAHEAD: 0, 1 (main stream) or 2 (own stream)", nullptr},
+    {GB25_OPT_SUBCYCLE_BLOCK, OPT_AT(baro_block), 1, 7, 2, "GB25_OPT_SUBCYCLE_BLOCK: 1, 3, 5 or 7 substeps per launch", nullptr},
+    {GB25_OPT_FILL_FUSED, OPT_AT(fill_fused), OPT_FLAG, nullptr},
+    {GB25_OPT_TWO_STREAMS, OPT_AT(two_streams), OPT_FLAG, nullptr},
+    {GB25_OPT_STORE_PRESSURE, OPT_AT(phy_pinned), OPT_FLAG, nullptr},
+    {GB25_OPT_SPLIT_TENDENCIES, OPT_AT(split_tendencies), OPT_FLAG, nullptr},
+    {GB25_OPT_PRESSURE_PRECISION, OPT_AT(pressure_bits), 32, 64, 32, "GB25_OPT_PRESSURE_PRECISION: 64 or 32", opt_pressure_precision},
+    {GB25_OPT_IMMERSED_KERNELS, OPT_AT(immersed), OPT_FLAG, opt_immersed_kernels},
+    {GB25_OPT_FOLD_FILLS, OPT_AT(fold_fills), OPT_FLAG, opt_fold_fills},
+    {GB25_OPT_LAZY_CORRECTOR, OPT_AT(lazy_corrector), OPT_FLAG, nullptr},
+    {GB25_OPT_MOMENTUM_CHUNK_LEVELS, OPT_AT(mom_chunk_levels), 6, 4096, 1, "chunk levels: 6 or more", opt_chunk_levels},
+    {GB25_OPT_TRACER_CHUNK_LEVELS, OPT_AT(trc_chunk_levels), 6, 4096, 1, "chunk levels: 6 or more", opt_chunk_levels},
+    {GB25_OPT_TRACERS_FIRST, OPT_AT(tracers_first), OPT_FLAG, nullptr},
+    {GB25_OPT_W_ON_THE_FLY, OPT_AT(w_fly), OPT_FLAG, nullptr},
+    {GB25_OPT_SUB_STREAM_PRIORITY, OPT_AT(sub_priority), OPT_FLAG, nullptr},
+    {GB25_OPT_SUBCYCLE_WHOLE, OPT_AT(baro_whole), OPT_FLAG, nullptr},
+    {GB25_OPT_EARLY_STRIPS, OPT_AT(early_strips), OPT_FLAG, nullptr},
+    {GB25_OPT_CATKE_STALE_E_HALOS, OPT_AT(catke_stale_e_halos), OPT_FLAG, opt_catke_stale_e_halos},
+    {GB25_OPT_COMM_TIMEOUT_SECONDS, OPT_AT(comm_timeout_s), 1, INT_MAX, 1, "comm_timeout_seconds: at least 1", nullptr},
+    {GB25_OPT_ROCTX_RANGES, OPT_AT(roctx_ranges), OPT_FLAG, nullptr},
+    {GB25_OPT_SUBSTEP_ORDER, OPT_AT(substep_order), 0, 1, 1, "substep_order: 0 (eta, then U, V) or 1 (U, V, then eta)", opt_substep_order},
+    {GB25_OPT_FOLD_PIVOT_SLAVED, OPT_AT(g.cv.pivot_slaved), OPT_FLAG, opt_fold_pivot_slaved},
+    {GB25_OPT_PRESSURE_FORM, OPT_AT(pressure_form), 0, 3, 1, "GB25_OPT_PRESSURE_FORM: 0 (the library's rule), 1 (tiles), 2 (one row per thread) or 3 (four rows per thread)", nullptr},
+    {GB25_OPT_SPECTRUM_TABLE, OPT_AT(spectrum_table_where), 0, 1, 1, "GB25_OPT_SPECTRUM_TABLE: 0 (the library's rule) or 1 (global memory)", nullptr},
+};
+#undef OPT_FLAG
+#undef OPT_AT
+static const OptionRow* option_row(gb25_option opt) {
+  for (const OptionRow& r : kOptions)
+    if (r.id == opt) return &r;
+  return nullptr;
+}
 gb25_status gb25_set_option(gb25_model* m, gb25_option opt, int32_t v) {
   CHECK_MODEL(m);
   if (gb25_status s = collective_guard(m, 5, (unsigned)opt, (double)v)) return s;
@@ -3308,133 +3356,20 @@ gb25_status gb25_set_option(gb25_model* m, gb25_option opt, int32_t v) {
   if (m->group) HIPCHK(m->group->sync_side());
   m->ahead_valid = m->ahead_uv_valid = m->ahead_baro_valid = false;
   m->tend_forkable = false;
-  switch (opt) {
-    case GB25_OPT_KERNELS:
-      if (v != 1 && v != 2) return fail(m, GB25_ERR_INVALID_ARGUMENT, "GB25_OPT_KERNELS: 1 (direct stencil) or 2 (default)");
-      if (v == 1 && m->immersed) return fail(m, GB25_ERR_STATE, "the direct-stencil kernels know no immersed boundary");
-      m->kernel_gen = v;
-      return GB25_OK;
-    case GB25_OPT_AB2_LOOKAHEAD:
-      if (v < 0 || v > 2) return fail(m, GB25_ERR_INVALID_ARGUMENT, "GB25_OPT_AB2_LOOKAHEAD: 0, 1 or 2 (tracers only)");
-      m->ab2_ahead = v;
-      return GB25_OK;
-    case GB25_OPT_SUBCYCLE_LOOKAHEAD:
-      if (v < 0 || v > 2) return fail(m, GB25_ERR_INVALID_ARGUMENT, "GB25_OPT_SUBCYCLE_LOOKAHEAD: 0, 1 (main stream) or 2 (own stream)");
-      m->baro_ahead = v;
-      return GB25_OK;
-    case GB25_OPT_SUBCYCLE_BLOCK:
-      if (v != 1 && v != 3 && v != 5 && v != 7)
-        return fail(m, GB25_ERR_INVALID_ARGUMENT, "GB25_OPT_SUBCYCLE_BLOCK: 1, 3, 5 or 7 substeps per launch");
-      m->baro_block = v;
-      return GB25_OK;
-    case GB25_OPT_FILL_FUSED: m->fill_fused = v != 0; return GB25_OK;
-    case GB25_OPT_TWO_STREAMS: m->two_streams = v != 0; return GB25_OK;
-    case GB25_OPT_STORE_PRESSURE: m->phy_pinned = v != 0; return GB25_OK;
-    case GB25_OPT_SPLIT_TENDENCIES: m->split_tendencies = v != 0; return GB25_OK;
-    case GB25_OPT_PRESSURE_PRECISION:
-      if (v != 32 && v != 64) return fail(m, GB25_ERR_INVALID_ARGUMENT, "GB25_OPT_PRESSURE_PRECISION: 64 or 32");
-      m->pressure_bits = (sizeof(real) == 8) ? 64 : v;   // (a Float64 model's own arithmetic IS fp64)
-      return GB25_OK;
-    case GB25_OPT_PRESSURE_FORM:
-      if (v < 0 || v > 3) return fail(m, GB25_ERR_INVALID_ARGUMENT, "GB25_OPT_PRESSURE_FORM: 0 (the library's rule), 1 (tiles), 2 (one row per thread) or 3 (four rows per thread)");
-      m->pressure_form = v;
-      return GB25_OK;
-    case GB25_OPT_SPECTRUM_TABLE:
-      if (v < 0 || v > 1) return fail(m, GB25_ERR_INVALID_ARGUMENT, "GB25_OPT_SPECTRUM_TABLE: 0 (the library's rule) or 1 (global memory)");
-      m->spectrum_table_where = v;
-      return GB25_OK;
-    case GB25_OPT_FOLD_FILLS:
-      m->fold_fills = v != 0;
-      m->complete_fills_needed = 2;
-      return GB25_OK;
-    case GB25_OPT_LAZY_CORRECTOR: m->lazy_corrector = v != 0; return GB25_OK;
-    case GB25_OPT_TRACERS_FIRST: m->tracers_first = v != 0; return GB25_OK;
-    case GB25_OPT_W_ON_THE_FLY: m->w_fly = v != 0; return GB25_OK;
-    case GB25_OPT_SUB_STREAM_PRIORITY: m->sub_priority = v != 0; return GB25_OK;
-    case GB25_OPT_SUBCYCLE_WHOLE: m->baro_whole = v != 0; return GB25_OK;
-    case GB25_OPT_EARLY_STRIPS: m->early_strips = v != 0; return GB25_OK;
-    case GB25_OPT_ROCTX_RANGES: m->roctx_ranges = v != 0; return GB25_OK;
-    case GB25_OPT_SUBSTEP_ORDER:
-      if (v != 0 && v != 1) return fail(m, GB25_ERR_INVALID_ARGUMENT, "substep_order: 0 (eta, then U, V) or 1 (U, V, then eta)");
-      if (v == 1 && m->g.cv.on) return fail(m, GB25_ERR_STATE, "substep_order = 1 is built for the LatitudeLongitudeGrid kernels only (the oracle has it on every grid)");
-      m->substep_order = v;
-      return GB25_OK;
-    case GB25_OPT_FOLD_PIVOT_SLAVED:
-      if (v != 0 && !m->g.cv.north_fold) return fail(m, GB25_ERR_STATE, "fold_pivot_slaved: this grid has no zipper fold");
-      if (v != 0 && m->slab) return fail(m, GB25_ERR_STATE, "fold_pivot_slaved is built for the single domain only (a slab's eastern half of the pivot row belongs to its partner rank)");
-      m->g.cv.pivot_slaved = v != 0 ? 1 : 0;
-      return GB25_OK;
-    case GB25_OPT_COMM_TIMEOUT_SECONDS:
-      if (v < 1) return fail(m, GB25_ERR_INVALID_ARGUMENT, "comm_timeout_seconds: at least 1");
-      m->comm_timeout_s = v;
-      return GB25_OK;
-    case GB25_OPT_CATKE_STALE_E_HALOS:
-      if (v != 0 && m->slab) return fail(m, GB25_ERR_STATE, "catke_stale_e_halos: a decomposition cannot leave the halos of e stale at its internal boundaries");
-      m->catke_stale_e_halos = v != 0;
-      return GB25_OK;
-    case GB25_OPT_MOMENTUM_CHUNK_LEVELS:
-    case GB25_OPT_TRACER_CHUNK_LEVELS:
-      if (v < 6 || v > 4096) return fail(m, GB25_ERR_INVALID_ARGUMENT, "chunk levels: 6 or more");
-      {
-        // the tendency kernels reach one chunk of levels plus its stencil planes with 32-bit byte offsets (gb25_create checks the
-        // default chunking): the chosen one must stay within that reach too
-        const double plane = (double)(m->Nx + 2 * m->cfg.halo) * (m->Ny + 2 * m->cfg.halo + 1);
-        const int kchunks = std::max(1, m->cfg.Nz / v), klen = (m->cfg.Nz + kchunks - 1) / kchunks;
-        if (plane * (klen + 10) * sizeof(real) >= 2147483648.0)
-          return fail(m, GB25_ERR_INVALID_ARGUMENT, "chunks of %d levels (+ 10 stencil planes of %.3g elements) exceed the 2 GB the tendency "
-                      "kernels address from one base: choose fewer levels per chunk", klen, plane);
-      }
-      (opt == GB25_OPT_MOMENTUM_CHUNK_LEVELS ? m->mom_chunk_levels : m->trc_chunk_levels) = v;
-      m->colsum_valid = false;
-      return GB25_OK;
-    case GB25_OPT_IMMERSED_KERNELS:
-      // 1: run the immersed-boundary kernel variants even where nothing is immersed (they must then give the bits of
-      // the plain ones: tests); 0: back to the choice the bottom makes
-      if (v != 0 && m->kernel_gen == 1) return fail(m, GB25_ERR_STATE, "the direct-stencil kernels know no immersed boundary");
-      if (v != 0 && !m->d_ord[0]) {
-        if (m->cfg.Nz > 254) return fail(m, GB25_ERR_INVALID_ARGUMENT, "an immersed boundary needs Nz <= 254");
-        if (gb25_status s = build_bottom(m, [](int, int) { return -1e30; })) return s;
-      }
-      {
-        bool any = false;
-        for (int kb : m->kbot) any = any || (kb > 0 && kb < 255);
-        m->immersed = any || v != 0;
-      }
-      return GB25_OK;
-    default: return fail(m, GB25_ERR_INVALID_ARGUMENT, "unknown option %d", (int)opt);
-  }
+  const OptionRow* row = option_row(opt);
+  if (!row) return fail(m, GB25_ERR_INVALID_ARGUMENT, "unknown option %d", (int)opt);
+  if (row->step == 0) v = v != 0;
+  else if (v < row->lo || v > row->hi || (v - row->lo) % row->step != 0) return fail(m, GB25_ERR_INVALID_ARGUMENT, "%s", row->refusal);
+  if (row->hook)
+    if (gb25_status s = row->hook(m, &v)) return s;
+  row->at(m) = v;
+  return GB25_OK;
 }
 gb25_status gb25_get_option(const gb25_model* m, gb25_option opt, int32_t* v) {
   if (!m || !v) return GB25_ERR_INVALID_ARGUMENT;
-  switch (opt) {
-    case GB25_OPT_KERNELS: *v = m->kernel_gen; break;
-    case GB25_OPT_AB2_LOOKAHEAD: *v = m->ab2_ahead; break;
-    case GB25_OPT_SUBCYCLE_LOOKAHEAD: *v = m->baro_ahead; break;
-    case GB25_OPT_SUBCYCLE_BLOCK: *v = m->baro_block; break;
-    case GB25_OPT_FILL_FUSED: *v = m->fill_fused; break;
-    case GB25_OPT_TWO_STREAMS: *v = m->two_streams; break;
-    case GB25_OPT_STORE_PRESSURE: *v = m->phy_pinned; break;
-    case GB25_OPT_SPLIT_TENDENCIES: *v = m->split_tendencies; break;
-    case GB25_OPT_PRESSURE_PRECISION: *v = m->pressure_bits; break;
-    case GB25_OPT_PRESSURE_FORM: *v = m->pressure_form; break;
-    case GB25_OPT_SPECTRUM_TABLE: *v = m->spectrum_table_where; break;
-    case GB25_OPT_IMMERSED_KERNELS: *v = m->immersed; break;
-    case GB25_OPT_FOLD_FILLS: *v = m->fold_fills; break;
-    case GB25_OPT_LAZY_CORRECTOR: *v = m->lazy_corrector; break;
-    case GB25_OPT_MOMENTUM_CHUNK_LEVELS: *v = m->mom_chunk_levels; break;
-    case GB25_OPT_TRACER_CHUNK_LEVELS: *v = m->trc_chunk_levels; break;
-    case GB25_OPT_TRACERS_FIRST: *v = m->tracers_first; break;
-    case GB25_OPT_W_ON_THE_FLY: *v = m->w_fly; break;
-    case GB25_OPT_SUB_STREAM_PRIORITY: *v = m->sub_priority; break;
-    case GB25_OPT_SUBCYCLE_WHOLE: *v = m->baro_whole; break;
-    case GB25_OPT_EARLY_STRIPS: *v = m->early_strips; break;
-    case GB25_OPT_CATKE_STALE_E_HALOS: *v = m->catke_stale_e_halos; break;
-    case GB25_OPT_COMM_TIMEOUT_SECONDS: *v = m->comm_timeout_s; break;
-    case GB25_OPT_ROCTX_RANGES: *v = m->roctx_ranges; break;
-    case GB25_OPT_SUBSTEP_ORDER: *v = m->substep_order; break;
-    case GB25_OPT_FOLD_PIVOT_SLAVED: *v = m->g.cv.pivot_slaved; break;
-    default: return GB25_ERR_INVALID_ARGUMENT;
-  }
+  const OptionRow* row = option_row(opt);
+  if (!row) return GB25_ERR_INVALID_ARGUMENT;
+  *v = row->at(const_cast<gb25_model*>(m));   // (read only: the rows name their members through one accessor)
   return GB25_OK;
 }
 

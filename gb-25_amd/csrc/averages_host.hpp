@@ -70,7 +70,7 @@ gb25_status gb25_averages_begin(gb25_model* m, int32_t groups, int32_t k_first, 
   int kc = 0;
   if (gb25_status s = diag_window(m, "gb25_averages_begin", k_first, k_count, m->cfg.Nz, "levels (k_first, k_count)", &kc)) return s;
   if (gb25_status s = diag_need_device(m, "gb25_averages_begin")) return s;
-  if (gb25_status s = diag_wait_for_model(m)) return s;
+  if (gb25_status s = wait_for_model(m)) return s;
   m->diag.release_averages();   // (a model that already has averages starts over)
   // one allocation: every active accumulator, then the array a normalized read-out is divided into (the largest quantity);
   // each part starts on a multiple of two doubles
@@ -110,7 +110,7 @@ gb25_status gb25_averages_accumulate(gb25_model* m, double weight) {
   const real* src[6];
   for (int q = 0; q < 6; q++)
     if (gb25_status s = diag_source(m, ids[q], &src[q])) return s;
-  if (gb25_status s = diag_wait_for_model(m)) return s;
+  if (gb25_status s = wait_for_model(m)) return s;
   const Grid& g = m->g;
   AvgArgs a;
   for (int q = 0; q < GB25_A_COUNT; q++) a.acc[q] = m->diag.avg_acc[q];

@@ -87,7 +87,7 @@ gb25_status gb25_get_class_sums(gb25_model* m, gb25_class_what what, gb25_class_
   if (gb25_status s = diag_source(m, GB25_S, &a.S)) return s;
   if (gb25_status s = class_buffer(m, B)) return s;
   if ((size_t)N > m->diag.class_rows) return fail(m, GB25_ERR_STATE, "gb25_get_class_sums: more rows than the model's buffer holds");
-  if (gb25_status s = diag_wait_for_model(m)) return s;
+  if (gb25_status s = wait_for_model(m)) return s;
   if (gb25_status s = moments_tables(m)) return s;
   double padded[CLASS_MAX_BINS];   // (alive until the stream is synchronised below)
   for (int e = 0; e < CLASS_MAX_BINS; e++) padded[e] = e < n_edges ? edges[e] : HUGE_VAL;

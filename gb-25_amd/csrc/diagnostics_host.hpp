@@ -4,7 +4,7 @@
 // diagnostics_kernels.hpp; the memory: DiagState (diagnostics_state.hpp), m->diag.  Nothing here writes model memory or a schedule
 // flag: the calls may sit between any two steps.  The first section holds what every diagnostic shares, averages_host.hpp,
 // classes_host.hpp and particles_host.hpp included: diag_need_device, diag_window, diag_download, diag_upload, diag_room_for /
-// diag_alloc_zeroed, diag_wait_for_model, diag_source (is_folded, has_north_wall and first_wet_level: gb25_api.hip, beside is_2d).
+// diag_alloc_zeroed, diag_source; wait_for_model: gb25_api.hip (is_folded, has_north_wall and first_wet_level: gb25_api.hip, beside is_2d).
 #pragma once
 
 namespace {
@@ -80,15 +80,6 @@ gb25_status diag_scratch(gb25_model* m) {
   return GB25_OK;
 }
 inline void* diag_result_slot(gb25_model* m, int q) { return (char*)m->diag.scratch + (m->diag.scratch_records + q) * DIAG_RECORD; }
-
-// the whole model is quiet (what gb25_synchronize waits for)
-gb25_status diag_wait_for_model(gb25_model* m) {
-  HIPCHK(hipStreamSynchronize(m->stream));
-  HIPCHK(hipStreamSynchronize(m->side_stream));
-  if (m->baro_stream) HIPCHK(hipStreamSynchronize(m->baro_stream));
-  if (m->group) HIPCHK(m->group->sync_side());
-  return GB25_OK;
-}
 
 // The array that holds what gb25_get_field(id) would return, without moving anything: previous_velocities are read where they
 // live (prev_uv_src), a stale pHY' is recomputed from the T, S it belongs to (the launch is filed under GB25_K_DIAGNOSTICS).
@@ -339,7 +330,7 @@ gb25_status derived_run(gb25_model* m, gb25_derived q, double param, int k0, int
   if (gb25_status s = diag_source(m, vel ? GB25_U : GB25_T, &a)) return s;
   if (gb25_status s = diag_source(m, vel ? GB25_V : GB25_S, &b)) return s;
   if (gb25_status s = derived_scratch(m)) return s;
-  if (gb25_status s = diag_wait_for_model(m)) return s;
+  if (gb25_status s = wait_for_model(m)) return s;
   if (gb25_status s = moments_tables(m)) return s;
   int32_t e[3];
   derived_extents(m, q, e);
@@ -441,7 +432,7 @@ gb25_status gb25_get_transport(gb25_model* m, gb25_transport_faces faces, gb25_t
   if (gb25_status s = diag_source(m, GB25_S, &S)) return s;
   if (gb25_status s = transport_buffer(m)) return s;
   if ((size_t)N > m->diag.transport_lines) return fail(m, GB25_ERR_STATE, "gb25_get_transport: more lines than the model's buffer holds");
-  if (gb25_status s = diag_wait_for_model(m)) return s;
+  if (gb25_status s = wait_for_model(m)) return s;
   if (gb25_status s = moments_tables(m)) return s;
   const Grid& g = m->g;
   TransportTables tab;
@@ -531,7 +522,7 @@ gb25_status gb25_get_field_levels(gb25_model* m, gb25_field f, int32_t k_first, 
   if (gb25_status s = derived_scratch(m)) return s;
   const size_t n = (size_t)b.bx * b.by * kc;
   if (n > m->diag.derived_elems - m->diag.derived_plane) return fail(m, GB25_ERR_STATE, "gb25_get_field_levels: the levels need more room than the model's result array has");
-  if (gb25_status s = diag_wait_for_model(m)) return s;
+  if (gb25_status s = wait_for_model(m)) return s;
   b.origin += b.plane * k_first;
   b.bz = kc;
   real* out = m->diag.derived + m->diag.derived_plane;
@@ -557,7 +548,7 @@ gb25_status gb25_get_field_stats(gb25_model* m, gb25_field f, int include_halos,
   if (gb25_status s = diag_scratch(m)) return s;
   if (gb25_status s = diag_box(m, f, include_halos, &b)) return s;
   if (gb25_status s = diag_check_box(m, b)) return s;
-  if (gb25_status s = diag_wait_for_model(m)) return s;
+  if (gb25_status s = wait_for_model(m)) return s;
   return diag_stats_of(m, f, src, b, include_halos, out);
 }
 
@@ -583,7 +574,7 @@ gb25_status gb25_compare_field(gb25_model* m, gb25_field f, int include_halos, c
   ob.pitch = other_dims[0];
   ob.plane = (long long)other_dims[0] * other_dims[1];
   ob.origin = o[0] + ob.pitch * o[1] + ob.plane * o[2];
-  if (gb25_status s = diag_wait_for_model(m)) return s;
+  if (gb25_status s = wait_for_model(m)) return s;
   const long long nb = diag_blocks(b);
   {
     Timed t(m, GB25_K_DIAGNOSTICS);
@@ -621,7 +612,7 @@ gb25_status gb25_get_state_monitor(gb25_model* m, gb25_state_monitor* out) {
   if (gb25_status s = diag_scratch(m)) return s;
   for (int q = 0; q < 6; q++)
     if (gb25_status s = diag_check_box(m, b[q])) return s;
-  if (gb25_status s = diag_wait_for_model(m)) return s;
+  if (gb25_status s = wait_for_model(m)) return s;
   {
     Timed t(m, GB25_K_DIAGNOSTICS);
     for (int q = 0; q < 6; q++)
@@ -668,7 +659,7 @@ gb25_status gb25_integrate_field(gb25_model* m, gb25_field f, gb25_sum_shape sha
                 (long long)want, b.by, b.bz, (long long)count);
   if (gb25_status s = moments_buffer(m)) return s;
   if (gb25_status s = moments_check_box(m, b)) return s;
-  if (gb25_status s = diag_wait_for_model(m)) return s;
+  if (gb25_status s = wait_for_model(m)) return s;
   if (gb25_status s = moments_tables(m)) return s;
   {
     Timed t(m, GB25_K_DIAGNOSTICS);
@@ -692,7 +683,7 @@ gb25_status gb25_get_budget(gb25_model* m, gb25_budget* out) {
   if (gb25_status s = moments_buffer(m)) return s;
   for (int q = 0; q < MOMENTS_SLOTS; q++)
     if (gb25_status s = moments_check_box(m, b[q])) return s;
-  if (gb25_status s = diag_wait_for_model(m)) return s;
+  if (gb25_status s = wait_for_model(m)) return s;
   if (gb25_status s = moments_tables(m)) return s;
   {
     Timed t(m, GB25_K_DIAGNOSTICS);
@@ -718,7 +709,7 @@ gb25_status gb25_field_device_ptr_readonly(gb25_model* m, gb25_field f, const vo
   if (!m || !dev) return GB25_ERR_INVALID_ARGUMENT;
   const real* src = nullptr;
   if (gb25_status s = diag_source(m, f, &src)) return s;
-  if (gb25_status s = diag_wait_for_model(m)) return s;
+  if (gb25_status s = wait_for_model(m)) return s;
   *dev = src;
   if (device_dims) {
     device_dims[0] = m->f[f].nx; device_dims[1] = m->f[f].ny; device_dims[2] = m->f[f].nz;

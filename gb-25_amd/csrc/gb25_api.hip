@@ -14,6 +14,7 @@
 #include "particle_kernels.hpp"
 #include "spectrum_kernels.hpp"
 #include "diagnostics_state.hpp"
+#include "validity.hpp"
 
 #include <cmath>
 #include <cstdarg>
@@ -88,25 +89,17 @@ struct gb25_model {
   Field pp[3];                   // ping-pong partners of eta, U, V
   Field dpx, dpy;                // p'(i)-p'(i-1), p'(j)-p'(j-1), differenced in fp64 by k_compute_p, stored fp32
   Field colsum[2];               // column integrals of u, v after the AB2 update (consumed by the corrector)
-  bool colsum_valid = false;
-  // AB2 look-ahead (kernels_v2.hpp, Ab2Ahead): the tracer tendency kernel also writes T, S of the next time level
-  // into `ahead`; ab2_step! adopts them by pointer exchange when dt, chi and every input are still the same.
+  // The look-aheads' buffers, adopted by pointer exchange; whether each may be trusted: `valid` (validity.hpp).  T, S of the next time
+  // level, written by the tracer tendency kernel (Ab2Ahead) ...
   Field ahead[2];
-  bool ahead_valid = false, ptr_exposed = false;
-  real ahead_dt = 0, ahead_chi = 0;
-  // ... and the momentum kernel does the same for u, v (UvAhead): partner buffers of u, v, of G.U, G.V and of the
-  // corrector's column integrals, plus the per-chunk partial sums the kernel leaves for k_ab2_velocities_finish
+  // ... u, v, G.U, G.V, the corrector's column integrals and the partial sums for k_ab2_velocities_finish, by the momentum kernel (UvAhead) ...
   Field ahead_uv[2], ahead_G[2], ahead_colsum[2];
   real* uv_partials = nullptr;
-  bool ahead_uv_valid = false;
-  real ahead_uv_dt = 0, ahead_uv_chi = 0;
-  // ... and once G.U, G.V of the next step exist (momentum look-ahead), so does everything its split-explicit
-  // sub-cycle needs: it runs on the side stream beside the tracer tendency kernel (latency-bound next to
-  // issue-bound) into partner buffers of eta, U, V and of the filtered state, adopted like the others.
+  // ... and the split-explicit sub-cycle of the next step runs from those into partners of eta, U, V and of the filtered state
   Field pp2[3];                      // second scratch set: the sub-cycle never writes the arrays it starts from
   Field ahead_eta[3], ahead_bar[3];  // partners of eta, U, V and of eta_bar, U_bar, V_bar
   real* bars_ahead = nullptr;        // (the three partners of the averages are one allocation, like `bars`)
-  bool ahead_baro_valid = false;
+  Validity<real> valid;
   // pHY' is a diagnostic: inside a composite step only its differences are stored (4 of the kernel's 20 B/cell
   // saved) and the field is recomputed when the host asks for it; pinned to "always stored" once its pointer is out
   bool phy_stale = false;
@@ -162,7 +155,6 @@ struct gb25_model {
   bool strips_issued = false;
   int early_strips = 1;              // option EARLY_STRIPS
   int tracers_first = 1;
-  bool tend_forkable = false;       // the last tendency evaluation was a composite step's, tracers first: ev_tend covers both kernels
   int two_streams = 1;              // option TWO_STREAMS = 0: strictly sequential phases on one stream
   bool profile = false;
   int profile_only = -1;             // >= 0: time this kernel id alone (keeps the event records out of the other launches)
@@ -181,12 +173,11 @@ struct gb25_model {
   // single periodic domain: the last writers of u, v (corrector), T, S (tracer look-ahead) and eta, U, V (last barotropic
   // launch) also write the halo cells the fills derive from them, and the fill launches leave the step.  Halo cells
   // deeper than one layer in y / z are static while stepping, so their x images only need the complete fills of the two
-  // steps (one per buffer of each alternating pair) that follow a host write.
+  // steps (one per buffer of each alternating pair) that follow a host write (valid.complete_fills_needed).
   int n_cu = 256;                    // compute units of the device
   int fold_fills = 1;
   bool composite = false;            // inside gb25_time_step / gb25_loop (the phase entry points leave halos alone, as the
                                      // reference's phases do: there the producers do not fold)
-  int complete_fills_needed = 2;
   bool ahead_ts_folded = false, ahead_eta_folded = false, last_baro_folded = false;
   int split_tendencies = 1;          // slab of a decomposition: interior tile columns before the x-halo bundle has arrived
   int baro_whole = 1;                // narrow slab: the whole sub-cycle in one launch (option SUBCYCLE_WHOLE)
@@ -211,7 +202,6 @@ struct gb25_model {
   int tracer_order = 5;              // tracer_advection = WENO(order = 5 | 7)
   double bottom_drag = 0.0;          // quadratic bottom drag coefficient (0: none); the two flux arrays behind Grid.bottom_flux
   real* d_bottom_flux[2] = {nullptr, nullptr};
-  bool halo_colsum_valid = false;    // slab: the x-halo columns of colsum hold their owner's integrals (packed with group 0)
   // the corrector applied inside its consumers (k_corrector_2d): du, dv of the current step; while uv_lazy is set, u and
   // v in memory lack them (only between the steps of one composite call: gb25_loop applies them before it returns)
   Field corr[2];
@@ -256,7 +246,6 @@ struct gb25_model {
   // it left hold u, v as they were at the last compute_diffusivities!, halos included.  materialize_prev_uv brings them home.
   int prev_uv_src = 0;
   int catke_stale_e_halos = 0;       // option CATKE_STALE_E_HALOS
-  bool n2_fresh = false;             // (unused since N^2 = g (alpha dzT - beta dzS) has a kernel of its own)
   Field catke_gam[2];                // Nz > 64: the elimination factors of the streamed implicit solve
   real* d_implicit[2] = {nullptr, nullptr};   // elimination tables of the implicit solve for (u, v) and (T, S): lo | 1/beta | gamma
   double implicit_key[2][2] = {{0, 0}, {0, 0}};   // the (dt, K) they were built for
@@ -936,7 +925,7 @@ gb25_status build_bottom(gb25_model* m, ZB zb) {
     if ((s = upload(wf.data(), wf.size() * sizeof(real), (void**)&m->d_wideH[0]))) return s;
     if ((s = upload(wc.data(), wc.size() * sizeof(real), (void**)&m->d_wideH[1]))) return s;
   }
-  m->ahead_valid = m->ahead_uv_valid = m->ahead_baro_valid = false;
+  m->valid.void_lookaheads();
   return GB25_OK;
 }
 // gaussian_islands(lambda, phi) = zb + h (mtn1 + mtn2), zb = z[1], h = -zb + 100; mountains 5 degrees wide at (70 E,
@@ -1148,12 +1137,10 @@ gb25_status compute_p_impl(gb25_model* m, int i_first = INT_MIN, int i_last = IN
     hipLaunchKernelGGL(k_pressure_differences, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, m->stream, g,
                        m->f[GB25_PHY].d, m->dpx.d, m->dpy.d, n);
     m->phy_stale = false;
-    m->n2_fresh = false;
     LAUNCHCHK();
     return GB25_OK;
   }
   real* n2 = nullptr;   // (CATKE's N^2 is SeawaterBuoyancy's dz_b -- alpha dzT - beta dzS -- not a difference of buoyancies: k_catke_n2)
-  m->n2_fresh = false;
   const bool write_p = !may_skip_p || m->phy_pinned;
   m->phy_stale = !write_p;
   if (i_first == INT_MIN) {
@@ -1251,7 +1238,7 @@ struct MomentumKernels {   // k_momentum_tendencies_v5
 // part: see momentum_impl.  WFLY: w on the fly in a lazy step, or beside the corrector's sweep (memory holds the corrected
 // velocities, only w is not read) -- in the passes over the whole domain
 std::array<bool, MomentumKernels::n> momentum_flags(const gb25_model* m, int part) {
-  const bool ahead = m->ab2_ahead == 1 && !m->ptr_exposed, curv = m->g.cv.on;
+  const bool ahead = m->ab2_ahead == 1 && !m->valid.ptr_exposed, curv = m->g.cv.on;
   return {ahead, m->immersed || curv, curv, m->uv_lazy, m->bottom_drag != 0, ahead && m->w_fly_now && (m->uv_lazy || part == 0)};
 }
 
@@ -1270,7 +1257,7 @@ struct TracerKernels {   // k_tracer_tendencies_v5; the flag O7: ORD = 7 (WENO(o
 // WCORR: the corrector through the tracer kernel -- it adds du, dv as it loads (LAZY) and writes the corrected u, v; the halo
 // cells of the next T, S are then left to the fill (no FOLD)
 std::array<bool, TracerKernels::n> tracer_flags(const gb25_model* m) {
-  const bool ahead = m->ab2_ahead && !m->ptr_exposed, curv = m->g.cv.on, wcorr = m->uv_corr_pending;
+  const bool ahead = m->ab2_ahead && !m->valid.ptr_exposed, curv = m->g.cv.on, wcorr = m->uv_corr_pending;
   return {ahead, m->immersed || curv, ahead && producers_fold(m) && !wcorr, curv, m->uv_lazy || wcorr, m->tracer_order == 7,
           ahead && m->w_fly_now, wcorr};
 }
@@ -1294,8 +1281,7 @@ gb25_status materialize_prev_uv(gb25_model* m);
 gb25_status momentum_impl(gb25_model* m, int part = 0) {
   const Grid& g = m->g;
   int nbx, nb;
-  m->tend_forkable = false;
-  if (part != 2) m->ahead_uv_valid = m->ahead_baro_valid = false;   // look-aheads made from the previous tendencies are void
+  m->valid.tendency_kernel_runs(part != 2);   // look-aheads made from the previous tendencies are void
   if (m->kernel_gen >= 2) {
     Timed t(m, GB25_K_GU);   // the fused G_u + G_v kernel is accounted under the "gu" timer
     nbx = (g.Nx + V2_TX - 1) / V2_TX;
@@ -1367,9 +1353,7 @@ gb25_status momentum_impl(gb25_model* m, int part = 0) {
       dim3 b(64, 4);
       hipLaunchKernelGGL(k_ab2_velocities_finish, grid2(g.Nx, v_rows(g), b), b, 0, m->stream, g, m->uv_partials, kchunks,
                          nx.plane2, m->ahead_G[0].d, m->ahead_G[1].d, m->ahead_colsum[0].d, m->ahead_colsum[1].d);
-      m->ahead_uv_valid = true;
-      m->ahead_uv_dt = dt;
-      m->ahead_uv_chi = chi;
+      m->valid.record_velocity_lookahead(dt, chi);
     }
     LAUNCHCHK();
     return GB25_OK;
@@ -1395,7 +1379,7 @@ gb25_status momentum_impl(gb25_model* m, int part = 0) {
 gb25_status tracers_impl(gb25_model* m) {
   const Grid& g = m->g;
   int nbx, nb;
-  m->tend_forkable = false;
+  m->valid.tendency_kernel_runs(false);
   if (m->kernel_gen >= 2) {
     Timed t(m, GB25_K_TRACERS);
     nbx = (g.Nx + V3_OUT - 1) / V3_OUT;
@@ -1426,9 +1410,7 @@ gb25_status tracers_impl(gb25_model* m) {
                        m->f[GB25_V].d, m->f[GB25_W].d, m->f[GB25_T].d, m->f[GB25_S].d, m->f[GB25_GN_T].d,
                        m->f[GB25_GN_S].d, nbx, kchunks, nb, nx, lz);
     LAUNCHCHK();
-    m->ahead_valid = ahead;
-    m->ahead_dt = nx.dt;
-    m->ahead_chi = (real)m->cfg.chi;
+    m->valid.record_tracer_lookahead(ahead, nx.dt, (real)m->cfg.chi);
     if (m->uv_corr_pending) {
       // the arrays the kernel wrote ARE u, v from here on (the uncorrected ones become the scratch pair of the next step), and
       // their halo cells come from the ordinary fill -- y / z layers, the rows beyond a zipper fold, the periodic x copy
@@ -1438,7 +1420,7 @@ gb25_status tracers_impl(gb25_model* m) {
     }
     return GB25_OK;
   }
-  m->ahead_valid = false;   // only the packed kernel looks ahead
+  m->valid.void_tracer_lookahead();   // only the packed kernel looks ahead
   if (m->immersed || g.cv.on) return fail(m, GB25_ERR_STATE, "the direct-stencil kernels (GB25_OPT_KERNELS = 1) know neither immersed boundaries nor curvilinear grids");
   if (g.top_flux[2] || g.top_flux[3]) return fail(m, GB25_ERR_STATE, "the direct-stencil kernels (GB25_OPT_KERNELS = 1) know no flux boundary conditions");
   tile_grid(g, &nbx, &nb);
@@ -1511,7 +1493,7 @@ gb25_status implicit_vertical_impl(gb25_model* m, int kind, real dt) {
     dim3 b(64, 4);
     hipLaunchKernelGGL(kern, dim3((g.Nx + 63) / 64, ((kind == 0 ? v_rows(g) : g.Ny) + 3) / 4, 2), b, 0, m->stream, g, A, kchunks);
     LAUNCHCHK();
-    if (kind == 0) m->colsum_valid = true;
+    if (kind == 0) m->valid.record_colsums();
     return GB25_OK;
   }
   // deeper columns: the column and the per-thread elimination factors in LDS
@@ -1529,7 +1511,7 @@ gb25_status implicit_vertical_impl(gb25_model* m, int kind, real dt) {
   hipLaunchKernelGGL(kern, dim3((g.Nx + T - 1) / T, kind == 0 ? v_rows(g) : g.Ny, 2), dim3(T), lds, m->stream, g, a, b, kind, K, K,
                      dt, sa, sb, kchunks);
   LAUNCHCHK();
-  if (kind == 0) m->colsum_valid = true;
+  if (kind == 0) m->valid.record_colsums();
   return GB25_OK;
 }
 
@@ -1545,7 +1527,7 @@ gb25_status materialize_prev_uv(gb25_model* m) {
 }
 gb25_status ab2_velocities_impl(gb25_model* m, real dt, real chi) {
   const Grid& g = m->g;
-  if (m->ahead_uv_valid && dt == m->ahead_uv_dt && chi == m->ahead_uv_chi) {
+  if (m->valid.velocities_adoptable(dt, chi)) {
     // the last momentum evaluation already advanced u and v with exactly these parameters: adopt its buffers
     // (closure = CATKE: the buffers given up hold the velocities of the last compute_diffusivities!: its previous_velocities)
     if (m->prev_uv_src == 2)
@@ -1556,12 +1538,12 @@ gb25_status ab2_velocities_impl(gb25_model* m, real dt, real chi) {
       std::swap(m->f[GB25_GN_BT_U + q].d, m->ahead_G[q].d);
       std::swap(m->colsum[q].d, m->ahead_colsum[q].d);
     }
-    m->colsum_valid = true;
-    m->ahead_uv_valid = false;
+    m->valid.record_colsums();
+    m->valid.void_velocity_lookahead_alone();
     if (m->catke) return catke_implicit_impl(m, 0, dt);
     return implicit_vertical_impl(m, 0, dt);
   }
-  m->ahead_uv_valid = false;
+  m->valid.void_velocity_lookahead_alone();
   if (m->prev_uv_src == 1)   // (u, v are about to be advanced in place)
     if (gb25_status s_ = materialize_prev_uv(m)) return s_;
   dim3 b(64, 4);
@@ -1570,7 +1552,7 @@ gb25_status ab2_velocities_impl(gb25_model* m, real dt, real chi) {
                      m->f[GB25_GN_U].d, m->f[GB25_GM_U].d, m->f[GB25_GN_V].d, m->f[GB25_GM_V].d,
                      m->f[GB25_GN_BT_U].d, m->f[GB25_GN_BT_V].d, m->colsum[0].d, m->colsum[1].d, dt, chi,
                      mom_kchunks(m));   // the momentum kernel's chunking (momentum_impl)
-  m->colsum_valid = true;
+  m->valid.record_colsums();
   LAUNCHCHK();
   if (m->catke) return catke_implicit_impl(m, 0, dt);
   return implicit_vertical_impl(m, 0, dt);
@@ -1580,15 +1562,15 @@ gb25_status ab2_velocities_impl(gb25_model* m, real dt, real chi) {
 gb25_status catke_tracers_impl(gb25_model* m, real dt, real chi) { return catke_implicit_impl(m, 1, dt, chi); }
 gb25_status ab2_tracers_impl(gb25_model* m, real dt, real chi) {
   const Grid& g = m->g;
-  if (m->ahead_valid && dt == m->ahead_dt && chi == m->ahead_chi) {
+  if (m->valid.tracers_adoptable(dt, chi)) {
     // the last tendency evaluation already advanced T and S with exactly these parameters
     std::swap(m->f[GB25_T].d, m->ahead[0].d);
     std::swap(m->f[GB25_S].d, m->ahead[1].d);
-    m->ahead_valid = false;
+    m->valid.void_tracer_lookahead();
     if (m->catke) return catke_tracers_impl(m, dt, chi);
     return implicit_vertical_impl(m, 1, dt);
   }
-  m->ahead_valid = false;
+  m->valid.void_tracer_lookahead();
   Timed t(m, GB25_K_AB2_TRACERS);
   const real C1 = real(1.5) + chi, C2 = real(0.5) + chi;
   size_t off = (size_t)g.H * g.pl_c;
@@ -1856,7 +1838,7 @@ gb25_status barotropic_impl(gb25_model* m, real dt, bool ahead = false, const In
 // that now carry the G^n name.  (closure = CATKE: G^-.e is written by the e step itself -- cache_previous_tendencies! skips e)
 void cache_previous_tendencies(gb25_model* m) {
   for (int q = 0; q < 4; q++) std::swap(m->f[GB25_GN_U + q].d, m->f[GB25_GM_U + q].d);
-  m->ahead_valid = m->ahead_uv_valid = m->ahead_baro_valid = false;   // the look-aheads used the tendency pairs as they were before
+  m->valid.void_lookaheads();   // the look-aheads used the tendency pairs as they were before
 }
 // the corrector inside its consumers: du, dv (k_corrector_2d) on columns i0 + [0, ni) (from skip_from on: + skip), rows jr0 + [0, nj)
 gb25_status corrector_2d_impl(gb25_model* m, dim3 b, int i0, int ni, int skip_from, int skip, int jr0, int nj) {
@@ -1894,12 +1876,12 @@ gb25_status corrector_impl(gb25_model* m, bool use_colsum = false, int part = 0)
       if (!ext) return GB25_OK;
       i0 = -g.H; ni = 2 * g.H; skip_from = 0; skip = g.Nx;
     }
-    const bool cs = use_colsum && m->colsum_valid && part != 2;
+    const bool cs = use_colsum && m->valid.colsum_valid && part != 2;
     const bool fold = producers_fold(m) && m->composite;
     // one thread per cell where the column integrals are at hand: the own columns of a slab, and its x-halo columns when
     // the integrals came with the 3-D bundle (group 0 carries the owner's; marching 16 columns x Ny threads up 48 levels
     // for them was 36 us of latency on the critical path of a 180-column rank)
-    const bool cells_halo = m->slab && part == 2 && use_colsum && m->halo_colsum_valid;
+    const bool cells_halo = m->slab && part == 2 && use_colsum && m->valid.halo_colsum_valid;
     const bool cells = (m->slab && part == 1 && cs) || cells_halo;
     auto launch = [&](int i0_, int ni_, int skf, int sk, int jr0, int nj, int jskf, int jsk) {
       if (cells) {
@@ -1921,7 +1903,7 @@ gb25_status corrector_impl(gb25_model* m, bool use_colsum = false, int part = 0)
     LAUNCHCHK();
   }
   if (part == 2) return GB25_OK;
-  m->colsum_valid = false;
+  m->valid.void_colsums();
   cache_previous_tendencies(m);
   return GB25_OK;
 }
@@ -2012,7 +1994,7 @@ gb25_status catke_tke_step_impl(gb25_model* m) {
   // (prev_uv_src; 0.8 GB of copies per step at 1440x720x48 otherwise).  A rank of a decomposition, whose stages write the
   // partner buffers ahead of this one, and models without the look-ahead: D2D copies behind the kernel that read them.
   m->prev_uv_src = 1;
-  if (m->slab || m->ab2_ahead != 1 || m->ptr_exposed || !m->two_streams)
+  if (m->slab || m->ab2_ahead != 1 || m->valid.ptr_exposed || !m->two_streams)
     if (gb25_status s_ = materialize_prev_uv(m)) return s_;
   const double dt_since = m->time - m->catke_prev_time;
   m->catke_prev_time = m->time;
@@ -2119,7 +2101,7 @@ gb25_status catke_implicit_impl(gb25_model* m, int mode, real dt, real chi, int 
   const int rows = mode == 0 ? v_rows(g) : g.Ny;   // (with the zipper fold v has the fold line too)
   hipLaunchKernelGGL(kern, dim3((g.Nx + 63) / 64, (rows + 3) / 4, nz), b, 0, m->stream, g, A);
   LAUNCHCHK();
-  if (mode == 0) m->colsum_valid = true;
+  if (mode == 0) m->valid.record_colsums();
   return GB25_OK;
 }
 
@@ -2171,7 +2153,7 @@ gb25_status update_state_impl(gb25_model* m) {
 
 gb25_status ab2_step_impl(gb25_model* m, double dt, int euler) {
   gb25_status s;
-  m->ahead_baro_valid = false;   // this route always runs the sub-cycle itself
+  m->valid.void_subcycle_lookahead();   // this route always runs the sub-cycle itself
   const real chi = euler ? -real(0.5) : (real)m->cfg.chi;
   if ((s = ab2_local_impl(m, (real)dt, chi))) return s;
   Halo2 hG = halo2_G(m);
@@ -2203,7 +2185,7 @@ gb25_status materialize_uv(gb25_model* m, bool need_w = true) {
 // (slab_lazy_ok, below)
 inline bool lazy_instances_ok(const gb25_model* m) {
   return m->lazy_corrector && !m->coupled && m->bottom_drag == 0 && m->tracer_order == 5 && m->two_streams && !m->immersed &&
-         !m->g.cv.on && m->kernel_gen >= 2 && m->ab2_ahead == 1 && !m->ptr_exposed && m->pressure_bits == 64;
+         !m->g.cv.on && m->kernel_gen >= 2 && m->ab2_ahead == 1 && !m->valid.ptr_exposed && m->pressure_bits == 64;
 }
 // ... a single domain: the look-aheads able to write their halos; `more` (time_step_impl): the step is one of a composite call
 // (gb25_loop), which materialises u, v, w when it returns
@@ -2221,7 +2203,7 @@ inline bool wfly_sweep_ok(const gb25_model* m) {
   // (the sweep leaves corrected velocities in memory: the similarity-theory fluxes of a coupled model, the quadratic bottom drag and
   // WENO(order = 7) tracers -- the data-free climate model -- read them like anything else; instances of the three tendency kernels exist)
   return m->w_fly && m->baro_ahead != 0 && !m->slab && m->two_streams && m->kernel_gen >= 2 &&
-         m->ab2_ahead == 1 && !m->ptr_exposed && m->nu == 0 && m->kappa == 0 &&
+         m->ab2_ahead == 1 && !m->valid.ptr_exposed && m->nu == 0 && m->kappa == 0 &&
          // (closure = CATKE: the implicit solve of u, v that follows the AB2 update rewrites the look-ahead's chunk sums with
          // those of the velocities it leaves: catke_implicit_impl, ImplicitVarFields::P; e is advected by a kernel that carries w too)
          chunkings_match(m);
@@ -2264,38 +2246,36 @@ gb25_status time_step_impl(gb25_model* m, int euler, bool more = false) {
   const real chi = euler ? -real(0.5) : (real)m->cfg.chi;
   hipStream_t main = m->stream, side = m->side_stream;
   // ---- AB2 of u, v: normally the adoption of the look-ahead (a pointer exchange on the host, no kernel)
-  const bool adopted = m->ahead_uv_valid && (real)dt == m->ahead_uv_dt && chi == m->ahead_uv_chi;
-  const bool baro_adopted = adopted && m->ahead_baro_valid;   // (made from that very look-ahead, same dt)
-  m->ahead_baro_valid = false;
+  const bool adopted = m->valid.velocities_adoptable((real)dt, chi);
+  const bool baro_adopted = adopted && m->valid.ahead_baro_valid;   // (made from that very look-ahead, same dt)
+  m->valid.void_subcycle_lookahead();
   // The corrector inside its consumers: when everything this step needs was made ahead of time (u, v, the sub-cycle) and
   // another step follows, no sweep over u and v at all -- a 2-D kernel leaves du, dv and w, the tendency kernels add them.
-  const bool lazy = more && adopted && baro_adopted && m->complete_fills_needed == 0 && lazy_corrector_ok(m);
+  const bool lazy = more && adopted && baro_adopted && m->valid.complete_fills_needed == 0 && lazy_corrector_ok(m);
   // ... or the sweep stays and only w moves into the tendency kernels (the look-ahead's chunk integrals must be this step's)
   // ... or the tracer kernel applies it and writes the corrected velocities (grids with a bottom, curvilinear, folded) ...
-  const bool lazy_t = !lazy && more && adopted && baro_adopted && m->complete_fills_needed == 0 && lazy_through_tracers_ok(m);
-  const bool wfly_sweep = !lazy && !lazy_t && more && adopted && m->complete_fills_needed == 0 && wfly_sweep_ok(m);
+  const bool lazy_t = !lazy && more && adopted && baro_adopted && m->valid.complete_fills_needed == 0 && lazy_through_tracers_ok(m);
+  const bool wfly_sweep = !lazy && !lazy_t && more && adopted && m->valid.complete_fills_needed == 0 && wfly_sweep_ok(m);
   if (!lazy && (s = materialize_uv(m, !(wfly_sweep || lazy_t)))) return s;   // (the stand-alone kernels below expect corrected velocities)
   if ((s = ab2_velocities_impl(m, (real)dt, chi))) return s;
   Halo2 hG = halo2_G(m);
   // the sub-cycle reads G.U, G.V at interior points only (periodic wrap and walls are in the kernel): their halo
   // fill is for the state's sake and leaves the critical path when no kernel on this stream produced them
   if (!adopted && (s = fill_halos_2d(m, hG))) return s;
-  const bool ts_adopted = m->ahead_valid && (real)dt == m->ahead_dt && chi == m->ahead_chi;
+  const bool ts_adopted = m->valid.tracers_adoptable((real)dt, chi);
   // Everything the tracer branch reads was complete when the previous step's momentum kernel had finished (both
   // look-aheads adopted, the tracer kernel ran before the momentum kernel, no closure whose implicit solve sits in between):
   // the branch then starts behind THAT kernel -- beside this step's sub-cycle look-ahead, which is still in the queue of
   // the main stream -- and not behind everything the main stream holds.  (Not across the zipper fold: the fill of G.U, G.V
   // rewrites the eastern half of the fold line, which the sub-cycle reads.)
-  const bool early_fork = m->tend_forkable && adopted && ts_adopted && !m->catke && m->nu == 0 && m->kappa == 0 && !m->coupled &&
-                          !m->g.cv.north_fold;
-  m->tend_forkable = false;
+  const bool early_fork = m->valid.take_tend_forkable() && adopted && ts_adopted && !m->catke && m->nu == 0 && m->kappa == 0 &&
+                          !m->coupled && !m->g.cv.north_fold;
   HIPCHK(hipEventRecord(m->ev_fork, main));
   HIPCHK(hipStreamWaitEvent(side, early_fork ? m->ev_tend : m->ev_fork, 0));
   // ---- tracer branch (side stream)
   m->stream = side;
   // (complete fills for the two steps after a host write, one per buffer of each alternating pair: see fold_fills)
-  const bool complete = m->complete_fills_needed > 0;
-  if (complete) m->complete_fills_needed -= 1;
+  const bool complete = m->valid.take_complete_fill();
   s = ab2_tracers_impl(m, (real)dt, chi);
   // y/z/x halos of T, S -- unless the look-ahead that was just adopted wrote them itself
   if (!s && (complete || !(ts_adopted && m->ahead_ts_folded))) s = fill_halos_impl(m, true, false, 1, 2);
@@ -2334,7 +2314,7 @@ gb25_status time_step_impl(gb25_model* m, int euler, bool more = false) {
     Timed t(m, GB25_K_CORRECTOR);
     if ((s = corrector_2d_impl(m, b, 0, g.Nx, INT_MAX, 0, 0, g.Ny + 1))) return s;
     m->uv_lazy = true;
-    m->colsum_valid = false;
+    m->valid.void_colsums();
     m->w_fly_now = m->w_fly && chunkings_match(m);
     if (m->w_fly_now) {
       if ((s = w_bases_impl(m, b, -2, g.Nx + 4, INT_MAX, 0))) return s;
@@ -2357,7 +2337,7 @@ gb25_status time_step_impl(gb25_model* m, int euler, bool more = false) {
       hc.n = 2;
       if ((s = fill_halos_2d(m, hc))) return s;
     }
-    m->colsum_valid = false;
+    m->valid.void_colsums();
     m->w_fly_now = true;
     if ((s = w_bases_impl(m, b, -2, g.Nx + 4, INT_MAX, 0))) return s;
     m->w_stale = true;
@@ -2401,9 +2381,9 @@ gb25_status time_step_impl(gb25_model* m, int euler, bool more = false) {
   if ((s = momentum_impl(m))) return s;
   if (tracers_first) {
     HIPCHK(hipEventRecord(m->ev_tend, main));
-    m->tend_forkable = true;
+    m->valid.tendencies_forkable();
   }
-  if (m->baro_ahead && m->ahead_uv_valid && !m->ptr_exposed) {
+  if (m->valid.velocities_ready(m->baro_ahead)) {
     // G.U, G.V of the next step exist now, and with them everything its split-explicit sub-cycle needs: it runs here,
     // into the partner buffers, and leaves the head of the next step (where the corrector waits for it).
     if (m->baro_ahead == 2) {
@@ -2415,7 +2395,7 @@ gb25_status time_step_impl(gb25_model* m, int euler, bool more = false) {
       HIPCHK(hipEventRecord(m->ev_mom, main));
       HIPCHK(hipStreamWaitEvent(m->baro_stream, m->ev_mom, 0));
       m->stream = m->baro_stream;
-      s = barotropic_impl(m, m->ahead_uv_dt, true);
+      s = barotropic_impl(m, m->valid.ahead_uv_dt, true);
       m->ahead_eta_folded = m->last_baro_folded;
       m->stream = main;
       if (s) return s;
@@ -2424,10 +2404,10 @@ gb25_status time_step_impl(gb25_model* m, int euler, bool more = false) {
     } else {
       // ... on the main stream, between the momentum and the tracer tendencies: three launches of 60 us with the GPU to
       // themselves, no cross-stream dependency at all.
-      if ((s = barotropic_impl(m, m->ahead_uv_dt, true))) return s;
+      if ((s = barotropic_impl(m, m->valid.ahead_uv_dt, true))) return s;
       m->ahead_eta_folded = m->last_baro_folded;
     }
-    m->ahead_baro_valid = true;
+    m->valid.record_subcycle_lookahead();
   }
   if (!tracers_first && (s = tracers_impl(m))) return s;
   return atmosphere_ocean_fluxes_impl(m);   // (a coupled model: the fluxes the NEXT evaluation of the tendencies sees)
@@ -2485,10 +2465,7 @@ gb25_status quiesce_for_grid_change(gb25_model* m) {
   HIPCHK(hipStreamSynchronize(m->own_stream));
   HIPCHK(hipStreamSynchronize(m->side_stream));
   if (m->baro_stream) HIPCHK(hipStreamSynchronize(m->baro_stream));
-  m->ahead_valid = m->ahead_uv_valid = m->ahead_baro_valid = false;
-  m->colsum_valid = m->halo_colsum_valid = false;
-  m->tend_forkable = false;
-  m->complete_fills_needed = 2;
+  m->valid.grid_changes();
   m->implicit_key[0][0] = m->implicit_key[1][0] = -1.0;   // (the elimination tables of a closure hold the old spacings)
   return GB25_OK;
 }
@@ -2497,6 +2474,15 @@ gb25_status quiesce_for_grid_change(gb25_model* m) {
 
 #include "slab_step.hpp"
 #include "state_io.hpp"
+
+// everything a model has in flight finishes (quiesce_for_grid_change and implicit_tables wait for stream lists of their own)
+static gb25_status wait_for_model(gb25_model* m) {
+  HIPCHK(hipStreamSynchronize(m->stream));
+  HIPCHK(hipStreamSynchronize(m->side_stream));
+  if (m->baro_stream) HIPCHK(hipStreamSynchronize(m->baro_stream));
+  if (m->group) HIPCHK(m->group->sync_side());
+  return GB25_OK;
+}
 
 // =============================================================================================
 extern "C" {
@@ -2756,11 +2742,7 @@ gb25_status gb25_use_own_stream(gb25_model* m) {
 }
 gb25_status gb25_synchronize(gb25_model* m) {
   CHECK_MODEL(m);
-  HIPCHK(hipStreamSynchronize(m->stream));
-  HIPCHK(hipStreamSynchronize(m->side_stream));
-  if (m->baro_stream) HIPCHK(hipStreamSynchronize(m->baro_stream));   // the sub-cycle look-ahead may still be running there
-  if (m->group) HIPCHK(m->group->sync_side());   // (a slab's runs on the second stream of its context)
-  return GB25_OK;
+  return wait_for_model(m);
 }
 
 gb25_status gb25_field_dims(const gb25_model* m, gb25_field id, int include_halos, int32_t d[3]) {
@@ -2782,17 +2764,13 @@ gb25_status gb25_field_dims(const gb25_model* m, gb25_field id, int include_halo
 static gb25_status copy_field(gb25_model* m, gb25_field id, real* host, int include_halos, bool to_device) {
   if (!m || id < 0 || id >= GB25_FIELD_COUNT || !host) return GB25_ERR_INVALID_ARGUMENT;
   if (!m->f[id].d) return fail(m, GB25_ERR_INVALID_ARGUMENT, "this model has no such field (closure = CATKEVerticalDiffusivity() only)");
-  if (to_device && (id == GB25_U || id == GB25_V)) m->colsum_valid = false;  // cached column integrals are stale
+  if (to_device && (id == GB25_U || id == GB25_V)) m->valid.void_colsums();  // cached column integrals are stale
   if (m->uv_lazy)   // (only after a composite call that failed half-way: memory must hold the corrected velocities)
     if (gb25_status s = materialize_uv(m)) return s;
   if (gb25_status s = materialize_prev_uv(m)) return s;   // (CATKE's previous velocities into their fields before the host reads or writes)
   Field& F = m->f[id];
-  HIPCHK(hipStreamSynchronize(m->stream));
-  if (to_device) {   // a look-ahead may still be reading the old values
-    HIPCHK(hipStreamSynchronize(m->side_stream));
-    if (m->baro_stream) HIPCHK(hipStreamSynchronize(m->baro_stream));
-    if (m->group) HIPCHK(m->group->sync_side());
-  }
+  if (!to_device) HIPCHK(hipStreamSynchronize(m->stream));
+  else if (gb25_status s = wait_for_model(m)) return s;   // a look-ahead may still be reading the old values
   int32_t d[3];
   gb25_field_dims(m, id, include_halos, d);
   if (include_halos && d[1] == F.ny) {
@@ -2824,16 +2802,16 @@ static gb25_status widen_phy(gb25_model* m) {   // the host uploaded pHY': rebui
 // T and S alternate between two buffers (AB2 look-ahead).  Whatever the host writes into one, halos included, goes
 // into the partner too, so that the halo layers no kernel ever rewrites are the same in both.
 static gb25_status mirror_tracers(gb25_model* m) {
-  m->ahead_valid = false;
-  m->complete_fills_needed = 2;
+  m->valid.void_tracer_lookahead();
+  m->valid.complete_fills_owed();
   for (int q = 0; q < 2; q++)
     HIPCHK(hipMemcpyAsync(m->ahead[q].d, m->f[GB25_T + q].d, m->f[GB25_T + q].elems() * sizeof(real),
                           hipMemcpyDeviceToDevice, m->stream));
   return GB25_OK;
 }
 static gb25_status mirror_velocities(gb25_model* m) {   // u and v alternate between two buffers likewise
-  m->ahead_uv_valid = false;
-  m->complete_fills_needed = 2;
+  m->valid.void_velocity_lookahead_alone();
+  m->valid.complete_fills_owed();
   for (int q = 0; q < 2; q++)
     HIPCHK(hipMemcpyAsync(m->ahead_uv[q].d, m->f[GB25_U + q].d, m->f[GB25_U + q].elems() * sizeof(real),
                           hipMemcpyDeviceToDevice, m->stream));
@@ -2851,12 +2829,9 @@ gb25_status gb25_set_field(gb25_model* m, gb25_field f, const void* host, int in
   if (s == GB25_OK && m->immersed && (f == GB25_U || f == GB25_V || f == GB25_T || f == GB25_S || f == GB25_BT_U || f == GB25_BT_V))
     s = mask_impl(m);   // set!(model, ...) masks what it has set (as Oceananigans' set! does on an immersed grid)
   if (s == GB25_OK) {
-    m->ahead_valid = m->ahead_uv_valid = m->ahead_baro_valid = false;   // any input of the look-aheads may have changed
-    m->complete_fills_needed = 2;
-    if (f == GB25_T || f == GB25_S) {
-      s = mirror_tracers(m);
-      m->n2_fresh = false;
-    }
+    m->valid.void_lookaheads();   // any input of the look-aheads may have changed
+    m->valid.complete_fills_owed();
+    if (f == GB25_T || f == GB25_S) s = mirror_tracers(m);
     if (f == GB25_U || f == GB25_V) s = mirror_velocities(m);
     if (s == GB25_OK && f >= GB25_ETA && f <= GB25_V_BAR) {   // eta, U, V and the filtered state alternate likewise
       Field& P = (f <= GB25_BT_V) ? m->ahead_eta[f - GB25_ETA] : m->ahead_bar[f - GB25_ETA_BAR];
@@ -2884,8 +2859,7 @@ gb25_status gb25_field_device_ptr(gb25_model* m, gb25_field id, void** dev) {
       (id >= GB25_ETA && id <= GB25_GN_BT_V)) {
     // the host can now write prognostic fields or their tendencies behind our back: no more look-ahead for this
     // model, u, v, T, S stay in the buffers whose addresses are handed out
-    m->ptr_exposed = true;
-    m->ahead_valid = m->ahead_uv_valid = m->ahead_baro_valid = false;
+    m->valid.pointer_handed_out();
   }
   if (id == GB25_PHY) {
     m->phy_pinned = true;
@@ -2958,8 +2932,8 @@ gb25_status gb25_set_vertical_diffusivity(gb25_model* m, double nu, double kappa
   if (gb25_status s = collective_guard(m, 7, 1, kappa)) return s;
   m->nu = nu;
   m->kappa = kappa;
-  m->ahead_valid = false;   // (a look-ahead of T, S written with its halos predates the solve)
-  if (!m->slab) m->complete_fills_needed = 2;
+  m->valid.void_tracer_lookahead();   // (a look-ahead of T, S written with its halos predates the solve)
+  if (!m->slab) m->valid.complete_fills_owed();
   return GB25_OK;
 }
 gb25_status gb25_set_closure_catke(gb25_model* m, int32_t on) {
@@ -2967,8 +2941,7 @@ gb25_status gb25_set_closure_catke(gb25_model* m, int32_t on) {
   if (gb25_status s = collective_guard(m, 8, (unsigned)(on != 0), 0.0)) return s;
   if (on && (m->nu != 0 || m->kappa != 0)) return fail(m, GB25_ERR_STATE, "one closure at a time: the vertical diffusivity is set");
   if (on && m->cfg.Nz < 2) return fail(m, GB25_ERR_INVALID_ARGUMENT, "CATKE needs at least two levels (it lives on the faces between them)");
-  HIPCHK(hipStreamSynchronize(m->stream));
-  HIPCHK(hipStreamSynchronize(m->side_stream));
+  if (gb25_status s = wait_for_model(m)) return s;
   if (on && !m->f[GB25_E].d) {
     const int H = m->cfg.halo, sx = m->Nx + 2 * H, sy = m->Ny + 2 * H, nz = m->cfg.Nz + 2 * H;
     gb25_status s;
@@ -2982,9 +2955,8 @@ gb25_status gb25_set_closure_catke(gb25_model* m, int32_t on) {
   }
   if (gb25_status s_ = materialize_prev_uv(m)) return s_;   // (while the closure still says where they are)
   m->catke = on != 0;
-  m->n2_fresh = false;
-  m->ahead_valid = false;
-  m->complete_fills_needed = 2;
+  m->valid.void_tracer_lookahead();
+  m->valid.complete_fills_owed();
   return GB25_OK;
 }
 void gb25_default_catke_parameters(gb25_catke_parameters* p) {
@@ -3004,7 +2976,7 @@ gb25_status gb25_set_catke_parameters(gb25_model* m, const gb25_catke_parameters
     return fail(m, GB25_ERR_INVALID_ARGUMENT, "CATKE parameters: CRid, the damping time scale, the minimum convective buoyancy flux and the minimum TKE must be positive");
   if (gb25_status s = collective_guard(m, 10, 0, p->Cb)) return s;
   m->catke_par = *p;
-  m->ahead_valid = m->ahead_uv_valid = m->ahead_baro_valid = false;
+  m->valid.void_lookaheads();
   return GB25_OK;
 }
 gb25_status gb25_get_catke_parameters(const gb25_model* m, gb25_catke_parameters* p) {
@@ -3024,7 +2996,7 @@ gb25_status gb25_mask_immersed_fields(gb25_model* m) {
   CHECK_MODEL(m);
   gb25_status s = mask_impl(m);
   if (s == GB25_OK && m->immersed) {   // the partner buffers of the look-aheads follow
-    m->ahead_valid = m->ahead_uv_valid = m->ahead_baro_valid = false;
+    m->valid.void_lookaheads();
     if ((s = mirror_tracers(m))) return s;
     s = mirror_velocities(m);
   }
@@ -3135,9 +3107,8 @@ gb25_status gb25_set_top_flux(gb25_model* m, gb25_field f, const void* host) {
   const int q = f == GB25_U ? 0 : f == GB25_V ? 1 : f == GB25_T ? 2 : f == GB25_S ? 3 : -1;
   if (q < 0) return fail(m, GB25_ERR_INVALID_ARGUMENT, "top flux boundary conditions exist for u, v, T, S");
   if (gb25_status s = collective_guard(m, 6, (unsigned)f, host ? 1.0 : 0.0)) return s;
-  HIPCHK(hipStreamSynchronize(m->stream));
-  HIPCHK(hipStreamSynchronize(m->side_stream));
-  m->ahead_valid = m->ahead_uv_valid = m->ahead_baro_valid = false;
+  if (gb25_status s = wait_for_model(m)) return s;
+  m->valid.void_lookaheads();
   const Field& F = m->f[f];
   const size_t n2 = (size_t)F.nx * F.ny;
   if (!host) {
@@ -3157,15 +3128,14 @@ gb25_status gb25_set_bottom_drag(gb25_model* m, double Cd) {
   CHECK_MODEL(m);
   if (!(Cd >= 0)) return fail(m, GB25_ERR_INVALID_ARGUMENT, "the bottom drag coefficient must be >= 0");
   if (gb25_status s = collective_guard(m, 11, 0, Cd)) return s;
-  HIPCHK(hipStreamSynchronize(m->stream));
-  HIPCHK(hipStreamSynchronize(m->side_stream));
+  if (gb25_status s = wait_for_model(m)) return s;
   const size_t n2 = (size_t)m->g.sx * m->g.sy_v;
   for (int q = 0; q < 2; q++) {
     if (Cd != 0 && !m->d_bottom_flux[q]) HIPCHK(m->mem.alloc(&m->d_bottom_flux[q], n2 * sizeof(real), true));
     m->g.bottom_flux[q] = Cd != 0 ? m->d_bottom_flux[q] : nullptr;
   }
   m->bottom_drag = Cd;
-  m->ahead_valid = m->ahead_uv_valid = m->ahead_baro_valid = false;
+  m->valid.void_lookaheads();
   return GB25_OK;
 }
 gb25_status gb25_set_tracer_advection_order(gb25_model* m, int32_t order) {
@@ -3175,8 +3145,8 @@ gb25_status gb25_set_tracer_advection_order(gb25_model* m, int32_t order) {
   if (order == 7 && m->kernel_gen < 2) return fail(m, GB25_ERR_STATE, "the direct-stencil kernels (GB25_OPT_KERNELS = 1) know WENO(order = 5) only");
   if (gb25_status s = collective_guard(m, 12, (unsigned)order, 0.0)) return s;
   m->tracer_order = order;
-  m->ahead_valid = m->ahead_uv_valid = m->ahead_baro_valid = false;
-  m->complete_fills_needed = 2;
+  m->valid.void_lookaheads();
+  m->valid.complete_fills_owed();
   return GB25_OK;
 }
 gb25_status gb25_get_tracer_advection_order(const gb25_model* m, int32_t* order) {
@@ -3207,8 +3177,7 @@ gb25_status gb25_set_prescribed_atmosphere(gb25_model* m, gb25_atmosphere_field 
   CHECK_MODEL(m);
   if ((int)f < 0 || (int)f >= GB25_ATM_COUNT) return fail(m, GB25_ERR_INVALID_ARGUMENT, "atmosphere field %d", (int)f);
   if (gb25_status s = collective_guard(m, 9, (unsigned)f, host ? 1.0 : 0.0)) return s;
-  HIPCHK(hipStreamSynchronize(m->stream));
-  HIPCHK(hipStreamSynchronize(m->side_stream));
+  if (gb25_status s = wait_for_model(m)) return s;
   const size_t n2 = (size_t)m->g.sx * m->g.sy_c;
   if (!host) {
     if (m->d_atm[f]) m->mem.release(m->d_atm[f]);
@@ -3218,14 +3187,14 @@ gb25_status gb25_set_prescribed_atmosphere(gb25_model* m, gb25_atmosphere_field 
   }
   m->coupled = true;
   for (auto p : m->d_atm) m->coupled = m->coupled && p != nullptr;
-  m->ahead_valid = m->ahead_uv_valid = m->ahead_baro_valid = false;
+  m->valid.void_lookaheads();
   return GB25_OK;
 }
 gb25_status gb25_compute_atmosphere_ocean_fluxes(gb25_model* m) {
   CHECK_MODEL(m);
   if (!m->coupled) return fail(m, GB25_ERR_STATE, "no prescribed atmosphere: set all of its fields first (gb25_set_prescribed_atmosphere)");
   if (gb25_status s = materialize_uv(m)) return s;
-  m->ahead_valid = m->ahead_uv_valid = m->ahead_baro_valid = false;   // (made from tendencies with the old fluxes)
+  m->valid.void_lookaheads();   // (made from tendencies with the old fluxes)
   return atmosphere_ocean_fluxes_impl(m);
 }
 gb25_status gb25_compute_tendencies(gb25_model* m) {
@@ -3239,7 +3208,7 @@ gb25_status gb25_ab2_step(gb25_model* m, double dt, int euler) {
   if (m->slab) return fail(m, GB25_ERR_STATE, "gb25_ab2_step: phase-by-phase driving is for single-domain models");
   // ab2_step! leaves every halo as it is; look-ahead buffers written with their halos (fold_fills) are therefore not
   // adopted here: the stand-alone kernels give the same interior bits
-  if (m->fold_fills) m->ahead_valid = false;
+  if (m->fold_fills) m->valid.void_tracer_lookahead();
   return ab2_step_impl(m, dt, euler);
 }
 gb25_status gb25_correct_velocities_and_cache_previous_tendencies(gb25_model* m, double) {
@@ -3271,7 +3240,7 @@ static gb25_status opt_pressure_precision(gb25_model*, int32_t* v) {
   return GB25_OK;
 }
 static gb25_status opt_fold_fills(gb25_model* m, int32_t*) {
-  m->complete_fills_needed = 2;
+  m->valid.complete_fills_owed();
   return GB25_OK;
 }
 static gb25_status opt_substep_order(gb25_model* m, int32_t* v) {
@@ -3295,7 +3264,7 @@ static gb25_status opt_chunk_levels(gb25_model* m, int32_t* v) {
   if (plane * (klen + 10) * sizeof(real) >= 2147483648.0)
     return fail(m, GB25_ERR_INVALID_ARGUMENT, "chunks of %d levels (+ 10 stencil planes of %.3g elements) exceed the 2 GB the tendency "
                 "kernels address from one base: choose fewer levels per chunk", klen, plane);
-  m->colsum_valid = false;
+  m->valid.void_colsums();
   return GB25_OK;
 }
 static gb25_status opt_immersed_kernels(gb25_model* m, int32_t* v) {
@@ -3350,12 +3319,8 @@ gb25_status gb25_set_option(gb25_model* m, gb25_option opt, int32_t v) {
   CHECK_MODEL(m);
   if (gb25_status s = collective_guard(m, 5, (unsigned)opt, (double)v)) return s;
   // a switch may change which buffers carry the next time level: whatever is in flight finishes, every look-ahead is void
-  HIPCHK(hipStreamSynchronize(m->stream));
-  HIPCHK(hipStreamSynchronize(m->side_stream));
-  if (m->baro_stream) HIPCHK(hipStreamSynchronize(m->baro_stream));
-  if (m->group) HIPCHK(m->group->sync_side());
-  m->ahead_valid = m->ahead_uv_valid = m->ahead_baro_valid = false;
-  m->tend_forkable = false;
+  if (gb25_status s = wait_for_model(m)) return s;
+  m->valid.option_changes();
   const OptionRow* row = option_row(opt);
   if (!row) return fail(m, GB25_ERR_INVALID_ARGUMENT, "unknown option %d", (int)opt);
   if (row->step == 0) v = v != 0;
@@ -3584,7 +3549,7 @@ static gb25_status loop_impl(gb25_model* m, int32_t n) {
 
 gb25_status gb25_lookahead_state(const gb25_model* m, int32_t* velocities_ready, int32_t* subcycle_adopted) {
   if (!m) return GB25_ERR_INVALID_ARGUMENT;
-  if (velocities_ready) *velocities_ready = (m->ahead_uv_valid && m->baro_ahead && !m->ptr_exposed) ? 1 : 0;
+  if (velocities_ready) *velocities_ready = m->valid.velocities_ready(m->baro_ahead) ? 1 : 0;
   if (subcycle_adopted) *subcycle_adopted = m->baro_adopted ? 1 : 0;
   return GB25_OK;
 }

@@ -35,7 +35,7 @@ gb25_status gb25_particles_begin(gb25_model* m, int64_t capacity) {
   if (!m) return GB25_ERR_INVALID_ARGUMENT;
   if (capacity <= 0) return fail(m, GB25_ERR_INVALID_ARGUMENT, "gb25_particles_begin: capacity = %lld must be > 0", (long long)capacity);
   if (gb25_status s = diag_need_device(m, "gb25_particles_begin")) return s;
-  if (gb25_status s = diag_wait_for_model(m)) return s;
+  if (gb25_status s = wait_for_model(m)) return s;
   // one allocation, every part on a multiple of 16 bytes: two copies of the state (3 doubles, 4 ints per particle), the sample
   // array, the per-wave counter slots and their totals, the kbot table
   const int H = m->cfg.halo;
@@ -140,7 +140,7 @@ gb25_status gb25_particles_advance(gb25_model* m, double dt, int32_t substeps) {
   const real* src[3];
   for (int q = 0; q < 3; q++)
     if (gb25_status s = diag_source(m, ids[q], &src[q])) return s;
-  if (gb25_status s = diag_wait_for_model(m)) return s;
+  if (gb25_status s = wait_for_model(m)) return s;
   if (gb25_status s = particles_tables(m)) return s;
   gb25_particles_info& I = m->diag.part_info;
   unsigned long long totals[GB25_PC_COUNT] = {};
@@ -205,7 +205,7 @@ gb25_status gb25_particles_sample(gb25_model* m, gb25_field f, double* out, int6
   if (count > 0 && !out) return fail(m, GB25_ERR_INVALID_ARGUMENT, "gb25_particles_sample: out is NULL");
   const real* src = nullptr;
   if (gb25_status s = diag_source(m, f, &src)) return s;
-  if (gb25_status s = diag_wait_for_model(m)) return s;
+  if (gb25_status s = wait_for_model(m)) return s;
   if (count == 0) return GB25_OK;
   const Grid& g = m->g;
   {

@@ -320,9 +320,9 @@ gb25_status slab_stage(gb25_model* m, int stage, int euler) {
   if (stage == 0) {
     // AB2 update of u,v,T,S + barotropic forcing, then the y/z boundary layers of the 3-D bundle so that its packed
     // x columns (group 0) can travel WHILE the own columns are corrected
-    const bool uv_adopted = m->ahead_uv_valid && (real)dt == m->ahead_uv_dt && chi == m->ahead_uv_chi;
-    m->baro_adopted = uv_adopted && m->ahead_baro_valid;
-    m->ahead_baro_valid = false;
+    const bool uv_adopted = m->valid.velocities_adoptable((real)dt, chi);
+    m->baro_adopted = uv_adopted && m->valid.ahead_baro_valid;
+    m->valid.void_subcycle_lookahead();
     // The corrector inside its consumers (as on a single domain, time_step_impl): when everything this step needs was made
     // ahead of time, no sweep over u and v -- 2-D kernels leave du, dv (own columns in stage 2, halo columns in stage 3 from the
     // column integrals the bundle carries) and the kernels that read u, v add them.  Memory holds the uncorrected velocities
@@ -366,7 +366,7 @@ gb25_status slab_stage(gb25_model* m, int stage, int euler) {
     // Folded grid: stage 1 / 5 end after the interior copy (the image rows beyond the pivot row travel next: group 8),
     // stage 16 / 56 do the rest.
     const bool ahead = stage == 5 || stage == 56, second_half = stage == 16 || stage == 56;
-    if (ahead && !m->ahead_uv_valid) return fail(m, GB25_ERR_STATE, "stage 5 without a velocity look-ahead");
+    if (ahead && !m->valid.ahead_uv_valid) return fail(m, GB25_ERR_STATE, "stage 5 without a velocity look-ahead");
     if (!ahead && m->baro_adopted) return fail(m, GB25_ERR_STATE, "stage 1 after stage 0 adopted the sub-cycle");
     std::vector<Piece> ps;
     int nc = 0;
@@ -390,13 +390,13 @@ gb25_status slab_stage(gb25_model* m, int stage, int euler) {
     const InteriorCopies* own = two_halves ? nullptr : &C;
     bool layers_done = false;
     if (ahead) {
-      if ((s = barotropic_impl(m, m->ahead_uv_dt, true, own, &layers_done))) return s;
+      if ((s = barotropic_impl(m, m->valid.ahead_uv_dt, true, own, &layers_done))) return s;
       Halo2 h2{};
       for (int q = 0; q < 3; q++) { h2.p[q] = m->ahead_eta[q].d; h2.is_v[q] = q == 2; }
       h2.n = 3;
       // y layer, x halo columns included: the widened sub-cycle computed those like the neighbour did (no group 4)
       if (!layers_done && (s = fill_halos_impl(m, false, true, 2, 3, nullptr, true, &h2))) return s;
-      m->ahead_baro_valid = true;
+      m->valid.record_subcycle_lookahead();
       return GB25_OK;
     }
     if ((s = barotropic_impl(m, (real)dt, false, own, &layers_done))) return s;
@@ -413,14 +413,14 @@ gb25_status slab_stage(gb25_model* m, int stage, int euler) {
       // (stage 20 did the corrector's part)
     } else if (m->step_lazy) {
       m->lazy_head_done = stage == 20;
-      if (!m->colsum_valid) return fail(m, GB25_ERR_STATE, "internal: a lazy step without the column integrals of u, v");
+      if (!m->valid.colsum_valid) return fail(m, GB25_ERR_STATE, "internal: a lazy step without the column integrals of u, v");
       dim3 b(64, 4);
       Timed t(m, GB25_K_CORRECTOR);
       // (a rank of a 2-D decomposition has no interior pass: du, dv and the chunk bases of w over its whole extended range at
       // once, in stage 3, when every halo is in)
       if (m->Ry == 1 && (s = corrector_2d_impl(m, b, 0, g.Nx, INT_MAX, 0, 0, g.Ny + 1))) return s;
       m->uv_lazy = true;
-      if (m->Ry == 1) m->colsum_valid = false;
+      if (m->Ry == 1) m->valid.void_colsums();
       if (m->w_fly_now && m->Ry == 1) {
         // chunk bases of w on the columns [0, Nx - 2] (their u faces are own columns), before the interior momentum pass
         // overwrites the chunk sums they are made from
@@ -479,14 +479,14 @@ gb25_status slab_stage(gb25_model* m, int stage, int euler) {
       if (m->step_lazy) {
         // du, dv of the x halo columns: the neighbours' column integrals came with the bundle, the new U, V of those columns
         // from the widened sub-cycle; their y/z layers of u, v arrived filled -- nothing else to do
-        if (!m->halo_colsum_valid) return fail(m, GB25_ERR_STATE, "internal: a lazy step without the neighbours' column integrals");
+        if (!m->valid.halo_colsum_valid) return fail(m, GB25_ERR_STATE, "internal: a lazy step without the neighbours' column integrals");
         if (m->Ry > 1) {
           // 2-D decomposition: everything at once -- own cells, halo columns, halo rows of the open sides (corners included)
           dim3 b(64, 4);
           // rows: from the southern halo rows (or row 0) to the last northern halo row of the cell-shaped arrays (or the wall face)
           const int hs = m->ys_open ? g.H : 0, nj = hs + g.Ny + (m->yn_open ? g.H : 1);
           if ((s = corrector_2d_impl(m, b, -g.H, g.Nx + 2 * g.H, INT_MAX, 0, -hs, nj))) return s;
-          m->colsum_valid = false;
+          m->valid.void_colsums();
           if (m->w_fly_now) {
             if ((s = w_bases_impl(m, b, -2, g.Nx + 4, INT_MAX, 0))) return s;
             m->w_stale = true;
@@ -1143,7 +1143,7 @@ struct GroupOps : StepOps {
       real* rb[2] = {G.send[s][b][0], G.send[s][b][1]};
       return move_rows(G.slabs[s], group, rb, true);
     }
-    if (group == 0) G.slabs[s]->halo_colsum_valid = G.slabs[s]->colsum_valid;   // (every slab alike: same calls, same state)
+    if (group == 0) G.slabs[s]->valid.halo_colsums_packed();   // (every slab alike: same calls, same state)
     real* buf[2] = {G.send[s][b][0], G.send[s][b][1]};
     return pack_unpack(G.slabs[s], group, buf, true);
   }
@@ -1195,7 +1195,7 @@ struct GroupOps : StepOps {
   }
   bool velocities_ready(int s) override {
     gb25_model* m = G.slabs[s];
-    return m->ahead_uv_valid && m->baro_ahead && !m->ptr_exposed;
+    return m->valid.velocities_ready(m->baro_ahead);
   }
   bool subcycle_adopted(int s) override { return G.slabs[s]->baro_adopted; }
   gb25_status record(int slot, int c) override {

@@ -66,7 +66,7 @@ gb25_status spectrum_run(gb25_model* m, const char* what, const real* src, const
                          gb25_spectral_coefficient* out, int64_t* nonfinite_lines) {
   const size_t records = (size_t)L.by * L.kc * mc;
   if (gb25_status s = spectrum_buffer(m, what, records)) return s;
-  if (gb25_status s = diag_wait_for_model(m)) return s;
+  if (gb25_status s = wait_for_model(m)) return s;
   if (gb25_status s = spectrum_table(m)) return s;
   const SpecShape S = spectrum_shape(m, m_first, mc, L.bx);
   const int LB = 4 * S.lpw;

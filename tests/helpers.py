@@ -74,6 +74,9 @@ SQRT_EPS32 = float(np.sqrt(np.finfo(np.float32).eps))   # 3.4527e-4: the referen
 # kernel; with an fp32 equation of state G.u, G.S and w sit ~1e-3 away from an fp64 run.
 TENDENCY_RTOL = SQRT_EPS32
 STATE_FIELDS = ("u", "v", "w", "eta", "T", "S", "filtered.U", "filtered.V", "filtered.eta")
+# every parent array of a model without a closure, by the names of binding.FIELD_IDS (the bitwise tests compare them all)
+ALL_FIELDS = ["u", "v", "w", "T", "S", "pHY", "Gn.u", "Gn.v", "Gn.T", "Gn.S", "Gm.u", "Gm.v", "Gm.T", "Gm.S",
+              "eta", "U", "V", "eta_bar", "U_bar", "V_bar", "Gn.U", "Gn.V"]
 
 
 def assert_states_close(m1, m2, *, state_rtol=SQRT_EPS32, tendency_rtol=TENDENCY_RTOL, include_halos=True, label=""):

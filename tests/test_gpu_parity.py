@@ -8,13 +8,9 @@ import numpy as np
 import pytest
 
 import gb25_amd as gb
-from helpers import (SQRT_EPS32, assert_states_close, counter_rng, make_pair, set_noisy_velocities)
+from helpers import (ALL_FIELDS, SQRT_EPS32, assert_states_close, counter_rng, make_pair, set_noisy_velocities)
 
 pytestmark = pytest.mark.gpu
-
-ALL_FIELDS = ["u", "v", "w", "T", "S", "pHY", "Gn.u", "Gn.v", "Gn.T", "Gn.S", "Gm.u", "Gm.v", "Gm.T", "Gm.S",
-              "eta", "U", "V", "eta_bar", "U_bar", "V_bar", "Gn.U", "Gn.V"]
-
 
 def sync_all(rmodel, vmodel, names=ALL_FIELDS):
     """Copy every parent array of the CPU model into the GPU model (rounded to fp32) and back,

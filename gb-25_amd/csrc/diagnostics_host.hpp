@@ -86,7 +86,7 @@ inline void* diag_result_slot(gb25_model* m, int q) { return (char*)m->diag.scra
 gb25_status diag_source(gb25_model* m, gb25_field id, const real** src) {
   if (id < 0 || id >= GB25_FIELD_COUNT) return GB25_ERR_INVALID_ARGUMENT;
   if (!m->f[id].d) return fail(m, GB25_ERR_INVALID_ARGUMENT, "this model has no such field (closure = CATKEVerticalDiffusivity() only)");
-  if (m->uv_lazy)   // (only after a composite call that failed half-way)
+  if (m->route.memory_lacks_correction())   // (only after a composite call that failed half-way)
     if (gb25_status s = materialize_uv(m)) return s;
   if (id == GB25_PHY && m->phy_stale) {
     m->prof_redirect = GB25_K_DIAGNOSTICS;

@@ -15,6 +15,7 @@
 #include "spectrum_kernels.hpp"
 #include "diagnostics_state.hpp"
 #include "validity.hpp"
+#include "step_route.hpp"
 
 #include <cmath>
 #include <cstdarg>
@@ -202,27 +203,21 @@ struct gb25_model {
   int tracer_order = 5;              // tracer_advection = WENO(order = 5 | 7)
   double bottom_drag = 0.0;          // quadratic bottom drag coefficient (0: none); the two flux arrays behind Grid.bottom_flux
   real* d_bottom_flux[2] = {nullptr, nullptr};
-  // the corrector applied inside its consumers (k_corrector_2d): du, dv of the current step; while uv_lazy is set, u and
-  // v in memory lack them (only between the steps of one composite call: gb25_loop applies them before it returns)
+  // Which kernel corrects u, v this step, and in what form u, v and w sit in memory meanwhile (step_route.hpp; chosen once per step
+  // by choose_corrector).  corr: du, dv of the current step as 2-D fields (k_corrector_2d, or a by-product of the sweep).
+  StepRoute route;
   Field corr[2];
-  bool uv_lazy = false;
-  bool lazy_head_done = false;       // ... and its du, dv, chunk bases of w are made (stage 20)
-  bool step_lazy = false;            // slab: this step keeps the corrector inside its consumers (decided in stage 0)
   int lazy_corrector = 1;            // option LAZY_CORRECTOR
   // ... and with it w ON THE FLY (option W_ON_THE_FLY): in those steps the tendency kernels carry w up their chunks of levels
   // from the divergence of the transports they hold; no k_compute_w launch, no w traffic.  wbase: w at the first level of every
-  // chunk (k_w_bases).  While w_stale is set the field w in memory is the one of an earlier step (recomputed with the
-  // velocities: materialize_uv).  Results agree with the stand-alone w to round-off, not to the last bit.
+  // chunk (k_w_bases).  Results agree with the stand-alone w to round-off, not to the last bit.
   real* wbase = nullptr;
   int w_fly = 1;
-  bool w_stale = false, w_fly_now = false;
-  bool corr_out = false;             // corrector_impl: the sweep also writes du, dv of the own columns into corr[0], corr[1]
   // The corrector through the tracer kernel (round 4; grids with a bottom / curvilinear / folded, single domain): du, dv as 2-D
   // fields; the tracer kernel -- first in the step, and every u, v is some cell's west / south face -- adds them as it loads and
   // writes the corrected velocities into this second pair of arrays, which then BECOME u, v (pointer exchange) and get their halo
   // cells from the ordinary fill; the momentum kernel reads corrected velocities like any other.  No sweep over u and v.
   Field uvc[2];
-  bool uv_corr_pending = false;      // this step's tracer kernel writes the corrected velocities
   // levels a block of the momentum / tracer tendency kernel marches through (options MOMENTUM_CHUNK_LEVELS,
   // TRACER_CHUNK_LEVELS): fewer, longer chunks amortise the start-up of the vertical windows, more chunks fill the chip.
   // The momentum chunking is also the association of every column integral of u, v (all their producers share it).
@@ -340,6 +335,14 @@ struct Range {
   ~Range() {
     if (on) roctx().pop();
   }
+};
+// the model's launches go to another stream while this lives (the side stream of a step, the streams of an exchange context);
+// whichever way the scope is left, the model is back on the stream it had
+struct OnStream {
+  gb25_model* m;
+  hipStream_t saved;
+  OnStream(gb25_model* m_, hipStream_t st) : m(m_), saved(m_->stream) { m->stream = st; }
+  ~OnStream() { m->stream = saved; }
 };
 // the phase a kernel timer belongs to (src/precompile.jl:31-42; ":" + what inside the phase)
 inline const char* phase_name(int k) {
@@ -1112,7 +1115,7 @@ gb25_status compute_w_impl(gb25_model* m, int part = 0) {
   dim3 b = (na + nbcols) >= 64 ? dim3(64, 4) : dim3(16, 16);
   const LazyCorr lz{m->corr[0].d, m->corr[1].d, m->wbase, m->g.sx * m->g.sy_v};
   auto kw = k_compute_w<false, false>;
-  if (m->uv_lazy) kw = k_compute_w<false, true>;
+  if (m->route.kernels_add_correction()) kw = k_compute_w<false, true>;
   else if (g.cv.on) kw = k_compute_w<true, false>;
   hipLaunchKernelGGL(kw, grid2(na + nbcols, ey, b), b, 0, m->stream, g, m->f[GB25_U].d, m->f[GB25_V].d, m->f[GB25_W].d, ia,
                      na, ib, nbcols, lz);
@@ -1239,7 +1242,9 @@ struct MomentumKernels {   // k_momentum_tendencies_v5
 // velocities, only w is not read) -- in the passes over the whole domain
 std::array<bool, MomentumKernels::n> momentum_flags(const gb25_model* m, int part) {
   const bool ahead = m->ab2_ahead == 1 && !m->valid.ptr_exposed, curv = m->g.cv.on;
-  return {ahead, m->immersed || curv, curv, m->uv_lazy, m->bottom_drag != 0, ahead && m->w_fly_now && (m->uv_lazy || part == 0)};
+  const StepRoute& r = m->route;
+  return {ahead, m->immersed || curv, curv, r.kernels_add_correction(), m->bottom_drag != 0,
+          ahead && r.kernels_carry_w() && (r.kernels_add_correction() || part == 0)};
 }
 
 struct TracerKernels {   // k_tracer_tendencies_v5; the flag O7: ORD = 7 (WENO(order = 7)), else 5
@@ -1257,9 +1262,9 @@ struct TracerKernels {   // k_tracer_tendencies_v5; the flag O7: ORD = 7 (WENO(o
 // WCORR: the corrector through the tracer kernel -- it adds du, dv as it loads (LAZY) and writes the corrected u, v; the halo
 // cells of the next T, S are then left to the fill (no FOLD)
 std::array<bool, TracerKernels::n> tracer_flags(const gb25_model* m) {
-  const bool ahead = m->ab2_ahead && !m->valid.ptr_exposed, curv = m->g.cv.on, wcorr = m->uv_corr_pending;
-  return {ahead, m->immersed || curv, ahead && producers_fold(m) && !wcorr, curv, m->uv_lazy || wcorr, m->tracer_order == 7,
-          ahead && m->w_fly_now, wcorr};
+  const bool ahead = m->ab2_ahead && !m->valid.ptr_exposed, curv = m->g.cv.on, wcorr = m->route.tracer_kernel_corrects();
+  return {ahead, m->immersed || curv, ahead && producers_fold(m) && !wcorr, curv, m->route.kernels_add_correction() || wcorr,
+          m->tracer_order == 7, ahead && m->route.kernels_carry_w(), wcorr};
 }
 
 struct SingleKernels {   // k_tracer_tendencies_single (CATKE's e); O7 as in TracerKernels
@@ -1272,7 +1277,7 @@ struct SingleKernels {   // k_tracer_tendencies_single (CATKE's e); O7 as in Tra
 // (WFLY: the field w is stale, the kernel carries w up its chunks like the two others)
 std::array<bool, SingleKernels::n> single_flags(const gb25_model* m) {
   const bool curv = m->g.cv.on;
-  return {m->immersed || curv, curv, m->tracer_order == 7, m->w_fly_now};
+  return {m->immersed || curv, curv, m->tracer_order == 7, m->route.kernels_carry_w()};
 }
 
 // part: 0 = every tile column; 1 = the interior tile columns (a12: launched before the x-halo bundle has arrived);
@@ -1321,7 +1326,7 @@ gb25_status momentum_impl(gb25_model* m, int part = 0) {
     }
     const LazyCorr lz{m->corr[0].d, m->corr[1].d, m->wbase, m->g.sx * m->g.sy_v};
     // (single domain: the kernel also writes the halo images of the next u, v; a slab's come with the next bundle)
-    if (m->uv_lazy && !(m->slab || (nx.fold && part == 0)))
+    if (m->route.memory_lacks_correction() && !(m->slab || (nx.fold && part == 0)))
       return fail(m, GB25_ERR_STATE, "internal: uncorrected velocities in a step whose momentum kernel cannot correct them");
     MomentumKernels::kernel_t k5;
     if (gb25_status s_ = tendency_instance<MomentumKernels>(m, flags, &k5)) return s_;
@@ -1396,11 +1401,12 @@ gb25_status tracers_impl(gb25_model* m) {
       nx.C1 = real(1.5) + (real)m->cfg.chi; nx.C2 = real(0.5) + (real)m->cfg.chi;
     }
     const LazyCorr lz{m->corr[0].d, m->corr[1].d, m->wbase, m->g.sx * m->g.sy_v};
-    if (m->uv_lazy && !(fold || m->slab))
+    if (m->route.memory_lacks_correction() && !(fold || m->slab))
       return fail(m, GB25_ERR_STATE, "internal: uncorrected velocities in a step whose tracer kernel cannot correct them");
     TracerKernels::kernel_t kern;
     if (gb25_status s_ = tendency_instance<TracerKernels>(m, flags, &kern)) return s_;
-    if (m->uv_corr_pending) {
+    const bool wcorr = m->route.tracer_kernel_corrects();
+    if (wcorr) {
       if (!m->uvc[0].d) return fail(m, GB25_ERR_STATE, "internal: the corrected velocities have no arrays");
       nx.uc = m->uvc[0].d;
       nx.vc = m->uvc[1].d;
@@ -1411,10 +1417,10 @@ gb25_status tracers_impl(gb25_model* m) {
                        m->f[GB25_GN_S].d, nbx, kchunks, nb, nx, lz);
     LAUNCHCHK();
     m->valid.record_tracer_lookahead(ahead, nx.dt, (real)m->cfg.chi);
-    if (m->uv_corr_pending) {
+    if (wcorr) {
       // the arrays the kernel wrote ARE u, v from here on (the uncorrected ones become the scratch pair of the next step), and
       // their halo cells come from the ordinary fill -- y / z layers, the rows beyond a zipper fold, the periodic x copy
-      m->uv_corr_pending = false;
+      m->route.tracer_kernel_wrote_corrected();
       for (int q = 0; q < 2; q++) std::swap(m->f[GB25_U + q].d, m->uvc[q].d);
       if (gb25_status s = fill_halos_impl(m, true, false, 1, 1)) return s;
     }
@@ -1883,6 +1889,8 @@ gb25_status corrector_impl(gb25_model* m, bool use_colsum = false, int part = 0)
     // for them was 36 us of latency on the critical path of a 180-column rank)
     const bool cells_halo = m->slab && part == 2 && use_colsum && m->valid.halo_colsum_valid;
     const bool cells = (m->slab && part == 1 && cs) || cells_halo;
+    real* const du = m->route.sweep_leaves_increments() ? m->corr[0].d : nullptr;
+    real* const dv = m->route.sweep_leaves_increments() ? m->corr[1].d : nullptr;
     auto launch = [&](int i0_, int ni_, int skf, int sk, int jr0, int nj, int jskf, int jsk) {
       if (cells) {
         hipLaunchKernelGGL(m->immersed ? k_corrector_cells<true> : k_corrector_cells<false>,
@@ -1895,7 +1903,7 @@ gb25_status corrector_impl(gb25_model* m, bool use_colsum = false, int part = 0)
         hipLaunchKernelGGL(kern, grid2(ni_, nj, b), b, 0, m->stream, g, m->f[GB25_U].d, m->f[GB25_V].d,
                            m->f[GB25_BT_U].d, m->f[GB25_BT_V].d, m->f[GB25_U_BAR].d, m->f[GB25_V_BAR].d,
                            cs ? m->colsum[0].d : nullptr, cs ? m->colsum[1].d : nullptr, i0_, ni_, mom_kchunks(m),
-                           skf, sk, jr0, nj, jskf, jsk, m->corr_out ? m->corr[0].d : nullptr, m->corr_out ? m->corr[1].d : nullptr);
+                           skf, sk, jr0, nj, jskf, jsk, du, dv);
       }
     };
     // rows: the own ones (the halo rows of a rank of a 2-D decomposition arrive corrected: group 10 travels after this)
@@ -2165,60 +2173,79 @@ gb25_status ab2_step_impl(gb25_model* m, double dt, int euler) {
 // need_w = false: the step that follows carries w inside its tendency kernels as well (w on the fly beside the corrector's sweep):
 // the field w stays stale
 gb25_status materialize_uv(gb25_model* m, bool need_w = true) {
-  if (m->uv_lazy) {
+  if (m->route.memory_lacks_correction()) {
     const Grid& g = m->g;
     dim3 b(64, 4);
     hipLaunchKernelGGL(k_apply_correction, grid2(g.sx, g.sy_v, b), b, 0, m->stream, g, m->f[GB25_U].d, m->f[GB25_V].d,
                        LazyCorr{m->corr[0].d, m->corr[1].d, nullptr, 0});
     LAUNCHCHK();
-    m->uv_lazy = false;
   }
-  m->w_fly_now = false;
-  if (need_w && m->w_stale) {   // the steps behind carried w inside their tendency kernels: the field itself, from the corrected velocities
-    m->w_stale = false;
-    return compute_w_impl(m);
-  }
-  return GB25_OK;
+  // the steps behind carried w inside their tendency kernels: the field itself, from the corrected velocities
+  const bool w_too = need_w && m->route.w_field_stale();
+  m->route.materialized(w_too);
+  return w_too ? compute_w_impl(m) : GB25_OK;
 }
-// may this step leave u, v uncorrected in memory?  The flat lat-lon grid (the LAZY instances of the tendency kernels), both
-// look-aheads on, the default kernels, no bottom drag, WENO(order = 5) -- on a single domain (lazy_corrector_ok) or a slab
-// (slab_lazy_ok, below)
+// What each route of a step requires ("Which kernel corrects u, v: the route of a step", one row per term).  The LAZY
+// instances of the tendency kernels exist for the flat lat-lon grid; a single domain also needs look-aheads that write their halos
 inline bool lazy_instances_ok(const gb25_model* m) {
   return m->lazy_corrector && !m->coupled && m->bottom_drag == 0 && m->tracer_order == 5 && m->two_streams && !m->immersed &&
          !m->g.cv.on && m->kernel_gen >= 2 && m->ab2_ahead == 1 && !m->valid.ptr_exposed && m->pressure_bits == 64;
 }
-// ... a single domain: the look-aheads able to write their halos; `more` (time_step_impl): the step is one of a composite call
-// (gb25_loop), which materialises u, v, w when it returns
 inline bool lazy_corrector_ok(const gb25_model* m) { return lazy_instances_ok(m) && producers_fold(m); }
-
-// w on the fly beside the corrector's SWEEP (round 4): the grids the corrector-inside-its-consumers instances do not exist for --
-// a GridFittedBottom, the curvilinear grids, the zipper fold -- still drop the k_compute_w launch: the sweep leaves du, dv of the
-// own columns as a by-product, k_w_bases turns the look-ahead's chunk integrals + du, dv into w at the chunk boundaries, and the
-// WFLY instances of the two tendency kernels carry w up their chunks.  Single domain, between the steps of one gb25_loop call.
-// ... and the sweep itself through the tracer kernel (above: uvc): everything wfly_sweep_ok asks for, the tracer kernel first
-inline bool lazy_through_tracers_ok(const gb25_model* m);
+// w on the fly beside the corrector's sweep: every other grid of a single domain (the sweep leaves corrected velocities, so drag,
+// fluxes and WENO(order = 7) are fine; not with a closure, whose implicit solve rewrites the chunk sums k_w_bases starts from)
 inline bool wfly_sweep_ok(const gb25_model* m) {
-  // (like the corrector inside its consumers it rides on the sub-cycle look-ahead -- on by default from 8 M cells on: small models
-  // keep the stand-alone w, bit for bit what their decompositions compute)
-  // (the sweep leaves corrected velocities in memory: the similarity-theory fluxes of a coupled model, the quadratic bottom drag and
-  // WENO(order = 7) tracers -- the data-free climate model -- read them like anything else; instances of the three tendency kernels exist)
   return m->w_fly && m->baro_ahead != 0 && !m->slab && m->two_streams && m->kernel_gen >= 2 &&
-         m->ab2_ahead == 1 && !m->valid.ptr_exposed && m->nu == 0 && m->kappa == 0 &&
-         // (closure = CATKE: the implicit solve of u, v that follows the AB2 update rewrites the look-ahead's chunk sums with
-         // those of the velocities it leaves: catke_implicit_impl, ImplicitVarFields::P; e is advected by a kernel that carries w too)
-         chunkings_match(m);
+         m->ab2_ahead == 1 && !m->valid.ptr_exposed && m->nu == 0 && m->kappa == 0 && chunkings_match(m);
 }
-
+// ... and the sweep itself through the tracer kernel, first in the step (not with a closure: its kernels read u, v ahead of it)
 inline bool lazy_through_tracers_ok(const gb25_model* m) {
-  // (not with a closure: its kernels read u, v ahead of the tracer kernel that would write the corrected ones)
   return m->lazy_corrector && wfly_sweep_ok(m) && !m->catke && !m->coupled && m->bottom_drag == 0 && m->tracer_order == 5 &&
          (m->immersed || m->g.cv.on) && m->tracers_first != 0 && m->pressure_bits == 64;
 }
-
-// ... and a slab of an x decomposition or a rank of a 2-D one: the same kernels without the halo images (its halos come with the
-// bundles, and with them the neighbours' column integrals: du, dv of the halo columns / rows are computed locally)
+// a slab or a rank of a mesh: the LAZY instances without the halo images (du, dv of the halo columns / rows are computed locally)
 inline bool slab_lazy_ok(const gb25_model* m) { return m->slab && lazy_instances_ok(m) && m->nu == 0 && m->kappa == 0 && !m->catke; }
 inline bool slab_wfly_ok(const gb25_model* m) { return slab_lazy_ok(m) && m->w_fly && chunkings_match(m); }
+
+// Which kernel corrects u, v this step: the one decision of a step (time_step_impl; stage 0 of a slab) and the only caller of the four
+// _ok functions.  more: a step of a composite call (gb25_loop), which materialises u, v, w when it returns; uv_adopted, baro_adopted:
+// the step adopted the velocity / the sub-cycle look-ahead
+Corrector choose_corrector(const gb25_model* m, bool more, bool uv_adopted, bool baro_adopted) {
+  if (m->slab)   // a slab asks for neither `more` nor complete_fills_needed == 0, and never takes ThroughTracers or SweepWFly
+    return uv_adopted && baro_adopted && slab_lazy_ok(m) ? Corrector::InConsumers : Corrector::Sweep;
+  if (!(more && uv_adopted && m->valid.complete_fills_needed == 0)) return Corrector::Sweep;
+  if (baro_adopted && lazy_corrector_ok(m)) return Corrector::InConsumers;
+  if (baro_adopted && lazy_through_tracers_ok(m)) return Corrector::ThroughTracers;
+  if (wfly_sweep_ok(m)) return Corrector::SweepWFly;   // does not ask for baro_adopted: it asks for baro_ahead != 0 (wfly_sweep_ok)
+  return Corrector::Sweep;
+}
+// ... and whether that step's tendency kernels carry w: in the consumers, a slab follows slab_wfly_ok, a single domain the option and
+// the chunkings; the two other routes away from the plain sweep exist only with w on the fly
+inline bool route_carries_w(const gb25_model* m, Corrector c) {
+  if (c == Corrector::InConsumers) return m->slab ? slab_wfly_ok(m) : (m->w_fly && chunkings_match(m));
+  return c != Corrector::Sweep;
+}
+
+// The head of a step whose corrector is not the sweep: du, dv (k_corrector_2d) on the columns `c`, rows jr0 + [0, nj), in blocks of
+// shape b; the chunk bases of w (k_w_bases) on the columns `bases`; G^- <- G^n where `cache` says so.  An empty range (ni = 0) launches
+// nothing; the column integrals are used up once du, dv of the OWN columns are made (a slab's halo columns skip them).  The timer is the caller's.
+struct Cols { int i0, ni, skip_from, skip; };   // columns i0 + [0, ni) (from skip_from on: + skip)
+constexpr Cols NO_COLS{0, 0, INT_MAX, 0};
+gb25_status unswept_head(gb25_model* m, dim3 b, Cols c, int jr0, int nj, Cols bases, bool cache) {
+  gb25_status s;
+  if (c.ni > 0) {
+    if ((s = corrector_2d_impl(m, b, c.i0, c.ni, c.skip_from, c.skip, jr0, nj))) return s;
+    if (c.skip == 0) m->valid.void_colsums();
+  }
+  // (through the tracer kernel: memory lacks du, dv only until that kernel has run, and no other kernel reads u, v before it)
+  if (!m->route.tracer_kernel_corrects()) m->route.correction_left_in_2d();
+  if (bases.ni > 0) {
+    if ((s = w_bases_impl(m, b, bases.i0, bases.ni, bases.skip_from, bases.skip))) return s;
+    m->route.w_carried_in_kernels();
+  }
+  if (cache) cache_previous_tendencies(m);
+  return GB25_OK;
+}
 
 // One time step on a single slab.  Two HIP streams: the tracer branch (AB2 of T,S -> their halos -> hydrostatic
 // pressure: HBM- then fp64-bound) is independent of the velocity branch (AB2 of u,v -> split-explicit sub-cycle,
@@ -2249,14 +2276,12 @@ gb25_status time_step_impl(gb25_model* m, int euler, bool more = false) {
   const bool adopted = m->valid.velocities_adoptable((real)dt, chi);
   const bool baro_adopted = adopted && m->valid.ahead_baro_valid;   // (made from that very look-ahead, same dt)
   m->valid.void_subcycle_lookahead();
-  // The corrector inside its consumers: when everything this step needs was made ahead of time (u, v, the sub-cycle) and
-  // another step follows, no sweep over u and v at all -- a 2-D kernel leaves du, dv and w, the tendency kernels add them.
-  const bool lazy = more && adopted && baro_adopted && m->valid.complete_fills_needed == 0 && lazy_corrector_ok(m);
-  // ... or the sweep stays and only w moves into the tendency kernels (the look-ahead's chunk integrals must be this step's)
-  // ... or the tracer kernel applies it and writes the corrected velocities (grids with a bottom, curvilinear, folded) ...
-  const bool lazy_t = !lazy && more && adopted && baro_adopted && m->valid.complete_fills_needed == 0 && lazy_through_tracers_ok(m);
-  const bool wfly_sweep = !lazy && !lazy_t && more && adopted && m->valid.complete_fills_needed == 0 && wfly_sweep_ok(m);
-  if (!lazy && (s = materialize_uv(m, !(wfly_sweep || lazy_t)))) return s;   // (the stand-alone kernels below expect corrected velocities)
+  // When everything this step needs was made ahead of time (u, v, the sub-cycle) and another step follows, no sweep over u and v:
+  // a 2-D kernel leaves du, dv and the consumers add them, or the tracer kernel writes corrected arrays; or only w leaves the step
+  const Corrector corrector = choose_corrector(m, more, adopted, baro_adopted);
+  // (every route but the first expects corrected velocities in memory; the plain sweep the field w as well)
+  if (corrector != Corrector::InConsumers && (s = materialize_uv(m, corrector == Corrector::Sweep))) return s;
+  m->route.begin(corrector, route_carries_w(m, corrector));
   if ((s = ab2_velocities_impl(m, (real)dt, chi))) return s;
   Halo2 hG = halo2_G(m);
   // the sub-cycle reads G.U, G.V at interior points only (periodic wrap and walls are in the kernel): their halo
@@ -2273,20 +2298,20 @@ gb25_status time_step_impl(gb25_model* m, int euler, bool more = false) {
   HIPCHK(hipEventRecord(m->ev_fork, main));
   HIPCHK(hipStreamWaitEvent(side, early_fork ? m->ev_tend : m->ev_fork, 0));
   // ---- tracer branch (side stream)
-  m->stream = side;
   // (complete fills for the two steps after a host write, one per buffer of each alternating pair: see fold_fills)
   const bool complete = m->valid.take_complete_fill();
-  s = ab2_tracers_impl(m, (real)dt, chi);
-  // y/z/x halos of T, S -- unless the look-ahead that was just adopted wrote them itself
-  if (!s && (complete || !(ts_adopted && m->ahead_ts_folded))) s = fill_halos_impl(m, true, false, 1, 2);
-  // (closure = CATKE: e is not stepped by ab2_step!; its halos were refilled after its step inside compute_diffusivities! --
-  // unless the option keeps them stale there, as Oceananigans does as recalled: then they are filled here, with the others)
-  if (!s && m->catke && m->catke_stale_e_halos) s = fill_halos_impl(m, true, false, 1, 4);
-  if (!s && hipEventRecord(m->ev_ts, side) != hipSuccess) s = fail(m, GB25_ERR_HIP, "hipEventRecord(ev_ts) failed");
-  if (!s) s = compute_p_impl(m, INT_MIN, INT_MIN, 0, -1, true);
-  if (!s && adopted) s = fill_halos_2d(m, hG);
-  m->stream = main;
-  if (s) return s;
+  {
+    OnStream on(m, side);
+    if ((s = ab2_tracers_impl(m, (real)dt, chi))) return s;
+    // y/z/x halos of T, S -- unless the look-ahead that was just adopted wrote them itself
+    if ((complete || !(ts_adopted && m->ahead_ts_folded)) && (s = fill_halos_impl(m, true, false, 1, 2))) return s;
+    // (closure = CATKE: e is not stepped by ab2_step!; its halos were refilled after its step inside compute_diffusivities! --
+    // unless the option keeps them stale there, as Oceananigans does as recalled: then they are filled here, with the others)
+    if (m->catke && m->catke_stale_e_halos && (s = fill_halos_impl(m, true, false, 1, 4))) return s;
+    HIPCHK(hipEventRecord(m->ev_ts, side));
+    if ((s = compute_p_impl(m, INT_MIN, INT_MIN, 0, -1, true))) return s;
+    if (adopted && (s = fill_halos_2d(m, hG))) return s;
+  }
   HIPCHK(hipEventRecord(m->ev_join, side));
   // ---- velocity branch (main stream)
   if (baro_adopted) {
@@ -2308,65 +2333,56 @@ gb25_status time_step_impl(gb25_model* m, int euler, bool more = false) {
   // The reference fills the halos of u, v, eta, U, V here as well as after the corrector.  On a single slab the
   // corrector reads and writes its own columns only, and the fill after it rewrites exactly the same halo cells from
   // the corrected interior, so the first fill has no effect on any later value: it is left out (3 launches).
-  if (lazy) {
-    const Grid& g = m->g;
-    dim3 b(64, 4);
-    Timed t(m, GB25_K_CORRECTOR);
-    if ((s = corrector_2d_impl(m, b, 0, g.Nx, INT_MAX, 0, 0, g.Ny + 1))) return s;
-    m->uv_lazy = true;
-    m->valid.void_colsums();
-    m->w_fly_now = m->w_fly && chunkings_match(m);
-    if (m->w_fly_now) {
-      if ((s = w_bases_impl(m, b, -2, g.Nx + 4, INT_MAX, 0))) return s;
-      m->w_stale = true;
+  const Grid& g = m->g;
+  const dim3 b(64, 4);
+  const Cols own{0, g.Nx, INT_MAX, 0}, wide{-2, g.Nx + 4, INT_MAX, 0};
+  switch (corrector) {
+    case Corrector::InConsumers: {
+      Timed t(m, GB25_K_CORRECTOR);
+      if ((s = unswept_head(m, b, own, 0, g.Ny + 1, m->route.kernels_carry_w() ? wide : NO_COLS, true))) return s;
+      break;
     }
-    cache_previous_tendencies(m);
-  } else if (lazy_t) {
-    const Grid& g = m->g;
-    dim3 b(64, 4);
-    Timed t(m, GB25_K_CORRECTOR);
-    for (int q = 0; q < 2; q++)
-      if (!m->uvc[q].d && (s = alloc_field(m, m->uvc[q], m->f[GB25_U + q].nx, m->f[GB25_U + q].ny, m->f[GB25_U + q].nz))) return s;
-    // du, dv on the own faces (rows of y faces: [0, Ny) on a folded grid, [0, Ny] below a wall) ...
-    if ((s = corrector_2d_impl(m, b, 0, g.Nx, INT_MAX, 0, 0, g.Ny + (g.cv.north_fold ? 0 : 1)))) return s;
-    // ... and their halo cells as the fills derive them (the rows beyond a zipper fold: images with the sign of a vector component)
-    if (g.cv.north_fold) {
-      Halo2 hc{};
-      hc.p[0] = m->corr[0].d; hc.is_v[0] = 0; hc.xf[0] = 1; hc.neg[0] = 1;
-      hc.p[1] = m->corr[1].d; hc.is_v[1] = 1; hc.xf[1] = 0; hc.neg[1] = 1;
-      hc.n = 2;
-      if ((s = fill_halos_2d(m, hc))) return s;
+    case Corrector::ThroughTracers: {
+      Timed t(m, GB25_K_CORRECTOR);
+      for (int q = 0; q < 2; q++)
+        if (!m->uvc[q].d && (s = alloc_field(m, m->uvc[q], m->f[GB25_U + q].nx, m->f[GB25_U + q].ny, m->f[GB25_U + q].nz))) return s;
+      // du, dv on the own faces (rows of y faces: [0, Ny) on a folded grid, [0, Ny] below a wall) ...
+      if ((s = unswept_head(m, b, own, 0, g.Ny + (g.cv.north_fold ? 0 : 1), NO_COLS, false))) return s;
+      // ... and their halo cells as the fills derive them (the rows beyond a zipper fold: images with the sign of a vector component)
+      if (g.cv.north_fold) {
+        Halo2 hc{};
+        hc.p[0] = m->corr[0].d; hc.is_v[0] = 0; hc.xf[0] = 1; hc.neg[0] = 1;
+        hc.p[1] = m->corr[1].d; hc.is_v[1] = 1; hc.xf[1] = 0; hc.neg[1] = 1;
+        hc.n = 2;
+        if ((s = fill_halos_2d(m, hc))) return s;
+      }
+      if ((s = unswept_head(m, b, NO_COLS, 0, 0, wide, false))) return s;
+      // (the two strips of halo cells of the uncorrected u, v the tracer kernel reads: k_uncorrected_edges)
+      hipLaunchKernelGGL(k_uncorrected_edges, dim3((std::max(g.Nx, g.Ny) + 255) / 256, g.Nz, g.cv.north_fold ? 3 : 2), dim3(256), 0, main, g,
+                         m->f[GB25_U].d, m->f[GB25_V].d);
+      LAUNCHCHK();
+      cache_previous_tendencies(m);
+      break;
     }
-    m->valid.void_colsums();
-    m->w_fly_now = true;
-    if ((s = w_bases_impl(m, b, -2, g.Nx + 4, INT_MAX, 0))) return s;
-    m->w_stale = true;
-    m->uv_corr_pending = true;
-    // (the two strips of halo cells of the uncorrected u, v the tracer kernel reads: k_uncorrected_edges)
-    hipLaunchKernelGGL(k_uncorrected_edges, dim3((std::max(g.Nx, g.Ny) + 255) / 256, g.Nz, g.cv.north_fold ? 3 : 2), dim3(256), 0, main, g,
-                       m->f[GB25_U].d, m->f[GB25_V].d);
-    LAUNCHCHK();
-    cache_previous_tendencies(m);
-  } else {
-    m->corr_out = wfly_sweep;      // (the sweep leaves du, dv of the own columns behind for k_w_bases)
-    s = corrector_impl(m, true);
-    m->corr_out = false;
-    if (s) return s;
-    m->w_fly_now = wfly_sweep;
-    if (wfly_sweep) {
-      if ((s = w_bases_impl(m, dim3(64, 4), -2, m->g.Nx + 4, INT_MAX, 0))) return s;
-      m->w_stale = true;
-    }
+    case Corrector::SweepWFly:   // (the sweep leaves du, dv of the own columns behind for k_w_bases)
+    case Corrector::Sweep:
+      s = corrector_impl(m, true);
+      m->route.sweep_done();
+      if (s) return s;
+      if (corrector == Corrector::SweepWFly && (s = w_bases_impl(m, b, wide.i0, wide.ni, wide.skip_from, wide.skip))) return s;
+      if (corrector == Corrector::SweepWFly) m->route.w_carried_in_kernels();
+      break;
   }
   {
     // u, v and eta, U, V -- whatever their last writers (the corrector, the sub-cycle's last launch) did not fill
-    // (lazy_t: u, v get their halo cells behind the tracer kernel, which writes their corrected interior: tracers_impl)
-    const bool uv_fresh = lazy || lazy_t || (producers_fold(m) && m->composite && !complete);
+    // (through the tracer kernel: u, v get their halo cells behind that kernel, which writes their corrected interior: tracers_impl)
+    const bool unswept = corrector == Corrector::InConsumers || corrector == Corrector::ThroughTracers;
+    const bool uv_fresh = unswept || (producers_fold(m) && m->composite && !complete);
     const int which = (uv_fresh ? 0 : 1) | ((eta_halos_fresh && !complete) ? 0 : 2);
     if (which && (s = fill_halos_impl(m, true, false, which, 1))) return s;
   }
-  if (!((lazy || wfly_sweep || lazy_t) && m->w_fly_now) && (s = compute_w_impl(m))) return s;
-  if (lazy_t && !m->tracers_first) return fail(m, GB25_ERR_STATE, "internal: the corrector through the tracer kernel needs the tracer kernel first");
+  if (!m->route.kernels_carry_w() && (s = compute_w_impl(m))) return s;
+  if (corrector == Corrector::ThroughTracers && !m->tracers_first) return fail(m, GB25_ERR_STATE, "internal: the corrector through the tracer kernel needs the tracer kernel first");
   // ---- join: the tendencies need w, u, v and T, S (the tracers) / the pressure differences (the momentum)
   const bool tracers_first = m->tracers_first != 0;
   if (m->catke) {   // compute_diffusivities! + the slow tendency of e, ahead of the tendency kernels (see update_state_impl)
@@ -2394,10 +2410,11 @@ gb25_status time_step_impl(gb25_model* m, int euler, bool more = false) {
       if (!m->baro_stream) HIPCHK(hipStreamCreateWithFlags(&m->baro_stream, hipStreamNonBlocking));
       HIPCHK(hipEventRecord(m->ev_mom, main));
       HIPCHK(hipStreamWaitEvent(m->baro_stream, m->ev_mom, 0));
-      m->stream = m->baro_stream;
-      s = barotropic_impl(m, m->valid.ahead_uv_dt, true);
-      m->ahead_eta_folded = m->last_baro_folded;
-      m->stream = main;
+      {
+        OnStream on(m, m->baro_stream);
+        s = barotropic_impl(m, m->valid.ahead_uv_dt, true);
+        m->ahead_eta_folded = m->last_baro_folded;
+      }
       if (s) return s;
       HIPCHK(hipEventRecord(m->ev_baro, m->baro_stream));
       m->baro_inflight = true;
@@ -2765,7 +2782,7 @@ static gb25_status copy_field(gb25_model* m, gb25_field id, real* host, int incl
   if (!m || id < 0 || id >= GB25_FIELD_COUNT || !host) return GB25_ERR_INVALID_ARGUMENT;
   if (!m->f[id].d) return fail(m, GB25_ERR_INVALID_ARGUMENT, "this model has no such field (closure = CATKEVerticalDiffusivity() only)");
   if (to_device && (id == GB25_U || id == GB25_V)) m->valid.void_colsums();  // cached column integrals are stale
-  if (m->uv_lazy)   // (only after a composite call that failed half-way: memory must hold the corrected velocities)
+  if (m->route.memory_lacks_correction())   // (only after a composite call that failed half-way: memory must hold the corrected velocities)
     if (gb25_status s = materialize_uv(m)) return s;
   if (gb25_status s = materialize_prev_uv(m)) return s;   // (CATKE's previous velocities into their fields before the host reads or writes)
   Field& F = m->f[id];
@@ -2852,7 +2869,7 @@ gb25_status gb25_field_device_ptr(gb25_model* m, gb25_field id, void** dev) {
   if (!m || id < 0 || id >= GB25_FIELD_COUNT || !dev) return GB25_ERR_INVALID_ARGUMENT;
   if (!m->f[id].d) return fail(m, GB25_ERR_INVALID_ARGUMENT, "this model has no such field (closure = CATKEVerticalDiffusivity() only)");
   if (gb25_status s = collective_guard(m, 2, (unsigned)id, 0.0)) return s;
-  if (m->uv_lazy)
+  if (m->route.memory_lacks_correction())
     if (gb25_status s = materialize_uv(m)) return s;
   if (gb25_status s = materialize_prev_uv(m)) return s;
   if (id == GB25_U || id == GB25_V || id == GB25_T || id == GB25_S || (id >= GB25_GN_U && id <= GB25_GM_S) ||

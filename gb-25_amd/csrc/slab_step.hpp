@@ -327,11 +327,10 @@ gb25_status slab_stage(gb25_model* m, int stage, int euler) {
     // ahead of time, no sweep over u and v -- 2-D kernels leave du, dv (own columns in stage 2, halo columns in stage 3 from the
     // column integrals the bundle carries) and the kernels that read u, v add them.  Memory holds the uncorrected velocities
     // until the composite call returns (gb25_loop).
-    m->step_lazy = uv_adopted && m->baro_adopted && slab_lazy_ok(m);
-    m->lazy_head_done = false;
     // ... and with it w on the fly: no k_compute_w launch, the tendency kernels carry w up their chunks of levels from 2-D bases
-    m->w_fly_now = m->step_lazy && slab_wfly_ok(m);
-    if (!m->step_lazy && (s = materialize_uv(m))) return s;   // (the sweeps below expect corrected velocities)
+    const Corrector corrector = choose_corrector(m, false, uv_adopted, m->baro_adopted);
+    if (corrector == Corrector::Sweep && (s = materialize_uv(m))) return s;   // (the sweeps below expect corrected velocities)
+    m->route.begin(corrector, route_carries_w(m, corrector));
     if ((s = ab2_local_impl(m, (real)dt, chi))) return s;
     if (m->baro_adopted) {
       // the sub-cycle of this step, its wide-halo exchange and the exchange of the new eta, U, V columns all ran
@@ -351,11 +350,10 @@ gb25_status slab_stage(gb25_model* m, int stage, int euler) {
       // difference of this pass reads a stale halo column and is redone by the west strip.
       HIPCHK(hipEventRecord(m->ev_fork, m->stream));
       HIPCHK(hipStreamWaitEvent(m->side_stream, m->ev_fork, 0));
-      hipStream_t main = m->stream;
-      m->stream = m->side_stream;
-      s = compute_p_impl(m, 0, g.Nx - 1, 0, -1, true);
-      m->stream = main;
-      if (s) return s;
+      {
+        OnStream on(m, m->side_stream);
+        if ((s = compute_p_impl(m, 0, g.Nx - 1, 0, -1, true))) return s;
+      }
       HIPCHK(hipEventRecord(m->ev_join, m->side_stream));
     }
     return GB25_OK;
@@ -409,32 +407,28 @@ gb25_status slab_stage(gb25_model* m, int stage, int euler) {
     // corrector on the slab's own columns and, when the tendency kernels are split (a12), the y/z layers and w of the
     // own columns and the momentum tendencies of the interior tile columns.
     // (stage 20: the head of a lazy step -- du, dv and the chunk bases of w -- ahead of the wait for the packed bundle)
-    if (stage == 2 && m->lazy_head_done) {
+    const bool lazy = m->route.corrector_in_consumers(), wfly = m->route.kernels_carry_w();
+    if (stage == 2 && m->route.head_is_done()) {
       // (stage 20 did the corrector's part)
-    } else if (m->step_lazy) {
-      m->lazy_head_done = stage == 20;
+    } else if (lazy) {
+      if (stage == 20) m->route.head_done();
       if (!m->valid.colsum_valid) return fail(m, GB25_ERR_STATE, "internal: a lazy step without the column integrals of u, v");
-      dim3 b(64, 4);
       Timed t(m, GB25_K_CORRECTOR);
       // (a rank of a 2-D decomposition has no interior pass: du, dv and the chunk bases of w over its whole extended range at
       // once, in stage 3, when every halo is in)
-      if (m->Ry == 1 && (s = corrector_2d_impl(m, b, 0, g.Nx, INT_MAX, 0, 0, g.Ny + 1))) return s;
-      m->uv_lazy = true;
-      if (m->Ry == 1) m->valid.void_colsums();
-      if (m->w_fly_now && m->Ry == 1) {
-        // chunk bases of w on the columns [0, Nx - 2] (their u faces are own columns), before the interior momentum pass
-        // overwrites the chunk sums they are made from
-        if ((s = w_bases_impl(m, b, 0, g.Nx - 1, INT_MAX, 0))) return s;
-        m->w_stale = true;
-      }
-      cache_previous_tendencies(m);
+      // chunk bases of w on the columns [0, Nx - 2] (their u faces are own columns), before the interior momentum pass
+      // overwrites the chunk sums they are made from
+      const bool own = m->Ry == 1;
+      if ((s = unswept_head(m, dim3(64, 4), own ? Cols{0, g.Nx, INT_MAX, 0} : NO_COLS, 0, g.Ny + 1,
+                            own && wfly ? Cols{0, g.Nx - 1, INT_MAX, 0} : NO_COLS, true)))
+        return s;
     } else if ((s = corrector_impl(m, true, 1))) {
       return s;
     }
     if (stage == 20 || !split) return GB25_OK;
     // y/z layers of the corrected u, v, own columns (lazy: the layers of the uncorrected ones are in place since stage 0)
-    if (!m->step_lazy && (s = fill_halos_impl(m, false, false, 1, 1))) return s;
-    if (!m->w_fly_now && (s = compute_w_impl(m, 1))) return s;
+    if (!lazy && (s = fill_halos_impl(m, false, false, 1, 1))) return s;
+    if (!wfly && (s = compute_w_impl(m, 1))) return s;
     HIPCHK(hipStreamWaitEvent(m->stream, m->ev_join, 0));       // the own columns' pressure differences (side stream)
     return momentum_impl(m, 1);
   } else if (stage == 33) {
@@ -449,23 +443,23 @@ gb25_status slab_stage(gb25_model* m, int stage, int euler) {
     // 2-D decomposition: group 0 has been unpacked; the corrector on the x-halo columns of the own rows, so that the rows that
     // leave for the southern / northern neighbour next (group 10) are corrected over their whole width
     // (a lazy step: the rows leave uncorrected, like the columns; the receiver makes du, dv of its halo rows itself)
-    return m->step_lazy ? GB25_OK : corrector_impl(m, true, 2);
+    return m->route.corrector_in_consumers() ? GB25_OK : corrector_impl(m, true, 2);
   } else if (stage == 3 || stage == 30 || stage == 31) {
     // groups 2 and 0 have been unpacked: corrector on the x-halo columns, then update_state without any
     // further exchange (y/z layers re-filled over the extended x range; w and p recomputed in the halos).
     // Folded grid: stage 30 = up to the y/z layers, then the rows beyond the fold arrive from the partner, stage 31 = the rest.
     // (a closure's fields travel in the bundle as well and its fills follow: the strips keep their old place behind them)
     const bool strips_first = p_early && !m->catke;
+    const bool lazy = m->route.corrector_in_consumers(), wfly = m->route.kernels_carry_w();
     const bool strips_done = m->strips_issued;   // (stage 33 ran them on the exchange stream)
     if (stage != 30) m->strips_issued = false;
     auto pressure_strips = [&]() -> gb25_status {
-      hipStream_t main = m->stream;
-      HIPCHK(hipEventRecord(m->ev_fork, main));
+      HIPCHK(hipEventRecord(m->ev_fork, m->stream));
       HIPCHK(hipStreamWaitEvent(m->side_stream, m->ev_fork, 0));
-      m->stream = m->side_stream;
-      gb25_status r = compute_p_impl(m, -g.H + 1, 0, g.Nx, g.Nx + g.H - 2, true);   // west strip (redoes column 0) + east strip
-      m->stream = main;
-      if (r) return r;
+      {
+        OnStream on(m, m->side_stream);
+        if (gb25_status r = compute_p_impl(m, -g.H + 1, 0, g.Nx, g.Nx + g.H - 2, true)) return r;   // west strip (redoes column 0) + east strip
+      }
       HIPCHK(hipEventRecord(m->ev_join, m->side_stream));
       return GB25_OK;
     };
@@ -476,38 +470,34 @@ gb25_status slab_stage(gb25_model* m, int stage, int euler) {
         // interior pass of stage 0 -- beside the corrector, the fills and w of the edge strips instead of after them
         if ((s = pressure_strips())) return s;
       }
-      if (m->step_lazy) {
+      if (lazy) {
         // du, dv of the x halo columns: the neighbours' column integrals came with the bundle, the new U, V of those columns
         // from the widened sub-cycle; their y/z layers of u, v arrived filled -- nothing else to do
         if (!m->valid.halo_colsum_valid) return fail(m, GB25_ERR_STATE, "internal: a lazy step without the neighbours' column integrals");
         if (m->Ry > 1) {
           // 2-D decomposition: everything at once -- own cells, halo columns, halo rows of the open sides (corners included)
-          dim3 b(64, 4);
           // rows: from the southern halo rows (or row 0) to the last northern halo row of the cell-shaped arrays (or the wall face)
           const int hs = m->ys_open ? g.H : 0, nj = hs + g.Ny + (m->yn_open ? g.H : 1);
-          if ((s = corrector_2d_impl(m, b, -g.H, g.Nx + 2 * g.H, INT_MAX, 0, -hs, nj))) return s;
-          m->valid.void_colsums();
-          if (m->w_fly_now) {
-            if ((s = w_bases_impl(m, b, -2, g.Nx + 4, INT_MAX, 0))) return s;
-            m->w_stale = true;
-          }
+          if ((s = unswept_head(m, dim3(64, 4), Cols{-g.H, g.Nx + 2 * g.H, INT_MAX, 0}, -hs, nj,
+                                wfly ? Cols{-2, g.Nx + 4, INT_MAX, 0} : NO_COLS, false)))
+            return s;
           // (the bottom / top layers of the halo rows, which arrived with their interior levels: the fill below)
         } else {
-          dim3 b(16, 16);
-          if ((s = corrector_2d_impl(m, b, -g.H, 2 * g.H, 0, g.Nx, 0, g.Ny + 1))) return s;
-          // the chunk bases of w on the columns -2, -1 and Nx - 1, Nx, Nx + 1 (the w tiles reach two columns out)
-          if (m->w_fly_now && (s = w_bases_impl(m, b, -2, 5, 0, g.Nx - 1))) return s;
+          // ... in blocks of 16 x 16, and the chunk bases of w on the columns -2, -1 and Nx - 1, Nx, Nx + 1 (the w tiles reach two columns out)
+          if ((s = unswept_head(m, dim3(16, 16), Cols{-g.H, 2 * g.H, 0, g.Nx}, 0, g.Ny + 1,
+                                wfly ? Cols{-2, 5, 0, g.Nx - 1} : NO_COLS, false)))
+            return s;
         }
       } else if (m->Ry == 1 && (s = corrector_impl(m, true, 2))) {   // (2-D decomposition: done in stage 32)
         return s;
       }
       // (with the early strips T and S are left alone here: their layers are in place, own columns since stage 0)
       if (p_early && !strips_first) HIPCHK(hipStreamWaitEvent(m->stream, m->ev_join, 0));   // (the interior pass reads T, S)
-      if (!(m->step_lazy && strips_first) && (s = fill_halos_impl(m, false, true, 3, strips_first ? 1 : 3))) return s;
+      if (!(lazy && strips_first) && (s = fill_halos_impl(m, false, true, 3, strips_first ? 1 : 3))) return s;
       if (stage == 30) return GB25_OK;
     }
     if (p_early && !strips_first && (s = pressure_strips())) return s;   // (beside w)
-    if (!m->w_fly_now && (s = compute_w_impl(m, split ? 2 : 0))) return s;
+    if (!wfly && (s = compute_w_impl(m, split ? 2 : 0))) return s;
     if (strips_done) {
       HIPCHK(hipStreamWaitEvent(m->stream, m->ev_strips, 0));
     } else if (p_early) {
@@ -1099,12 +1089,6 @@ struct GroupOps : StepOps {
   SlabGroup& G;
   explicit GroupOps(SlabGroup& g_) : G(g_) {}
   int n() const override { return (int)G.slabs.size(); }
-  struct OnStream {   // run model calls with the model's kernels on the comm stream
-    gb25_model* m;
-    hipStream_t saved;
-    OnStream(gb25_model* m_, hipStream_t st) : m(m_), saved(m_->stream) { m->stream = st; }
-    ~OnStream() { m->stream = saved; }
-  };
   hipStream_t st(int on) const { return on == 2 ? G.sub : on == 1 ? G.comm : G.main; }
   gb25_status stage(int s, int stage, int euler, int c) override {
     OnStream on(G.slabs[s], st(c));
@@ -1118,7 +1102,7 @@ struct GroupOps : StepOps {
   bool mesh_y() override { return G.slabs[0]->Ry > 1; }
   bool lazy() override {
     for (gb25_model* m : G.slabs)
-      if (!m->step_lazy) return false;
+      if (!m->route.corrector_in_consumers()) return false;
     return true;
   }
   bool early_unpack() override {

@@ -1531,6 +1531,15 @@ gb25_status materialize_prev_uv(gb25_model* m) {
   m->prev_uv_src = 0;
   return GB25_OK;
 }
+// Adoption of the sub-cycle look-ahead: eta, U, V and the filtered state of the step that begins were made beside the last tracer
+// kernel; a pointer exchange on the host (time_step_impl; a slab: stage Update).  The velocities and T, S are adopted below.
+void adopt_subcycle(gb25_model* m) {
+  for (int q = 0; q < 3; q++) {
+    std::swap(m->f[GB25_ETA + q].d, m->ahead_eta[q].d);
+    std::swap(m->f[GB25_ETA_BAR + q].d, m->ahead_bar[q].d);
+  }
+  std::swap(m->bars, m->bars_ahead);
+}
 gb25_status ab2_velocities_impl(gb25_model* m, real dt, real chi) {
   const Grid& g = m->g;
   if (m->valid.velocities_adoptable(dt, chi)) {
@@ -2318,11 +2327,7 @@ gb25_status time_step_impl(gb25_model* m, int euler, bool more = false) {
     // the sub-cycle of this step ran in the previous one: adopt eta, U, V and the filtered state
     if (m->baro_inflight) HIPCHK(hipStreamWaitEvent(main, m->ev_baro, 0));
     m->baro_inflight = false;
-    for (int q = 0; q < 3; q++) {
-      std::swap(m->f[GB25_ETA + q].d, m->ahead_eta[q].d);
-      std::swap(m->f[GB25_ETA_BAR + q].d, m->ahead_bar[q].d);
-    }
-    std::swap(m->bars, m->bars_ahead);
+    adopt_subcycle(m);
     m->last_baro_folded = m->ahead_eta_folded;
   } else if ((s = barotropic_impl(m, (real)dt))) {
     return s;
@@ -3423,8 +3428,9 @@ gb25_status gb25_comm_init_rccl(gb25_model* m, const void* unique_id) {
   // decomposition, the fold partner -- a few bytes each, bounded by the same timeout: a peer that built another decomposition (or
   // none) shows here, with the rank and the buffer set, instead of as a hang in the first time step.
   SlabGroup* G = m->group;
-  for (int b : {0, 5, 3}) {
-    if ((b == 5 && m->Ry < 2) || (b == 3 && !m->g.cv.north_fold)) continue;
+  for (BufferSet b : {SetBundle, SetBundleRows, SetFoldBundle}) {   // (one set per Peer)
+    const Peer peer = set_info(b).peer;
+    if ((peer == Peer::Rows && m->Ry < 2) || (peer == Peer::FoldPartner && !m->g.cv.north_fold)) continue;
     const size_t nbytes = std::min<size_t>(16, G->elems[b] * sizeof(real));
     if (gb25_status s = tr->exchange(*G, b, nbytes, G->main)) return s;
     const auto t0 = std::chrono::steady_clock::now();
@@ -3432,7 +3438,7 @@ gb25_status gb25_comm_init_rccl(gb25_model* m, const void* unique_id) {
     while ((q = hipStreamQuery(G->main)) == hipErrorNotReady) {
       if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(m->comm_timeout_s))
         return fail(m, GB25_ERR_COMM, "rank %d of %d (%d x %d): the first exchange of buffer set %d (%s) did not complete within %d s",
-                    m->cfg.rank, m->cfg.nranks, m->Rx, m->Ry, b, b == 0 ? "west / east ring neighbours" : b == 5 ? "southern / northern neighbours" : "fold partner",
+                    m->cfg.rank, m->cfg.nranks, m->Rx, m->Ry, b, peer == Peer::Ring ? "west / east ring neighbours" : peer == Peer::Rows ? "southern / northern neighbours" : "fold partner",
                     m->comm_timeout_s);
       std::this_thread::sleep_for(std::chrono::milliseconds(1));
     }
@@ -3461,15 +3467,18 @@ gb25_status gb25_comm_info(const gb25_model* m, int32_t* transport, int32_t* com
 // The sends and receives ONE rank of an Rx x Ry decomposition posts for exchange group `group`, in posting order, as text:
 // "send <peer> <side>" / "recv <peer> <side>" per line ("copy" when the rank is its own fold partner).  No GPU is touched: this is
 // RcclTransport::exchange's own plan (exchange_plan).  folded_grid: the GLOBAL grid has a zipper fold (only the top row of ranks folds).
+// -1 for a `group` that is no row of the table of groups (slab_protocol.hpp).
 int64_t gb25_debug_exchange_plan(int32_t Rx, int32_t Ry, int32_t rank, int32_t folded_grid, int32_t group, char* out, int64_t cap) {
   if (Rx < 1 || Ry < 1 || rank < 0 || rank >= Rx * Ry) return -1;
   const MeshPos q(Rx, Ry, rank);
   const bool fold = folded_grid != 0 && q.ry == Ry - 1;
-  const int b = buffer_set(group);
+  const GroupInfo* info = find_group(group);
+  if (!info) return -1;
+  const Peer peer = info->peer;
   std::string log;
-  if (set_kind(b) == 1 && fold && q.partner() == rank) log = "copy\n";
-  else if (!(set_kind(b) == 1 && !fold) && !(set_kind(b) == 2 && Ry < 2))
-    for (const PlanOp& op : exchange_plan(q, fold, b)) {
+  if (peer == Peer::FoldPartner && fold && q.partner() == rank) log = "copy\n";
+  else if (!(peer == Peer::FoldPartner && !fold) && !(peer == Peer::Rows && Ry < 2))
+    for (const PlanOp& op : exchange_plan(q, fold, peer)) {
       char line[48];
       snprintf(line, sizeof line, "%s %d %d\n", op.send ? "send" : "recv", op.peer, op.side);
       log += line;

@@ -15,30 +15,35 @@
 // The sequencing itself (`sequence_time_step`) is written against an abstract StepOps so that a dry run can record the
 // order of operations without a GPU (gb25_debug_sequence; tests/test_distributed_cpu.py).
 //
-//   stage 0   AB2 update of u,v,T,S (adoption of the look-aheads), y/z layers of the 3-D bundle; pressure of the own
+//   (stages, groups, buffer sets, streams and event slots by name and number: slab_protocol.hpp; the table of groups: DESIGN.md)
+//   Update (stage 0)  AB2 update of u,v,T,S (adoption of the look-aheads), y/z layers of the 3-D bundle; pressure of the own
 //             columns starts on the slab's side stream                                            (main stream)
-//   group 0   H columns of u,v,T,S          -> x halos        packed + sent on the COMM stream, in flight during stage 2
-//   stage 2   barotropic corrector on the own columns, their y/z layers, w on the own columns, momentum tendencies of
+//   Bundle (group 0)  H columns of u,v,T,S  -> x halos        packed + sent on the COMM stream, in flight during OwnColumns
+//   OwnColumns (2)    barotropic corrector on the own columns, their y/z layers, w on the own columns, momentum tendencies of
 //             the INTERIOR tile columns                                              (main stream)
-//   stage 3   [wait for group 0] corrector in the halo columns, w and p' strips, momentum tendencies of the edge tile
+//   HaloColumns (3)   [wait for Bundle] corrector in the halo columns, w and p' strips, momentum tendencies of the edge tile
 //             columns                                                                                (main stream)
-//   stage 4   tracer tendencies                                                                     (main stream)
-//     beside stage 4, on the COMM stream, the sub-cycle of the NEXT step (its G.U, G.V exist since stage 3):
-//   group 3   W = Ns+1+H columns of eta,U,V and of the next G.U,G.V -> wide barotropic halos
-//   stage 5   Ns split-explicit substeps on the widened slab into the partner buffers of eta,U,V, filtered state; the slab
+//   Tracers (4)       tracer tendencies                                                             (main stream)
+//     beside Tracers, on the COMM stream, the sub-cycle of the NEXT step (its G.U, G.V exist since HaloColumns):
+//   BaroWideAhead (3) W = Ns+1+H columns of eta,U,V and of the next G.U,G.V -> wide barotropic halos
+//   SubcycleAhead (5) Ns split-explicit substeps on the widened slab into the partner buffers of eta,U,V, filtered state; the slab
 //             is wide enough that the x HALO columns of the new eta,U,V come out valid too: nothing is exchanged after it
-//   The next stage 0 adopts them.  When a look-ahead is not valid (first step, changed dt, host writes) the same work
-//   runs inside the step instead: group 1 (= 3), stage 1 (= 5), on the critical path.  (Group 2 -- H columns of eta,U,V --
+//   The next Update adopts them.  When a look-ahead is not valid (first step, changed dt, host writes) the same work
+//   runs inside the step instead: BaroWide (1), Subcycle (1), on the critical path.  (BaroHalo, 2 -- H columns of eta,U,V --
 //   remains for the initial state.)
 //   Folded (tripolar) grid: the work arrays of the sub-cycle are also TALL -- Wy rows beyond the pivot row, the images of the
-//   partner rank's rows south of it -- so between stage 1 / 5 (which then only copies the interiors) and the substeps
-//   (stage 16 / 56) one more exchange, group 8, carries those rows to the partner: ONE partner exchange per step for the
-//   sub-cycle, none inside it.  Group 6 is the partner exchange of the 3-D bundle's rows (and of eta, U, V).
+//   partner rank's rows south of it -- so between Subcycle / SubcycleAhead (which then only copy the interiors) and the substeps
+//   (SubcycleSubsteps 16 / SubcycleAheadSubsteps 56) one more exchange, FoldTall (8), carries those rows to the partner: ONE partner
+//   exchange per step for the sub-cycle, none inside it.  FoldBundle (6) is the partner exchange of the 3-D bundle's rows (and of
+//   eta, U, V): HaloColumnsToLayers (30) before it, HaloColumnsRest (31) after.
 //   2-D decomposition (Partition(Rx, Ry, 1), cfg.ranks_y > 1): every exchange in x is followed by the exchange of whole rows with
-//   the southern / northern neighbour, which carry the x halo columns just received (the corners): group 11 / 13 after group
-//   1 / 3 and the interior copy (the work arrays are widened in y as in x), group 10 after group 0 and the corrector of the own
-//   rows' x halo columns (stage 32: the rows arrive corrected), group 12 after group 2.  The fold partner is the mirrored rank of
-//   the top row.  No interior / edge split of the tendencies and no early pressure on such a rank.
+//   the southern / northern neighbour, which carry the x halo columns just received (the corners): BaroWideRows (11) /
+//   BaroWideRowsAhead (13) after BaroWide / BaroWideAhead and the interior copy (the work arrays are widened in y as in x),
+//   BundleRows (10) after Bundle and the corrector of the own rows' x halo columns (HaloRowsCorrector, 32: the rows arrive
+//   corrected), BaroHaloRows (12) after BaroHalo.  The fold partner is the mirrored rank of the top row.  No interior / edge split
+//   of the tendencies and no early pressure on such a rank.
+//   closure = CATKE: e and J^b travel once more per update_state!, after the step of e (CatkeColumns 20, CatkeRows 21, CatkeFold
+//   22), then CatkeFinish (41).
 #pragma once
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -47,74 +52,63 @@
 #include <string>
 #include <vector>
 
+#include "slab_protocol.hpp"
+
 // (included by gb25_api.hip after the model and its phase implementations)
 
 namespace {
 
-// ---- x-slab exchange pieces --------------------------------------------------------------------------------------
-// group 0: H columns of u, v, T, S (all parent rows) -> the neighbour's x halo.
-// group 1: W columns of eta, U, V, G.U, G.V -> the neighbour's wide barotropic halo.
-// group 2: H columns of eta, U, V -> x halos.
-// groups 3 and 4 are groups 1 and 2 of the sub-cycle LOOK-AHEAD: G.U, G.V come from the momentum look-ahead's partner
-// buffers, the new eta, U, V live in theirs.
+// ---- x-slab exchange pieces: the columns of a Mover::Columns group (what each group is: slab_protocol.hpp) --------------------
 struct Piece {
   real* src;      // array that is packed from (canonical layout)
   real* dst;      // array that is unpacked into
   int src_sx, src_xo, dst_sx, dst_xo;
   long rows;
 };
-void group_pieces(gb25_model* m, int group, std::vector<Piece>& out, int* ncols) {
+void group_pieces(gb25_model* m, Group group, std::vector<Piece>& out, int* ncols) {
   const int H = m->cfg.halo, sx = m->Nx + 2 * H;
-  if (group == 20) {
-    // closure = CATKE: the TKE tracer after its step inside compute_diffusivities!, and the filtered J^b (kappa of the first
-    // halo column is COMPUTED from them)
-    *ncols = H;
-    if (!m->catke) return;
-    for (int id : {GB25_E, GB25_JB}) {
-      Field& F = m->f[id];
-      out.push_back({F.d, F.d, sx, H, sx, H, (long)F.ny * F.nz});
-    }
-    return;
-  }
-  if (group == 0 || group == 2 || group == 4) {
-    *ncols = H;
-    if (group == 0) {
-      for (int id : {GB25_U, GB25_V, GB25_T, GB25_S}) {
-        Field& F = m->f[id];
-        out.push_back({F.d, F.d, sx, H, sx, H, (long)F.ny * F.nz});
-      }
+  auto whole = [&](real* p, long rows) { out.push_back({p, p, sx, H, sx, H, rows}); };   // H columns, unpacked where they came from
+  *ncols = H;
+  switch (group) {
+    case Group::CatkeColumns:
+      // the TKE tracer after its step inside compute_diffusivities!, and the filtered J^b (kappa of the first halo column is
+      // COMPUTED from them)
+      if (!m->catke) return;
+      for (int id : {GB25_E, GB25_JB}) whole(m->f[id].d, (long)m->f[id].ny * m->f[id].nz);
+      return;
+    case Group::Bundle:
+      for (int id : {GB25_U, GB25_V, GB25_T, GB25_S}) whole(m->f[id].d, (long)m->f[id].ny * m->f[id].nz);
       // the column integrals of u, v (the corrector's): the receiver corrects its halo columns cell by cell with them
-      for (int q = 0; q < 2; q++) out.push_back({m->colsum[q].d, m->colsum[q].d, sx, H, sx, H, (long)m->colsum[q].ny});
+      for (int q = 0; q < 2; q++) whole(m->colsum[q].d, (long)m->colsum[q].ny);
       // ... and their sums over the momentum kernel's chunks of levels (w on the fly: the chunk bases of w next to the x halos)
       if (slab_wfly_ok(m)) {
         const int kch = mom_kchunks(m);
         const long plane2 = (long)m->g.sx * m->g.sy_v;
-        for (int q = 2; q < 4; q++) {
-          real* P = m->uv_partials + (long)q * kch * plane2;
-          out.push_back({P, P, sx, H, sx, H, (long)kch * m->g.sy_v});
-        }
+        for (int q = 2; q < 4; q++) whole(m->uv_partials + (long)q * kch * plane2, (long)kch * m->g.sy_v);
       }
-    } else {
+      return;
+    case Group::BaroHalo:
+      for (int q = 0; q < 3; q++) whole(m->f[GB25_ETA + q].d, (long)m->f[GB25_ETA + q].ny * m->f[GB25_ETA + q].nz);
+      return;
+    case Group::BaroWide:
+    case Group::BaroWideAhead: {
+      *ncols = m->W;
+      const int wsx = m->Nx + 2 * m->W;
+      const size_t up = (size_t)m->Wys * wsx;   // (2-D decomposition: the work arrays start Wys rows below the canonical ones)
       for (int q = 0; q < 3; q++) {
-        Field& F = group == 2 ? m->f[GB25_ETA + q] : m->ahead_eta[q];
-        out.push_back({F.d, F.d, sx, H, sx, H, (long)F.ny * F.nz});
+        Field& F = m->f[GB25_ETA + q];
+        out.push_back({F.d, m->wide[0][q].d + up, sx, H, wsx, m->W, (long)F.ny});
       }
+      for (int q = 0; q < 2; q++) {
+        Field& F = group == Group::BaroWide ? m->f[GB25_GN_BT_U + q] : m->ahead_G[q];
+        out.push_back({F.d, m->wideG[q].d + up, sx, H, wsx, m->W, (long)F.ny});
+      }
+      return;
     }
-  } else {
-    *ncols = m->W;
-    const int wsx = m->Nx + 2 * m->W;
-    const size_t up = (size_t)m->Wys * wsx;   // (2-D decomposition: the work arrays start Wys rows below the canonical ones)
-    for (int q = 0; q < 3; q++) {
-      Field& F = m->f[GB25_ETA + q];
-      out.push_back({F.d, m->wide[0][q].d + up, sx, H, wsx, m->W, (long)F.ny});
-    }
-    for (int q = 0; q < 2; q++) {
-      Field& F = group == 1 ? m->f[GB25_GN_BT_U + q] : m->ahead_G[q];
-      out.push_back({F.d, m->wideG[q].d + up, sx, H, wsx, m->W, (long)F.ny});
-    }
+    default: return;   // (no columns: the unused groups and those of the other movers)
   }
 }
-int64_t halo_buffer_elems(gb25_model* m, int group) {
+int64_t halo_buffer_elems(gb25_model* m, Group group) {
   std::vector<Piece> ps;
   int nc = 0;
   group_pieces(m, group, ps, &nc);
@@ -123,7 +117,7 @@ int64_t halo_buffer_elems(gb25_model* m, int group) {
   return t > 0 ? t : 1;
 }
 // Both sides of a group in ONE launch (a group is up to ten small strips); buf[side] = that side's contiguous buffer.
-gb25_status pack_unpack(gb25_model* m, int group, real* const buf[2], bool pack) {
+gb25_status pack_unpack(gb25_model* m, Group group, real* const buf[2], bool pack) {
   std::vector<Piece> ps;
   int nc = 0;
   group_pieces(m, group, ps, &nc);
@@ -153,13 +147,11 @@ gb25_status pack_unpack(gb25_model* m, int group, real* const buf[2], bool pack)
 }
 
 // ---- y halos of a 2-D (x, y) decomposition: whole rows (every parent column) to the southern / northern neighbour ------------
-// group 10: H rows of u, v, T, S (interior levels) -- after group 0 and the barotropic corrector of the own rows (x halo columns
-//           included: the corners), so that the rows arrive corrected, as the rows beyond a fold do (group 6);
-// group 11: W rows of the sub-cycle's work arrays eta, U, V, G.U, G.V (all widened columns) -- after group 1 and the interior copy;
-// group 12: H rows of eta, U, V (initial state) -- after group 2.      13, 14: the same for the sub-cycle look-ahead.
+// BundleRows travels after Bundle and the barotropic corrector of the own rows (x halo columns included: the corners), so that the
+// rows arrive corrected, as the rows beyond a fold do (FoldBundle); BaroWideRows after BaroWide and the interior copy.
 // side 0: southern edge / halo, side 1: northern.  Rows [0, n) / [Ny - n, Ny) are packed, [-n, 0) / [Ny, Ny + n) unpacked.
 inline bool y_neighbour(const gb25_model* m, int side) { return side == 0 ? m->ys_open : m->yn_open; }
-void row_pieces(gb25_model* m, int group, int side, bool pack, real* buf, RowPieces& P) {
+void row_pieces(gb25_model* m, Group group, int side, bool pack, real* buf, RowPieces& P) {
   const Grid& g = m->g;
   const int H = g.H;
   P = RowPieces{};
@@ -171,36 +163,44 @@ void row_pieces(gb25_model* m, int group, int side, bool pack, real* buf, RowPie
     P.nrows = nrows;
     off += (size_t)nz * nrows * sx;
   };
-  if (group == 21) {   // (CATKE: the TKE tracer after its step, and J^b for kappa in the first halo row)
-    if (m->catke) {
-      Field& F = m->f[GB25_E];
-      add(F.d, g.sx, H, (long)g.sx * F.ny, H, g.Nz, H);
-      add(m->f[GB25_JB].d, g.sx, H, 0, 0, 1, H);
-    }
-  } else if (group == 10) {
-    for (int id : {GB25_U, GB25_V, GB25_T, GB25_S}) {
-      Field& F = m->f[id];
-      add(F.d, g.sx, H, (long)g.sx * F.ny, H, g.Nz, H);
-    }
-    if (slab_lazy_ok(m)) {
-      // the corrector inside its consumers: the column integrals of u, v of the rows (the receiver's du, dv there) and, for w on
-      // the fly, their sums over the chunks of levels
-      for (int q = 0; q < 2; q++) add(m->colsum[q].d, g.sx, H, 0, 0, 1, H);
-      if (slab_wfly_ok(m)) {
-        const int kch = mom_kchunks(m);
-        const long plane2 = (long)g.sx * g.sy_v;
-        for (int q = 2; q < 4; q++) add(m->uv_partials + (long)q * kch * plane2, g.sx, H, plane2, 0, kch, H);
+  switch (group) {
+    case Group::CatkeRows:   // (the TKE tracer after its step, and J^b for kappa in the first halo row)
+      if (m->catke) {
+        Field& F = m->f[GB25_E];
+        add(F.d, g.sx, H, (long)g.sx * F.ny, H, g.Nz, H);
+        add(m->f[GB25_JB].d, g.sx, H, 0, 0, 1, H);
       }
+      return;
+    case Group::BundleRows:
+      for (int id : {GB25_U, GB25_V, GB25_T, GB25_S}) {
+        Field& F = m->f[id];
+        add(F.d, g.sx, H, (long)g.sx * F.ny, H, g.Nz, H);
+      }
+      if (slab_lazy_ok(m)) {
+        // the corrector inside its consumers: the column integrals of u, v of the rows (the receiver's du, dv there) and, for w on
+        // the fly, their sums over the chunks of levels
+        for (int q = 0; q < 2; q++) add(m->colsum[q].d, g.sx, H, 0, 0, 1, H);
+        if (slab_wfly_ok(m)) {
+          const int kch = mom_kchunks(m);
+          const long plane2 = (long)g.sx * g.sy_v;
+          for (int q = 2; q < 4; q++) add(m->uv_partials + (long)q * kch * plane2, g.sx, H, plane2, 0, kch, H);
+        }
+      }
+      return;
+    case Group::BaroWideRows:
+    case Group::BaroWideRowsAhead: {
+      const int wsx = g.Nx + 2 * m->W;
+      for (int q = 0; q < 3; q++) add(m->wide[0][q].d, wsx, H + m->Wys, 0, 0, 1, m->W);
+      for (int q = 0; q < 2; q++) add(m->wideG[q].d, wsx, H + m->Wys, 0, 0, 1, m->W);
+      return;
     }
-  } else if (group == 11 || group == 13) {
-    const int wsx = g.Nx + 2 * m->W;
-    for (int q = 0; q < 3; q++) add(m->wide[0][q].d, wsx, H + m->Wys, 0, 0, 1, m->W);
-    for (int q = 0; q < 2; q++) add(m->wideG[q].d, wsx, H + m->Wys, 0, 0, 1, m->W);
-  } else {
-    for (int q = 0; q < 3; q++) add((group == 12 ? m->f[GB25_ETA + q] : m->ahead_eta[q]).d, g.sx, H, 0, 0, 1, H);
+    case Group::BaroHaloRows:
+      for (int q = 0; q < 3; q++) add(m->f[GB25_ETA + q].d, g.sx, H, 0, 0, 1, H);
+      return;
+    default: return;   // (no rows: the unused groups and those of the other movers)
   }
 }
-int64_t row_buffer_elems(gb25_model* m, int group) {
+int64_t row_buffer_elems(gb25_model* m, Group group) {
   if (m->Ry < 2) return 1;
   RowPieces P;
   row_pieces(m, group, 0, true, nullptr, P);
@@ -208,7 +208,7 @@ int64_t row_buffer_elems(gb25_model* m, int group) {
   for (int f = 0; f < P.n; f++) t += (int64_t)P.nz[f] * P.nrows * P.sx[f];
   return t > 0 ? t : 1;
 }
-gb25_status move_rows(gb25_model* m, int group, real* const buf[2], bool pack) {
+gb25_status move_rows(gb25_model* m, Group group, real* const buf[2], bool pack) {
   for (int side = 0; side < 2; side++) {
     if (!y_neighbour(m, side)) continue;
     RowPieces P;
@@ -225,10 +225,8 @@ gb25_status move_rows(gb25_model* m, int group, real* const buf[2], bool pack) {
 }
 
 // ---- zipper fold of a decomposed tripolar grid: the partner rank P-1-r holds the cells beyond this slab's fold line -----
-// buffer set 3: the H rows south of the pivot row of u, v, T, S (CATKE: e, J^b too) and eta, U, V (all parent
-// columns, interior levels);
-// buffer set 4: the Wy (+1) rows south of the pivot row of the sub-cycle's work arrays eta, U, V, G.U, G.V (TallRows, kernels.hpp)
-FoldFields fold_fields(gb25_model* m, bool closure = false) {   // closure: group 22 -- e and J^b after the e step
+// FoldBundle, CatkeFold: H rows south of the pivot row (all parent columns, interior levels); FoldTall: TallRows, kernels.hpp
+FoldFields fold_fields(gb25_model* m, bool closure = false) {   // closure: CatkeFold -- e and J^b after the e step
   FoldFields F{};
   const Grid& g = m->g;
   long off = 0;
@@ -258,11 +256,20 @@ int fold_levels(const FoldFields& F, bool with_layers) {   // blockIdx.z extent 
   for (int f = 0; f < F.n; f++) t += F.nz[f] == 1 ? 1 : F.nz[f] + (with_layers ? 2 : 0);
   return t;
 }
-int64_t fold_buffer_elems(gb25_model* m, int b) {
+int64_t fold_buffer_elems(gb25_model* m, bool closure) {
   const Grid& g = m->g;
-  if (!g.cv.north_fold) return 1;
-  if (b == 10) return std::max<int64_t>(1, (int64_t)g.H * g.sx * fold_levels(fold_fields(m, true), false));
-  return b == 3 ? (int64_t)g.H * g.sx * fold_levels(fold_fields(m), false) : tall_buffer_elems(m);
+  return std::max<int64_t>(1, (int64_t)g.H * g.sx * fold_levels(fold_fields(m, closure), false));
+}
+// Elements per side of buffer set b on this slab: what the set's group packs (the others of the set carry pieces of the same sizes)
+int64_t set_elems(gb25_model* m, BufferSet b) {
+  const GroupInfo& info = set_info(b);
+  switch (info.mover) {
+    case Mover::Columns: return halo_buffer_elems(m, info.group);
+    case Mover::Rows: return row_buffer_elems(m, info.group);
+    case Mover::FoldRows: return m->g.cv.north_fold ? fold_buffer_elems(m, info.closure) : 1;
+    case Mover::TallRows: return m->g.cv.north_fold ? tall_buffer_elems(m) : 1;
+  }
+  return 1;
 }
 gb25_status fold_pack(gb25_model* m, real* buf, bool closure = false) {
   const Grid& g = m->g;
@@ -290,7 +297,7 @@ inline bool strips_on_comm(const gb25_model* m) {
 
 // closure = CATKE on a rank of a decomposition.  compute_diffusivities! steps e on the own columns (time_step_catke_equation!)
 // and filters J^b there; the diffusivities of the first halo column / row and the advection of e then need the NEW e and J^b of
-// the neighbours: one more exchange per update_state! (groups 20: x columns, 21: rows of a 2-D decomposition, 22: the rows
+// the neighbours: one more exchange per update_state! (CatkeColumns: x columns, CatkeRows: rows of a 2-D decomposition, CatkeFold: the rows
 // beyond a zipper fold), between these two halves.
 gb25_status catke_step_local(gb25_model* m) {
   gb25_status s;
@@ -304,219 +311,246 @@ gb25_status catke_finish_local(gb25_model* m) {
   return catke_tendency_impl(m);
 }
 
-// ---- the stages of one slab's time step (see the header of this file) -------------------------------------------------
-gb25_status slab_stage(gb25_model* m, int stage, int euler) {
+// ---- the stages of one slab's time step (see the header of this file): one function per family, slab_stage picks the sub-case ----
+// own columns' pressure early, on the side stream.  (A folded slab too: the pressure of a cell and its differences to the west
+// and south never look north -- what arrives last, the rows beyond the fold, is no input of theirs; the pressure of halo cells
+// is not stored inside a composite step.)
+// (a rank of a 2-D decomposition computes its pressure in one pass once all halos are in: the early pass plus a one-row strip
+// for the y difference of row 0 measured slower on the one-rank proxy, 0.566 against 0.537 ms -- profiles/r03_tuning_log.md)
+inline bool pressure_early(const gb25_model* m) { return m->two_streams && m->pressure_bits == 64 && m->Ry == 1; }
+// Forks to the slab's side stream: the pressure of the columns [i0, i1] and [i0b, i1b] there, beside what the calling stream goes on
+// with; ev_join marks its end.
+gb25_status pressure_on_side_stream(gb25_model* m, int i0, int i1, int i0b, int i1b) {
+  HIPCHK(hipEventRecord(m->ev_fork, m->stream));
+  HIPCHK(hipStreamWaitEvent(m->side_stream, m->ev_fork, 0));
+  {
+    OnStream on(m, m->side_stream);
+    if (gb25_status s = compute_p_impl(m, i0, i1, i0b, i1b, true)) return s;
+  }
+  HIPCHK(hipEventRecord(m->ev_join, m->side_stream));
+  return GB25_OK;
+}
+
+// Update: AB2 update of u,v,T,S + barotropic forcing, then the y/z boundary layers of the 3-D bundle so that its packed x columns
+// (Bundle) can travel WHILE the own columns are corrected
+gb25_status stage_update(gb25_model* m, int euler) {
   const Grid& g = m->g;
   gb25_status s;
   const double dt = m->last_dt;
   const real chi = euler ? -real(0.5) : (real)m->cfg.chi;
-  const bool split = tendencies_split(m);
-  // own columns' pressure early, on the side stream.  (A folded slab too: the pressure of a cell and its differences to the west
-  // and south never look north -- what arrives last, the rows beyond the fold, is no input of theirs; the pressure of halo cells
-  // is not stored inside a composite step.)
-  // (a rank of a 2-D decomposition computes its pressure in one pass once all halos are in: the early pass plus a one-row strip
-  // for the y difference of row 0 measured slower on the one-rank proxy, 0.566 against 0.537 ms -- profiles/r03_tuning_log.md)
-  const bool p_early = m->two_streams && m->pressure_bits == 64 && m->Ry == 1;
-  if (stage == 0) {
-    // AB2 update of u,v,T,S + barotropic forcing, then the y/z boundary layers of the 3-D bundle so that its packed
-    // x columns (group 0) can travel WHILE the own columns are corrected
-    const bool uv_adopted = m->valid.velocities_adoptable((real)dt, chi);
-    m->baro_adopted = uv_adopted && m->valid.ahead_baro_valid;
-    m->valid.void_subcycle_lookahead();
-    // The corrector inside its consumers (as on a single domain, time_step_impl): when everything this step needs was made
-    // ahead of time, no sweep over u and v -- 2-D kernels leave du, dv (own columns in stage 2, halo columns in stage 3 from the
-    // column integrals the bundle carries) and the kernels that read u, v add them.  Memory holds the uncorrected velocities
-    // until the composite call returns (gb25_loop).
-    // ... and with it w on the fly: no k_compute_w launch, the tendency kernels carry w up their chunks of levels from 2-D bases
-    const Corrector corrector = choose_corrector(m, false, uv_adopted, m->baro_adopted);
-    if (corrector == Corrector::Sweep && (s = materialize_uv(m))) return s;   // (the sweeps below expect corrected velocities)
-    m->route.begin(corrector, route_carries_w(m, corrector));
-    if ((s = ab2_local_impl(m, (real)dt, chi))) return s;
-    if (m->baro_adopted) {
-      // the sub-cycle of this step, its wide-halo exchange and the exchange of the new eta, U, V columns all ran
-      // beside the last tracer kernel (stage 5): adopt the results, stage 1 and groups 1, 2 are skipped
-      for (int q = 0; q < 3; q++) {
-        std::swap(m->f[GB25_ETA + q].d, m->ahead_eta[q].d);
-        std::swap(m->f[GB25_ETA_BAR + q].d, m->ahead_bar[q].d);
-      }
-      std::swap(m->bars, m->bars_ahead);
-      m->time += dt;
-      m->iteration += 1;
-    }
-    if ((s = fill_halos_impl(m, false, false, 1))) return s;
-    if (p_early) {
-      // T, S of the slab's own columns are final from here on: their pressure (fp64-bound) runs on the side stream
-      // beside the exchanges and the sub-cycle; the strips next to the x halos follow in stage 3.  The first x
-      // difference of this pass reads a stale halo column and is redone by the west strip.
-      HIPCHK(hipEventRecord(m->ev_fork, m->stream));
-      HIPCHK(hipStreamWaitEvent(m->side_stream, m->ev_fork, 0));
-      {
-        OnStream on(m, m->side_stream);
-        if ((s = compute_p_impl(m, 0, g.Nx - 1, 0, -1, true))) return s;
-      }
-      HIPCHK(hipEventRecord(m->ev_join, m->side_stream));
-    }
-    return GB25_OK;
-  } else if (stage == 1 || stage == 5 || stage == 16 || stage == 56) {
-    // stage 1: group 1 has been unpacked into the wide halos: copy the interiors, sub-cycle, publish.
-    // stage 5: the same for the NEXT step (look-ahead): group 3 has been unpacked, G.U, G.V come from the momentum
-    //          look-ahead, the results go to the partner buffers of eta, U, V and of the filtered state.
-    // Folded grid: stage 1 / 5 end after the interior copy (the image rows beyond the pivot row travel next: group 8),
-    // stage 16 / 56 do the rest.
-    const bool ahead = stage == 5 || stage == 56, second_half = stage == 16 || stage == 56;
-    if (ahead && !m->valid.ahead_uv_valid) return fail(m, GB25_ERR_STATE, "stage 5 without a velocity look-ahead");
-    if (!ahead && m->baro_adopted) return fail(m, GB25_ERR_STATE, "stage 1 after stage 0 adopted the sub-cycle");
-    std::vector<Piece> ps;
-    int nc = 0;
-    group_pieces(m, ahead ? 3 : 1, ps, &nc);
-    const bool two_halves = g.cv.north_fold || m->Ry > 1;   // (more rows of the work arrays travel between the copy and the substeps)
-    InteriorCopies C{};
-    if (!second_half) {
-      int rmax = 0;
-      for (auto& p : ps) {
-        const int q = C.n++;
-        C.dst[q] = p.dst; C.dsx[q] = p.dst_sx; C.dxo[q] = p.dst_xo;
-        C.src[q] = p.src; C.ssx[q] = p.src_sx; C.sxo[q] = p.src_xo; C.rows[q] = (int)p.rows;
-        rmax = std::max(rmax, (int)p.rows);
-      }
-      // (a plain slab hands the copy to the sub-cycle: its one-launch kernel reads the own columns where they are)
-      if (two_halves)
-        hipLaunchKernelGGL(k_copy_interior_columns, dim3((g.Nx + 255) / 256, rmax, C.n), dim3(256), 0, m->stream, C, g.Nx);
-    }
-    LAUNCHCHK();
-    if (two_halves && !second_half) return GB25_OK;
-    const InteriorCopies* own = two_halves ? nullptr : &C;
-    bool layers_done = false;
-    if (ahead) {
-      if ((s = barotropic_impl(m, m->valid.ahead_uv_dt, true, own, &layers_done))) return s;
-      Halo2 h2{};
-      for (int q = 0; q < 3; q++) { h2.p[q] = m->ahead_eta[q].d; h2.is_v[q] = q == 2; }
-      h2.n = 3;
-      // y layer, x halo columns included: the widened sub-cycle computed those like the neighbour did (no group 4)
-      if (!layers_done && (s = fill_halos_impl(m, false, true, 2, 3, nullptr, true, &h2))) return s;
-      m->valid.record_subcycle_lookahead();
-      return GB25_OK;
-    }
-    if ((s = barotropic_impl(m, (real)dt, false, own, &layers_done))) return s;
+  const bool uv_adopted = m->valid.velocities_adoptable((real)dt, chi);
+  m->baro_adopted = uv_adopted && m->valid.ahead_baro_valid;
+  m->valid.void_subcycle_lookahead();
+  // The corrector inside its consumers (as on a single domain, time_step_impl): when everything this step needs was made
+  // ahead of time, no sweep over u and v -- 2-D kernels leave du, dv (own columns in OwnColumns, halo columns in HaloColumns from
+  // the column integrals the bundle carries) and the kernels that read u, v add them.  Memory holds the uncorrected velocities
+  // until the composite call returns (gb25_loop).
+  // ... and with it w on the fly: no k_compute_w launch, the tendency kernels carry w up their chunks of levels from 2-D bases
+  const Corrector corrector = choose_corrector(m, false, uv_adopted, m->baro_adopted);
+  if (corrector == Corrector::Sweep && (s = materialize_uv(m))) return s;   // (the sweeps below expect corrected velocities)
+  m->route.begin(corrector, route_carries_w(m, corrector));
+  if ((s = ab2_local_impl(m, (real)dt, chi))) return s;
+  if (m->baro_adopted) {
+    // the sub-cycle of this step, its wide-halo exchange and the exchange of the new eta, U, V columns all ran beside the last
+    // tracer kernel (SubcycleAhead): adopt the results, Subcycle and BaroWide are skipped
+    adopt_subcycle(m);
     m->time += dt;
     m->iteration += 1;
-    // y layer of the new eta, U, V, x halo columns included (computed by the widened sub-cycle: no group 2)
-    return layers_done ? GB25_OK : fill_halos_impl(m, false, true, 2);
-  } else if (stage == 2 || stage == 20) {
-    // Everything that needs nothing from the neighbours runs while the exchanges are in flight: the barotropic
-    // corrector on the slab's own columns and, when the tendency kernels are split (a12), the y/z layers and w of the
-    // own columns and the momentum tendencies of the interior tile columns.
-    // (stage 20: the head of a lazy step -- du, dv and the chunk bases of w -- ahead of the wait for the packed bundle)
-    const bool lazy = m->route.corrector_in_consumers(), wfly = m->route.kernels_carry_w();
-    if (stage == 2 && m->route.head_is_done()) {
-      // (stage 20 did the corrector's part)
-    } else if (lazy) {
-      if (stage == 20) m->route.head_done();
-      if (!m->valid.colsum_valid) return fail(m, GB25_ERR_STATE, "internal: a lazy step without the column integrals of u, v");
-      Timed t(m, GB25_K_CORRECTOR);
-      // (a rank of a 2-D decomposition has no interior pass: du, dv and the chunk bases of w over its whole extended range at
-      // once, in stage 3, when every halo is in)
-      // chunk bases of w on the columns [0, Nx - 2] (their u faces are own columns), before the interior momentum pass
-      // overwrites the chunk sums they are made from
-      const bool own = m->Ry == 1;
-      if ((s = unswept_head(m, dim3(64, 4), own ? Cols{0, g.Nx, INT_MAX, 0} : NO_COLS, 0, g.Ny + 1,
-                            own && wfly ? Cols{0, g.Nx - 1, INT_MAX, 0} : NO_COLS, true)))
-        return s;
-    } else if ((s = corrector_impl(m, true, 1))) {
+  }
+  if ((s = fill_halos_impl(m, false, false, 1))) return s;
+  // T, S of the slab's own columns are final from here on: their pressure (fp64-bound) runs on the side stream beside the
+  // exchanges and the sub-cycle; the strips next to the x halos follow in HaloColumns.  The first x difference of this pass reads
+  // a stale halo column and is redone by the west strip.
+  return pressure_early(m) ? pressure_on_side_stream(m, 0, g.Nx - 1, 0, -1) : GB25_OK;
+}
+
+// Subcycle: BaroWide has been unpacked into the wide halos: copy the interiors, sub-cycle, publish.
+// ahead: the same for the NEXT step: BaroWideAhead has been unpacked, G.U, G.V come from the momentum look-ahead, the results go
+//        to the partner buffers of eta, U, V and of the filtered state.
+// Fold / 2-D decomposition: the first call ends after the interior copy (more rows of the work arrays travel next: FoldTall,
+// BaroWideRows), a second one with substeps_only does the rest.
+gb25_status stage_subcycle(gb25_model* m, bool ahead, bool substeps_only) {
+  const Grid& g = m->g;
+  gb25_status s;
+  const double dt = m->last_dt;
+  if (ahead && !m->valid.ahead_uv_valid) return fail(m, GB25_ERR_STATE, "stage 5 without a velocity look-ahead");
+  if (!ahead && m->baro_adopted) return fail(m, GB25_ERR_STATE, "stage 1 after stage 0 adopted the sub-cycle");
+  std::vector<Piece> ps;
+  int nc = 0;
+  group_pieces(m, ahead ? Group::BaroWideAhead : Group::BaroWide, ps, &nc);
+  const bool two_halves = g.cv.north_fold || m->Ry > 1;
+  InteriorCopies C{};
+  if (!substeps_only) {
+    int rmax = 0;
+    for (auto& p : ps) {
+      const int q = C.n++;
+      C.dst[q] = p.dst; C.dsx[q] = p.dst_sx; C.dxo[q] = p.dst_xo;
+      C.src[q] = p.src; C.ssx[q] = p.src_sx; C.sxo[q] = p.src_xo; C.rows[q] = (int)p.rows;
+      rmax = std::max(rmax, (int)p.rows);
+    }
+    // (a plain slab hands the copy to the sub-cycle: its one-launch kernel reads the own columns where they are)
+    if (two_halves)
+      hipLaunchKernelGGL(k_copy_interior_columns, dim3((g.Nx + 255) / 256, rmax, C.n), dim3(256), 0, m->stream, C, g.Nx);
+  }
+  LAUNCHCHK();
+  if (two_halves && !substeps_only) return GB25_OK;
+  const InteriorCopies* own = two_halves ? nullptr : &C;
+  bool layers_done = false;
+  if (ahead) {
+    if ((s = barotropic_impl(m, m->valid.ahead_uv_dt, true, own, &layers_done))) return s;
+    Halo2 h2{};
+    for (int q = 0; q < 3; q++) { h2.p[q] = m->ahead_eta[q].d; h2.is_v[q] = q == 2; }
+    h2.n = 3;
+    // y layer, x halo columns included: the widened sub-cycle computed those like the neighbour did (no BaroHaloAhead)
+    if (!layers_done && (s = fill_halos_impl(m, false, true, 2, 3, nullptr, true, &h2))) return s;
+    m->valid.record_subcycle_lookahead();
+    return GB25_OK;
+  }
+  if ((s = barotropic_impl(m, (real)dt, false, own, &layers_done))) return s;
+  m->time += dt;
+  m->iteration += 1;
+  // y layer of the new eta, U, V, x halo columns included (computed by the widened sub-cycle: no BaroHalo)
+  return layers_done ? GB25_OK : fill_halos_impl(m, false, true, 2);
+}
+
+// OwnColumns: everything that needs nothing from the neighbours runs while the exchanges are in flight: the barotropic corrector
+// on the slab's own columns and, when the tendency kernels are split (a12), the y/z layers and w of the own columns and the
+// momentum tendencies of the interior tile columns.
+// head_only (LazyHead): the head of a lazy step -- du, dv and the chunk bases of w -- ahead of the wait for the packed bundle
+gb25_status stage_own_columns(gb25_model* m, bool head_only) {
+  const Grid& g = m->g;
+  gb25_status s;
+  const bool lazy = m->route.corrector_in_consumers(), wfly = m->route.kernels_carry_w();
+  if (!head_only && m->route.head_is_done()) {
+    // (LazyHead did the corrector's part)
+  } else if (lazy) {
+    if (head_only) m->route.head_done();
+    if (!m->valid.colsum_valid) return fail(m, GB25_ERR_STATE, "internal: a lazy step without the column integrals of u, v");
+    Timed t(m, GB25_K_CORRECTOR);
+    // (a rank of a 2-D decomposition has no interior pass: du, dv and the chunk bases of w over its whole extended range at
+    // once, in HaloColumns, when every halo is in)
+    // chunk bases of w on the columns [0, Nx - 2] (their u faces are own columns), before the interior momentum pass
+    // overwrites the chunk sums they are made from
+    const bool own = m->Ry == 1;
+    if ((s = unswept_head(m, dim3(64, 4), own ? Cols{0, g.Nx, INT_MAX, 0} : NO_COLS, 0, g.Ny + 1,
+                          own && wfly ? Cols{0, g.Nx - 1, INT_MAX, 0} : NO_COLS, true)))
+      return s;
+  } else if ((s = corrector_impl(m, true, 1))) {
+    return s;
+  }
+  if (head_only || !tendencies_split(m)) return GB25_OK;
+  // y/z layers of the corrected u, v, own columns (lazy: the layers of the uncorrected ones are in place since Update)
+  if (!lazy && (s = fill_halos_impl(m, false, false, 1, 1))) return s;
+  if (!wfly && (s = compute_w_impl(m, 1))) return s;
+  HIPCHK(hipStreamWaitEvent(m->stream, m->ev_join, 0));       // the own columns' pressure differences (side stream)
+  return momentum_impl(m, 1);
+}
+
+// StripsOnComm (issued on the exchange stream behind the unpack of Bundle): the two pressure strips: T, S of the halo columns are
+// in; the interior pass of Update (side stream: event ev_join) must be over -- the west strip redoes its column 0
+gb25_status stage_strips(gb25_model* m) {
+  const Grid& g = m->g;
+  HIPCHK(hipStreamWaitEvent(m->stream, m->ev_join, 0));
+  if (gb25_status s = compute_p_impl(m, -g.H + 1, 0, g.Nx, g.Nx + g.H - 2, true)) return s;
+  HIPCHK(hipEventRecord(m->ev_strips, m->stream));
+  m->strips_issued = true;
+  return GB25_OK;
+}
+
+// HaloRowsCorrector (2-D decomposition): Bundle has been unpacked; the corrector on the x-halo columns of the own rows, so that the
+// rows that leave for the southern / northern neighbour next (BundleRows) are corrected over their whole width
+// (a lazy step: the rows leave uncorrected, like the columns; the receiver makes du, dv of its halo rows itself)
+gb25_status stage_halo_rows_corrector(gb25_model* m) {
+  return m->route.corrector_in_consumers() ? GB25_OK : corrector_impl(m, true, 2);
+}
+
+// HaloColumns: Bundle has been unpacked: corrector on the x-halo columns, then update_state without any further exchange (y/z
+// layers re-filled over the extended x range; w and p recomputed in the halos).
+// Folded grid: first_part = up to the y/z layers, then the rows beyond the fold arrive from the partner, second_part = the rest.
+gb25_status stage_halo_columns(gb25_model* m, bool first_part, bool second_part) {
+  const Grid& g = m->g;
+  gb25_status s;
+  const bool split = tendencies_split(m), p_early = pressure_early(m);
+  // (a closure's fields travel in the bundle as well and its fills follow: the strips keep their old place behind them)
+  const bool strips_first = p_early && !m->catke;
+  const bool lazy = m->route.corrector_in_consumers(), wfly = m->route.kernels_carry_w();
+  const bool strips_done = m->strips_issued;   // (StripsOnComm ran them on the exchange stream)
+  if (second_part) m->strips_issued = false;
+  // west strip (redoes column 0) + east strip
+  auto pressure_strips = [&] { return pressure_on_side_stream(m, -g.H + 1, 0, g.Nx, g.Nx + g.H - 2); };
+  if (first_part) {
+    // the two pressure strips next to the x halos start as soon as the bundle is unpacked: T, S of the halo columns arrived
+    // complete (their y/z layers were filled by their owner before it packed them), and the side stream runs them behind the
+    // interior pass of Update -- beside the corrector, the fills and w of the edge strips instead of after them
+    if (strips_first && !strips_done && (s = pressure_strips())) return s;
+    if (lazy) {
+      // du, dv of the x halo columns: the neighbours' column integrals came with the bundle, the new U, V of those columns
+      // from the widened sub-cycle; their y/z layers of u, v arrived filled -- nothing else to do
+      if (!m->valid.halo_colsum_valid) return fail(m, GB25_ERR_STATE, "internal: a lazy step without the neighbours' column integrals");
+      if (m->Ry > 1) {
+        // 2-D decomposition: everything at once -- own cells, halo columns, halo rows of the open sides (corners included)
+        // rows: from the southern halo rows (or row 0) to the last northern halo row of the cell-shaped arrays (or the wall face)
+        const int hs = m->ys_open ? g.H : 0, nj = hs + g.Ny + (m->yn_open ? g.H : 1);
+        if ((s = unswept_head(m, dim3(64, 4), Cols{-g.H, g.Nx + 2 * g.H, INT_MAX, 0}, -hs, nj,
+                              wfly ? Cols{-2, g.Nx + 4, INT_MAX, 0} : NO_COLS, false)))
+          return s;
+        // (the bottom / top layers of the halo rows, which arrived with their interior levels: the fill below)
+      } else {
+        // ... in blocks of 16 x 16, and the chunk bases of w on the columns -2, -1 and Nx - 1, Nx, Nx + 1 (the w tiles reach two columns out)
+        if ((s = unswept_head(m, dim3(16, 16), Cols{-g.H, 2 * g.H, 0, g.Nx}, 0, g.Ny + 1,
+                              wfly ? Cols{-2, 5, 0, g.Nx - 1} : NO_COLS, false)))
+          return s;
+      }
+    } else if (m->Ry == 1 && (s = corrector_impl(m, true, 2))) {   // (2-D decomposition: done in HaloRowsCorrector)
       return s;
     }
-    if (stage == 20 || !split) return GB25_OK;
-    // y/z layers of the corrected u, v, own columns (lazy: the layers of the uncorrected ones are in place since stage 0)
-    if (!lazy && (s = fill_halos_impl(m, false, false, 1, 1))) return s;
-    if (!wfly && (s = compute_w_impl(m, 1))) return s;
-    HIPCHK(hipStreamWaitEvent(m->stream, m->ev_join, 0));       // the own columns' pressure differences (side stream)
-    return momentum_impl(m, 1);
-  } else if (stage == 33) {
-    // (issued on the exchange stream behind the unpack of group 0) the two pressure strips: T, S of the halo columns are in; the
-    // interior pass of stage 0 (side stream: event ev_join) must be over -- the west strip redoes its column 0
-    HIPCHK(hipStreamWaitEvent(m->stream, m->ev_join, 0));
-    if ((s = compute_p_impl(m, -g.H + 1, 0, g.Nx, g.Nx + g.H - 2, true))) return s;
-    HIPCHK(hipEventRecord(m->ev_strips, m->stream));
-    m->strips_issued = true;
-    return GB25_OK;
-  } else if (stage == 32) {
-    // 2-D decomposition: group 0 has been unpacked; the corrector on the x-halo columns of the own rows, so that the rows that
-    // leave for the southern / northern neighbour next (group 10) are corrected over their whole width
-    // (a lazy step: the rows leave uncorrected, like the columns; the receiver makes du, dv of its halo rows itself)
-    return m->route.corrector_in_consumers() ? GB25_OK : corrector_impl(m, true, 2);
-  } else if (stage == 3 || stage == 30 || stage == 31) {
-    // groups 2 and 0 have been unpacked: corrector on the x-halo columns, then update_state without any
-    // further exchange (y/z layers re-filled over the extended x range; w and p recomputed in the halos).
-    // Folded grid: stage 30 = up to the y/z layers, then the rows beyond the fold arrive from the partner, stage 31 = the rest.
-    // (a closure's fields travel in the bundle as well and its fills follow: the strips keep their old place behind them)
-    const bool strips_first = p_early && !m->catke;
-    const bool lazy = m->route.corrector_in_consumers(), wfly = m->route.kernels_carry_w();
-    const bool strips_done = m->strips_issued;   // (stage 33 ran them on the exchange stream)
-    if (stage != 30) m->strips_issued = false;
-    auto pressure_strips = [&]() -> gb25_status {
-      HIPCHK(hipEventRecord(m->ev_fork, m->stream));
-      HIPCHK(hipStreamWaitEvent(m->side_stream, m->ev_fork, 0));
-      {
-        OnStream on(m, m->side_stream);
-        if (gb25_status r = compute_p_impl(m, -g.H + 1, 0, g.Nx, g.Nx + g.H - 2, true)) return r;   // west strip (redoes column 0) + east strip
-      }
-      HIPCHK(hipEventRecord(m->ev_join, m->side_stream));
-      return GB25_OK;
-    };
-    if (stage != 31) {
-      if (strips_first && !strips_done) {
-        // the two pressure strips next to the x halos start as soon as the bundle is unpacked: T, S of the halo columns arrived
-        // complete (their y/z layers were filled by their owner before it packed them), and the side stream runs them behind the
-        // interior pass of stage 0 -- beside the corrector, the fills and w of the edge strips instead of after them
-        if ((s = pressure_strips())) return s;
-      }
-      if (lazy) {
-        // du, dv of the x halo columns: the neighbours' column integrals came with the bundle, the new U, V of those columns
-        // from the widened sub-cycle; their y/z layers of u, v arrived filled -- nothing else to do
-        if (!m->valid.halo_colsum_valid) return fail(m, GB25_ERR_STATE, "internal: a lazy step without the neighbours' column integrals");
-        if (m->Ry > 1) {
-          // 2-D decomposition: everything at once -- own cells, halo columns, halo rows of the open sides (corners included)
-          // rows: from the southern halo rows (or row 0) to the last northern halo row of the cell-shaped arrays (or the wall face)
-          const int hs = m->ys_open ? g.H : 0, nj = hs + g.Ny + (m->yn_open ? g.H : 1);
-          if ((s = unswept_head(m, dim3(64, 4), Cols{-g.H, g.Nx + 2 * g.H, INT_MAX, 0}, -hs, nj,
-                                wfly ? Cols{-2, g.Nx + 4, INT_MAX, 0} : NO_COLS, false)))
-            return s;
-          // (the bottom / top layers of the halo rows, which arrived with their interior levels: the fill below)
-        } else {
-          // ... in blocks of 16 x 16, and the chunk bases of w on the columns -2, -1 and Nx - 1, Nx, Nx + 1 (the w tiles reach two columns out)
-          if ((s = unswept_head(m, dim3(16, 16), Cols{-g.H, 2 * g.H, 0, g.Nx}, 0, g.Ny + 1,
-                                wfly ? Cols{-2, 5, 0, g.Nx - 1} : NO_COLS, false)))
-            return s;
-        }
-      } else if (m->Ry == 1 && (s = corrector_impl(m, true, 2))) {   // (2-D decomposition: done in stage 32)
-        return s;
-      }
-      // (with the early strips T and S are left alone here: their layers are in place, own columns since stage 0)
-      if (p_early && !strips_first) HIPCHK(hipStreamWaitEvent(m->stream, m->ev_join, 0));   // (the interior pass reads T, S)
-      if (!(lazy && strips_first) && (s = fill_halos_impl(m, false, true, 3, strips_first ? 1 : 3))) return s;
-      if (stage == 30) return GB25_OK;
-    }
-    if (p_early && !strips_first && (s = pressure_strips())) return s;   // (beside w)
-    if (!wfly && (s = compute_w_impl(m, split ? 2 : 0))) return s;
-    if (strips_done) {
-      HIPCHK(hipStreamWaitEvent(m->stream, m->ev_strips, 0));
-    } else if (p_early) {
-      HIPCHK(hipStreamWaitEvent(m->stream, m->ev_join, 0));
-    } else {
-      if ((s = compute_p_impl(m))) return s;
-    }
-    return momentum_impl(m, split ? 2 : 0);
-  } else if (stage == 4) {
-    // the tracer tendencies; the look-ahead of the next sub-cycle (groups 3, 4 and stage 5) runs beside them
-    if ((s = tracers_impl(m))) return s;
-    if (m->catke) return catke_step_local(m);   // (the rest after the halos of the new e and J^b: stage 41)
-    return atmosphere_ocean_fluxes_impl(m);
-  } else if (stage == 41) {
-    // closure = CATKE: groups 20 - 22 have been unpacked -- the diffusivities and the slow tendency of e, then the fluxes
-    if ((s = catke_finish_local(m))) return s;
-    return atmosphere_ocean_fluxes_impl(m);
+    // (with the early strips T and S are left alone here: their layers are in place, own columns since Update)
+    if (p_early && !strips_first) HIPCHK(hipStreamWaitEvent(m->stream, m->ev_join, 0));   // (the interior pass reads T, S)
+    if (!(lazy && strips_first) && (s = fill_halos_impl(m, false, true, 3, strips_first ? 1 : 3))) return s;
+    if (!second_part) return GB25_OK;
   }
-  return fail(m, GB25_ERR_INVALID_ARGUMENT, "unknown stage %d", stage);
+  if (p_early && !strips_first && (s = pressure_strips())) return s;   // (beside w)
+  if (!wfly && (s = compute_w_impl(m, split ? 2 : 0))) return s;
+  if (strips_done) {
+    HIPCHK(hipStreamWaitEvent(m->stream, m->ev_strips, 0));
+  } else if (p_early) {
+    HIPCHK(hipStreamWaitEvent(m->stream, m->ev_join, 0));
+  } else {
+    if ((s = compute_p_impl(m))) return s;
+  }
+  return momentum_impl(m, split ? 2 : 0);
+}
+
+// Tracers: the tracer tendencies; the look-ahead of the next sub-cycle (BaroWideAhead, SubcycleAhead) runs beside them
+gb25_status stage_tracers(gb25_model* m) {
+  if (gb25_status s = tracers_impl(m)) return s;
+  if (m->catke) return catke_step_local(m);   // (the rest after the halos of the new e and J^b: CatkeFinish)
+  return atmosphere_ocean_fluxes_impl(m);
+}
+// CatkeFinish: the Catke groups have been unpacked -- the diffusivities and the slow tendency of e, then the fluxes
+gb25_status stage_catke_finish(gb25_model* m) {
+  if (gb25_status s = catke_finish_local(m)) return s;
+  return atmosphere_ocean_fluxes_impl(m);
+}
+
+gb25_status slab_stage(gb25_model* m, Stage stage, int euler) {
+  switch (stage) {
+    case Stage::Update: return stage_update(m, euler);
+    case Stage::Subcycle: return stage_subcycle(m, false, false);
+    case Stage::SubcycleAhead: return stage_subcycle(m, true, false);
+    case Stage::SubcycleSubsteps: return stage_subcycle(m, false, true);
+    case Stage::SubcycleAheadSubsteps: return stage_subcycle(m, true, true);
+    case Stage::OwnColumns: return stage_own_columns(m, false);
+    case Stage::LazyHead: return stage_own_columns(m, true);
+    case Stage::StripsOnComm: return stage_strips(m);
+    case Stage::HaloRowsCorrector: return stage_halo_rows_corrector(m);
+    case Stage::HaloColumns: return stage_halo_columns(m, true, true);
+    case Stage::HaloColumnsToLayers: return stage_halo_columns(m, true, false);
+    case Stage::HaloColumnsRest: return stage_halo_columns(m, false, true);
+    case Stage::Tracers: return stage_tracers(m);
+    case Stage::CatkeFinish: return stage_catke_finish(m);
+  }
+  return fail(m, GB25_ERR_INVALID_ARGUMENT, "unknown stage %d", (int)stage);
 }
 
 gb25_status update_state_local_impl(gb25_model* m) {   // update_state! without the x-halo fill
@@ -527,38 +561,35 @@ gb25_status update_state_local_impl(gb25_model* m) {   // update_state! without 
   if ((s = compute_p_impl(m))) return s;
   if ((s = momentum_impl(m))) return s;
   if ((s = tracers_impl(m))) return s;
-  return m->catke ? catke_step_local(m) : GB25_OK;   // (the sequencer goes on with groups 20 - 22 and catke_finish_local)
+  return m->catke ? catke_step_local(m) : GB25_OK;   // (the sequencer goes on with the Catke groups and catke_finish_local)
 }
 
 // ---- sequencing ------------------------------------------------------------------------------------------------------
-// Everything a step of the slabs driven by this process does, in issue order.  Streams: `main` (on_comm = false) and
-// `comm`; record(slot, on_comm) marks everything issued so far on a stream, wait(slot, comm_waits) makes the other (or
-// the same) stream wait for that mark.  No host synchronisation anywhere.
-// Streams by number: 0 = main, 1 = comm (the exchanges: packs, transfers, unpacks), 2 = sub (the substeps of the sub-cycle
-// look-ahead: on a stream of their own so that the next step's bundle -- posted on the comm stream right behind stage 0 -- does
-// not queue behind five sub-cycle launches it has nothing to do with; 95 us of a 180-column rank's 640).
+// Everything a step of the slabs driven by this process does, in issue order, on the streams Main, Comm (the exchanges: packs,
+// transfers, unpacks) and Sub (slab_protocol.hpp); record(slot, stream) marks everything issued so far on a stream, wait(slot,
+// stream) makes a stream wait for that mark.  No host synchronisation anywhere.
 struct StepOps {
   virtual ~StepOps() {}
   virtual int n() const = 0;
-  virtual gb25_status stage(int s, int stage, int euler, int on) = 0;
-  virtual gb25_status pack(int s, int group, int on) = 0;
-  virtual gb25_status unpack(int s, int group, int on) = 0;
-  virtual gb25_status exchange(int group, int on) = 0;   // every slab's packs -> its neighbours' receive buffers
-  virtual gb25_status local(int s, int what) = 0;              // 0: initialize!, 1: y/z halo layers, 2: update_state! (local)
+  virtual gb25_status stage(int s, Stage stage, int euler, StreamId on) = 0;
+  virtual gb25_status pack(int s, Group group, StreamId on) = 0;
+  virtual gb25_status unpack(int s, Group group, StreamId on) = 0;
+  virtual gb25_status exchange(Group group, StreamId on) = 0;   // every slab's packs -> its neighbours' receive buffers
+  virtual gb25_status local(int s, LocalOp what) = 0;
   virtual bool velocities_ready(int s) = 0;
   virtual bool subcycle_adopted(int s) = 0;
   virtual bool coupled() { return false; }   // a prescribed atmosphere is set (data-free forcing)
-  virtual bool catke() { return false; }     // closure = CATKE: the halos of the new e, J^b travel inside update_state! (groups 20 - 22)
-  virtual bool folded() = 0;          // zipper fold: exchanges with the partner rank (buffer sets 3 and 4; groups 6 and 8)
-  virtual bool lazy() { return false; }     // this step keeps the corrector inside its consumers (known after stage 0)
+  virtual bool catke() { return false; }     // closure = CATKE: the halos of the new e, J^b travel inside update_state! (the Catke groups)
+  virtual bool folded() = 0;          // zipper fold: exchanges with the partner rank (the groups of Peer::FoldPartner)
+  virtual bool lazy() { return false; }     // this step keeps the corrector inside its consumers (known after stage Update)
   // the bundle is unpacked on the exchange stream right behind its transfer (halo columns only: nothing the main stream touches
-  // before it waits for event 3); on plain x slabs the two pressure strips next to the x halos follow it there (stage 33) --
-  // beside the interior momentum pass instead of in front of the edge pass
+  // before it waits for HaloColumnsArrived); on plain x slabs the two pressure strips next to the x halos follow it there
+  // (StripsOnComm) -- beside the interior momentum pass instead of in front of the edge pass
   virtual bool early_unpack() { return false; }
   virtual bool early_strips() { return false; }
-  virtual bool mesh_y() { return false; }   // 2-D decomposition: y halos from the southern / northern neighbour (groups 10 - 14)
-  virtual gb25_status record(int slot, int on) = 0;
-  virtual gb25_status wait(int slot, int waiter) = 0;
+  virtual bool mesh_y() { return false; }   // 2-D decomposition: y halos from the southern / northern neighbour (the groups of Peer::Rows)
+  virtual gb25_status record(EventSlot slot, StreamId on) = 0;
+  virtual gb25_status wait(EventSlot slot, StreamId waiter) = 0;
 };
 #define SEQ(call)            \
   do {                       \
@@ -569,169 +600,168 @@ struct StepOps {
   for (int s = 0; s < n; s++) SEQ(expr)
 
 // closure = CATKE: e was stepped and J^b filtered on the own columns; their halos, then the second half of compute_diffusivities!
-// and the slow tendency of e (`finish`: a stage of the step, or local operation 7 inside first_time_step!)
+// and the slow tendency of e (`finish`: stage CatkeFinish, or CatkeFinishLocal inside first_time_step!)
 gb25_status sequence_catke_halos(StepOps& o, int n) {
-  EACH(o.pack(s, 20, false));
-  SEQ(o.exchange(20, false));
-  EACH(o.unpack(s, 20, false));
+  EACH(o.pack(s, Group::CatkeColumns, Main));
+  SEQ(o.exchange(Group::CatkeColumns, Main));
+  EACH(o.unpack(s, Group::CatkeColumns, Main));
   if (o.mesh_y()) {       // whole rows, with the x halo columns just received (the corners)
-    EACH(o.pack(s, 21, false));
-    SEQ(o.exchange(21, false));
-    EACH(o.unpack(s, 21, false));
+    EACH(o.pack(s, Group::CatkeRows, Main));
+    SEQ(o.exchange(Group::CatkeRows, Main));
+    EACH(o.unpack(s, Group::CatkeRows, Main));
   }
   if (o.folded()) {
-    EACH(o.pack(s, 22, false));
-    SEQ(o.exchange(22, false));
-    EACH(o.unpack(s, 22, false));
+    EACH(o.pack(s, Group::CatkeFold, Main));
+    SEQ(o.exchange(Group::CatkeFold, Main));
+    EACH(o.unpack(s, Group::CatkeFold, Main));
   }
   return GB25_OK;
 }
 gb25_status sequence_time_step(StepOps& o, int euler, bool& lookahead_in_flight) {
   const int n = o.n();
-  // The previous step may have left the look-ahead chain (group 3, stage 5) running on the second stream.  Stage 0 touches
-  // nothing of it on the device (the adoption of eta, U, V is a pointer exchange on the host; its kernels update and fill
+  // The previous step may have left the look-ahead chain (BaroWideAhead, SubcycleAhead) running on the other streams.  Update
+  // touches nothing of it on the device (the adoption of eta, U, V is a pointer exchange on the host; its kernels update and fill
   // u, v, T, S and start the pressure), so it does not wait: on a narrow slab the chain (an exchange + the sub-cycle,
-  // ~230 us) outlasts the tracer kernel it runs beside (~120 us), and stage 0 fills part of the difference.
+  // ~230 us) outlasts the tracer kernel it runs beside (~120 us), and Update fills part of the difference.
   const bool in_flight = lookahead_in_flight;
   lookahead_in_flight = false;
-  EACH(o.stage(s, 0, euler, false));
+  EACH(o.stage(s, Stage::Update, euler, Main));
   bool adopted = true;         // the sub-cycle of this step is already done
   for (int s = 0; s < n; s++) adopted = adopted && o.subcycle_adopted(s);
   if (in_flight && !adopted)   // not adopted after all: it must be over before its buffers and work arrays are reused
-    SEQ(o.wait(4, false));    // (event 4: recorded behind the chain when it was issued)
-  SEQ(o.record(0, false));     // everything stage 0 wrote
+    SEQ(o.wait(ChainEnd, Main));
+  SEQ(o.record(UpdateWritten, Main));
   if (!adopted) {
     // The small barotropic exchange is on the critical path and is posted FIRST: the point-to-point transfers of one
     // communicator run in posting order, so the 6 MB bundle must not be queued ahead of it.
-    EACH(o.pack(s, 1, false));
-    SEQ(o.exchange(1, false));
+    EACH(o.pack(s, Group::BaroWide, Main));
+    SEQ(o.exchange(Group::BaroWide, Main));
   }
-  SEQ(o.wait(0, true));        // the 3-D bundle leaves on the second stream ...
-  EACH(o.pack(s, 0, true));
-  SEQ(o.record(1, true));      // (packed)
-  SEQ(o.exchange(0, true));
+  SEQ(o.wait(UpdateWritten, Comm));        // the 3-D bundle leaves on the second stream ...
+  EACH(o.pack(s, Group::Bundle, Comm));
+  SEQ(o.record(BundlePacked, Comm));
+  SEQ(o.exchange(Group::Bundle, Comm));
   const bool early = o.early_unpack();
   if (early)
     for (int s = 0; s < n; s++) {
-      SEQ(o.unpack(s, 0, true));
-      if (o.early_strips()) SEQ(o.stage(s, 33, euler, true));
+      SEQ(o.unpack(s, Group::Bundle, Comm));
+      if (o.early_strips()) SEQ(o.stage(s, Stage::StripsOnComm, euler, Comm));
     }
-  // 2-D decomposition, a step that keeps the corrector inside its consumers: the rows leave as they are (stage 32 has nothing to
-  // do), so their exchange follows the bundle on the exchange stream instead of waiting for the main stream to get there (one
-  // cross-stream hop less: 0.538 -> 0.504 ms per step of a 360 x 360 rank, tools/slab_selfring.py --mesh 4 2)
+  // 2-D decomposition, a step that keeps the corrector inside its consumers: the rows leave as they are (HaloRowsCorrector has
+  // nothing to do), so their exchange follows the bundle on the exchange stream instead of waiting for the main stream to get there
+  // (one cross-stream hop less: 0.538 -> 0.504 ms per step of a 360 x 360 rank, tools/slab_selfring.py --mesh 4 2)
   const bool rows_early = early && o.mesh_y() && o.lazy();
   if (rows_early) {
-    EACH(o.pack(s, 10, true));
-    SEQ(o.exchange(10, true));
-    EACH(o.unpack(s, 10, true));
+    EACH(o.pack(s, Group::BundleRows, Comm));
+    SEQ(o.exchange(Group::BundleRows, Comm));
+    EACH(o.unpack(s, Group::BundleRows, Comm));
   }
   if (!adopted && (o.folded() || o.mesh_y())) {
     // zipper fold: the work arrays are tall as well as wide.  Once every slab has its wide halo columns, the rows south of
-    // the pivot row go to the partner rank P-1-r (group 8) and become its image rows beyond the pivot row; then the substeps
+    // the pivot row go to the partner rank P-1-r (FoldTall) and become its image rows beyond the pivot row; then the substeps
     // run with no further exchange.  2-D decomposition: likewise the W rows next to an open side go to the southern /
-    // northern neighbour (group 11), with the wide halo columns just received: the corners
+    // northern neighbour (BaroWideRows), with the wide halo columns just received: the corners
     for (int s = 0; s < n; s++) {
-      SEQ(o.unpack(s, 1, false));
-      SEQ(o.stage(s, 1, euler, false));      // (the interior copy only)
-      if (o.mesh_y()) SEQ(o.pack(s, 11, false));
-      if (o.folded()) SEQ(o.pack(s, 8, false));
+      SEQ(o.unpack(s, Group::BaroWide, Main));
+      SEQ(o.stage(s, Stage::Subcycle, euler, Main));      // (the interior copy only)
+      if (o.mesh_y()) SEQ(o.pack(s, Group::BaroWideRows, Main));
+      if (o.folded()) SEQ(o.pack(s, Group::FoldTall, Main));
     }
-    if (o.mesh_y()) SEQ(o.exchange(11, false));
-    if (o.folded()) SEQ(o.exchange(8, false));
+    if (o.mesh_y()) SEQ(o.exchange(Group::BaroWideRows, Main));
+    if (o.folded()) SEQ(o.exchange(Group::FoldTall, Main));
     for (int s = 0; s < n; s++) {
-      if (o.mesh_y()) SEQ(o.unpack(s, 11, false));
-      if (o.folded()) SEQ(o.unpack(s, 8, false));
-      SEQ(o.stage(s, 16, euler, false));
+      if (o.mesh_y()) SEQ(o.unpack(s, Group::BaroWideRows, Main));
+      if (o.folded()) SEQ(o.unpack(s, Group::FoldTall, Main));
+      SEQ(o.stage(s, Stage::SubcycleSubsteps, euler, Main));
     }
   } else if (!adopted) {       // ... and is in flight while the sub-cycle runs here (it leaves the x halo columns of the
-    for (int s = 0; s < n; s++) {   // new eta, U, V behind as well: the slab is widened by Ns + 1 + H columns, no group 2)
-      SEQ(o.unpack(s, 1, false));
-      SEQ(o.stage(s, 1, euler, false));
+    for (int s = 0; s < n; s++) {   // new eta, U, V behind as well: the slab is widened by Ns + 1 + H columns, no BaroHalo)
+      SEQ(o.unpack(s, Group::BaroWide, Main));
+      SEQ(o.stage(s, Stage::Subcycle, euler, Main));
     }
   }
   if (o.lazy()) {
     // the corrector inside its consumers writes nothing the bundle is packed from: du, dv and the chunk bases of w of the own
-    // columns (stage 20) need the adopted sub-cycle only; the interior momentum pass, which overwrites chunk sums the bundle
+    // columns (LazyHead) need the adopted sub-cycle only; the interior momentum pass, which overwrites chunk sums the bundle
     // carries, waits for the pack
-    if (in_flight && adopted) SEQ(o.wait(4, false));
-    EACH(o.stage(s, 20, euler, false));
-    SEQ(o.wait(1, false));
+    if (in_flight && adopted) SEQ(o.wait(ChainEnd, Main));
+    EACH(o.stage(s, Stage::LazyHead, euler, Main));
+    SEQ(o.wait(BundlePacked, Main));
   } else {
-    SEQ(o.wait(1, false));       // the corrector rewrites the columns the bundle was packed from
-    if (in_flight && adopted)    // ... and reads the adopted sub-cycle: the look-ahead chain has finished (event 4 sits
-      SEQ(o.wait(4, false));     // behind the chain, ahead of this step's bundle on the same stream)
+    SEQ(o.wait(BundlePacked, Main));   // the corrector rewrites the columns the bundle was packed from
+    if (in_flight && adopted)          // ... and reads the adopted sub-cycle: the look-ahead chain has finished (ChainEnd sits
+      SEQ(o.wait(ChainEnd, Main));     // behind the chain, ahead of this step's bundle on the same stream)
   }
-  EACH(o.stage(s, 2, euler, false));   // own columns + interior tendencies, while the exchanges are in flight
-  SEQ(o.record(3, true));
-  SEQ(o.wait(3, false));       // the halo columns have arrived
+  EACH(o.stage(s, Stage::OwnColumns, euler, Main));   // own columns + interior tendencies, while the exchanges are in flight
+  SEQ(o.record(HaloColumnsArrived, Comm));
+  SEQ(o.wait(HaloColumnsArrived, Main));
   if (o.mesh_y() && !rows_early) {
     // 2-D decomposition: the H rows next to an open side, with the x halo columns just received (the corners)
     for (int s = 0; s < n; s++) {
-      if (!early) SEQ(o.unpack(s, 0, false));
-      SEQ(o.stage(s, 32, euler, false));   // (the corrector on the x halo columns: the rows leave corrected)
-      SEQ(o.pack(s, 10, false));
+      if (!early) SEQ(o.unpack(s, Group::Bundle, Main));
+      SEQ(o.stage(s, Stage::HaloRowsCorrector, euler, Main));   // (the rows leave corrected)
+      SEQ(o.pack(s, Group::BundleRows, Main));
     }
-    SEQ(o.exchange(10, false));
-    EACH(o.unpack(s, 10, false));
+    SEQ(o.exchange(Group::BundleRows, Main));
+    EACH(o.unpack(s, Group::BundleRows, Main));
   }
   if (o.folded()) {
     // the rows beyond the fold come from the partner once every slab has its x halos and y/z layers (the partner sends
     // its halo columns too: the corners), then the rest of update_state!
     for (int s = 0; s < n; s++) {
-      if (!o.mesh_y() && !early) SEQ(o.unpack(s, 0, false));
-      SEQ(o.stage(s, 30, euler, false));
-      SEQ(o.pack(s, 6, false));
+      if (!o.mesh_y() && !early) SEQ(o.unpack(s, Group::Bundle, Main));
+      SEQ(o.stage(s, Stage::HaloColumnsToLayers, euler, Main));
+      SEQ(o.pack(s, Group::FoldBundle, Main));
     }
-    SEQ(o.exchange(6, false));
+    SEQ(o.exchange(Group::FoldBundle, Main));
     for (int s = 0; s < n; s++) {
-      SEQ(o.unpack(s, 6, false));
-      SEQ(o.stage(s, 31, euler, false));
+      SEQ(o.unpack(s, Group::FoldBundle, Main));
+      SEQ(o.stage(s, Stage::HaloColumnsRest, euler, Main));
     }
   } else {
     for (int s = 0; s < n; s++) {
-      if (!o.mesh_y() && !early) SEQ(o.unpack(s, 0, false));
-      SEQ(o.stage(s, 3, euler, false));
+      if (!o.mesh_y() && !early) SEQ(o.unpack(s, Group::Bundle, Main));
+      SEQ(o.stage(s, Stage::HaloColumns, euler, Main));
     }
   }
-  // the next step's G.U, G.V exist now: its wide-halo exchange, sub-cycle and eta,U,V exchange run on the second stream
-  // beside the tracer tendencies
+  // the next step's G.U, G.V exist now: its wide-halo exchange and sub-cycle run on the other streams beside the tracer tendencies
   bool ready = true;
   for (int s = 0; s < n; s++) ready = ready && o.velocities_ready(s);
   if (ready) {
-    SEQ(o.record(2, false));
-    SEQ(o.wait(2, true));
-    EACH(o.pack(s, 3, true));
-    SEQ(o.exchange(3, true));
+    SEQ(o.record(NextTendenciesExist, Main));
+    SEQ(o.wait(NextTendenciesExist, Comm));
+    EACH(o.pack(s, Group::BaroWideAhead, Comm));
+    SEQ(o.exchange(Group::BaroWideAhead, Comm));
     if (o.folded() || o.mesh_y()) {
       for (int s = 0; s < n; s++) {
-        SEQ(o.unpack(s, 3, 1));
-        SEQ(o.stage(s, 5, euler, 1));    // (the interior copy only)
-        if (o.mesh_y()) SEQ(o.pack(s, 13, 1));
-        if (o.folded()) SEQ(o.pack(s, 8, 1));
+        SEQ(o.unpack(s, Group::BaroWideAhead, Comm));
+        SEQ(o.stage(s, Stage::SubcycleAhead, euler, Comm));    // (the interior copy only)
+        if (o.mesh_y()) SEQ(o.pack(s, Group::BaroWideRowsAhead, Comm));
+        if (o.folded()) SEQ(o.pack(s, Group::FoldTall, Comm));
       }
       // the neighbours' rows / the image rows beyond the pivot row, then the substeps on their own stream
-      if (o.mesh_y()) SEQ(o.exchange(13, 1));
-      if (o.folded()) SEQ(o.exchange(8, 1));
+      if (o.mesh_y()) SEQ(o.exchange(Group::BaroWideRowsAhead, Comm));
+      if (o.folded()) SEQ(o.exchange(Group::FoldTall, Comm));
       for (int s = 0; s < n; s++) {
-        if (o.mesh_y()) SEQ(o.unpack(s, 13, 1));
-        if (o.folded()) SEQ(o.unpack(s, 8, 1));
+        if (o.mesh_y()) SEQ(o.unpack(s, Group::BaroWideRowsAhead, Comm));
+        if (o.folded()) SEQ(o.unpack(s, Group::FoldTall, Comm));
       }
-      SEQ(o.record(5, 1));
-      SEQ(o.wait(5, 2));
-      EACH(o.stage(s, 56, euler, 2));
+      SEQ(o.record(ChainExchanged, Comm));
+      SEQ(o.wait(ChainExchanged, Sub));
+      EACH(o.stage(s, Stage::SubcycleAheadSubsteps, euler, Sub));
     } else {
-      EACH(o.unpack(s, 3, 1));
-      SEQ(o.record(5, 1));
-      SEQ(o.wait(5, 2));
-      EACH(o.stage(s, 5, euler, 2));     // (x halo columns of the new eta, U, V included: nothing to exchange after it)
+      EACH(o.unpack(s, Group::BaroWideAhead, Comm));
+      SEQ(o.record(ChainExchanged, Comm));
+      SEQ(o.wait(ChainExchanged, Sub));
+      EACH(o.stage(s, Stage::SubcycleAhead, euler, Sub));     // (x halo columns of the new eta, U, V included: nothing to exchange after it)
     }
-    SEQ(o.record(4, 2));
+    SEQ(o.record(ChainEnd, Sub));
     lookahead_in_flight = true;
   }
-  EACH(o.stage(s, 4, euler, false));
+  EACH(o.stage(s, Stage::Tracers, euler, Main));
   if (o.catke()) {
     SEQ(sequence_catke_halos(o, n));
-    EACH(o.stage(s, 41, euler, false));
+    EACH(o.stage(s, Stage::CatkeFinish, euler, Main));
   }
   return GB25_OK;
 }
@@ -739,68 +769,68 @@ gb25_status sequence_time_step(StepOps& o, int euler, bool& lookahead_in_flight)
 gb25_status sequence_first_time_step(StepOps& o, bool& lookahead_in_flight) {
   const int n = o.n();
   if (lookahead_in_flight) {
-    SEQ(o.wait(4, 0));             // (the chain's last launches, on the sub stream)
-    SEQ(o.record(3, true));
-    SEQ(o.wait(3, false));
+    SEQ(o.wait(ChainEnd, Main));             // (the chain's last launches, on the sub stream)
+    SEQ(o.record(HaloColumnsArrived, Comm));
+    SEQ(o.wait(HaloColumnsArrived, Main));
     lookahead_in_flight = false;
   }
   for (int s = 0; s < n; s++) {
-    SEQ(o.local(s, 0));
-    SEQ(o.local(s, 1));
-    SEQ(o.pack(s, 0, false));
-    SEQ(o.pack(s, 2, false));
+    SEQ(o.local(s, Initialize));
+    SEQ(o.local(s, FillLocal));
+    SEQ(o.pack(s, Group::Bundle, Main));
+    SEQ(o.pack(s, Group::BaroHalo, Main));
   }
-  SEQ(o.exchange(0, false));
-  SEQ(o.exchange(2, false));
+  SEQ(o.exchange(Group::Bundle, Main));
+  SEQ(o.exchange(Group::BaroHalo, Main));
   if (o.mesh_y()) {
     for (int s = 0; s < n; s++) {
-      SEQ(o.unpack(s, 0, false));
-      SEQ(o.unpack(s, 2, false));
-      SEQ(o.pack(s, 10, false));
-      SEQ(o.pack(s, 12, false));
+      SEQ(o.unpack(s, Group::Bundle, Main));
+      SEQ(o.unpack(s, Group::BaroHalo, Main));
+      SEQ(o.pack(s, Group::BundleRows, Main));
+      SEQ(o.pack(s, Group::BaroHaloRows, Main));
     }
-    SEQ(o.exchange(10, false));
-    SEQ(o.exchange(12, false));
+    SEQ(o.exchange(Group::BundleRows, Main));
+    SEQ(o.exchange(Group::BaroHaloRows, Main));
     for (int s = 0; s < n; s++) {
-      SEQ(o.unpack(s, 10, false));
-      SEQ(o.unpack(s, 12, false));
+      SEQ(o.unpack(s, Group::BundleRows, Main));
+      SEQ(o.unpack(s, Group::BaroHaloRows, Main));
     }
   }
   if (o.folded()) {
     for (int s = 0; s < n; s++) {
       if (!o.mesh_y()) {
-        SEQ(o.unpack(s, 0, false));
-        SEQ(o.unpack(s, 2, false));
+        SEQ(o.unpack(s, Group::Bundle, Main));
+        SEQ(o.unpack(s, Group::BaroHalo, Main));
       }
-      SEQ(o.local(s, 3));          // mask, y/z layers over the extended columns
-      SEQ(o.pack(s, 6, false));
+      SEQ(o.local(s, MaskFillLocal));
+      SEQ(o.pack(s, Group::FoldBundle, Main));
     }
-    SEQ(o.exchange(6, false));
+    SEQ(o.exchange(Group::FoldBundle, Main));
     for (int s = 0; s < n; s++) {
-      SEQ(o.unpack(s, 6, false));
-      SEQ(o.local(s, 4));          // w, pressure, tendencies
+      SEQ(o.unpack(s, Group::FoldBundle, Main));
+      SEQ(o.local(s, AuxiliariesTendenciesLocal));
     }
   } else {
     for (int s = 0; s < n; s++) {
       if (!o.mesh_y()) {
-        SEQ(o.unpack(s, 0, false));
-        SEQ(o.unpack(s, 2, false));
+        SEQ(o.unpack(s, Group::Bundle, Main));
+        SEQ(o.unpack(s, Group::BaroHalo, Main));
       }
-      SEQ(o.local(s, 2));
+      SEQ(o.local(s, UpdateStateLocal));
     }
   }
   if (o.catke()) {
     SEQ(sequence_catke_halos(o, n));
-    EACH(o.local(s, 7));
+    EACH(o.local(s, CatkeFinishLocal));
   }
   if (o.coupled()) {
     // a coupled model (data-free forcing) updates its state at iteration 0: the atmosphere-ocean fluxes of the initial state,
     // then the tendencies (and, with CATKE, another compute_diffusivities!) that see them
-    EACH(o.local(s, 5));
-    EACH(o.local(s, 6));
+    EACH(o.local(s, FirstFluxesLocal));
+    EACH(o.local(s, TendenciesLocal));
     if (o.catke()) {
       SEQ(sequence_catke_halos(o, n));
-      EACH(o.local(s, 7));
+      EACH(o.local(s, CatkeFinishLocal));
     }
   }
   return sequence_time_step(o, 1, lookahead_in_flight);
@@ -831,29 +861,24 @@ struct TraceOps : StepOps {
     log += buf;
     log += '\n';
   }
-  static const char* st(int on) { return on == 2 ? "sub" : on == 1 ? "comm" : "main"; }
+  static const char* st(StreamId on) { return kStreamNames[on]; }
   int n() const override { return nslabs; }
-  gb25_status stage(int s, int stage, int euler, int c) override { add("stage %d slab %d euler %d %s", stage, s, euler, st(c)); return GB25_OK; }
-  gb25_status pack(int s, int group, int c) override { add("pack %d slab %d %s", group, s, st(c)); return GB25_OK; }
-  gb25_status unpack(int s, int group, int c) override { add("unpack %d slab %d %s", group, s, st(c)); return GB25_OK; }
-  gb25_status exchange(int group, int c) override { add("exchange %d %s", group, st(c)); return GB25_OK; }
-  gb25_status local(int s, int what) override {
-    static const char* names[] = {"initialize", "fill_local", "update_state_local", "mask_fill_local", "auxiliaries_tendencies_local",
-                                  "first_fluxes_local", "tendencies_local", "catke_finish_local"};
-    add("%s slab %d main", names[what], s);
-    return GB25_OK;
-  }
+  gb25_status stage(int s, Stage stage, int euler, StreamId c) override { add("stage %d slab %d euler %d %s", stage, s, euler, st(c)); return GB25_OK; }
+  gb25_status pack(int s, Group group, StreamId c) override { add("pack %d slab %d %s", group, s, st(c)); return GB25_OK; }
+  gb25_status unpack(int s, Group group, StreamId c) override { add("unpack %d slab %d %s", group, s, st(c)); return GB25_OK; }
+  gb25_status exchange(Group group, StreamId c) override { add("exchange %d %s", group, st(c)); return GB25_OK; }
+  gb25_status local(int s, LocalOp what) override { add("%s slab %d main", kLocalOpNames[what], s); return GB25_OK; }
   bool velocities_ready(int) override { return ready; }
   bool subcycle_adopted(int) override { return adopted; }
-  gb25_status record(int slot, int c) override { add("record %d %s", slot, st(c)); return GB25_OK; }
-  gb25_status wait(int slot, int waiter) override { add("wait %d %s", slot, st(waiter)); return GB25_OK; }
+  gb25_status record(EventSlot slot, StreamId c) override { add("record %d %s", slot, st(c)); return GB25_OK; }
+  gb25_status wait(EventSlot slot, StreamId waiter) override { add("wait %d %s", slot, st(waiter)); return GB25_OK; }
 };
 
 // ---- transports ------------------------------------------------------------------------------------------------------
 struct Transport {
   virtual ~Transport() {}
-  // buffer set b (0: group 0; 1: groups 1, 3; 2: groups 2, 4), nbytes per side, on stream st
-  virtual gb25_status exchange(SlabGroup& G, int b, size_t nbytes, hipStream_t st) = 0;
+  // buffer set b, nbytes per side, on stream st
+  virtual gb25_status exchange(SlabGroup& G, BufferSet b, size_t nbytes, hipStream_t st) = 0;
   virtual const char* name() const = 0;
 };
 
@@ -863,7 +888,7 @@ struct Transport {
 struct SlabGroup {
   std::vector<gb25_model*> slabs;
   hipStream_t main = nullptr, comm = nullptr, sub = nullptr;   // (sub: the substeps of the sub-cycle look-ahead)
-  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t ev[NSLOTS] = {};
   // everything the second and third stream hold is over (host writes, grid changes, collective setters)
   hipError_t sync_side() {
     hipError_t e = comm ? hipStreamSynchronize(comm) : hipSuccess;
@@ -871,13 +896,10 @@ struct SlabGroup {
     return e;
   }
   Transport* transport = nullptr;
-  // [slab][buffer set][side: 0 west, 1 east]; sets 3, 4 go to the fold partner (side 0 only); sets 5, 6, 7 to the southern
-  // (side 0) and northern (side 1) neighbour of a 2-D decomposition
-  // sets 8, 9, 10: closure = CATKE -- e and J^b after the e step: x columns (west / east), rows (south / north), fold partner
-  static constexpr int NSETS = 11;
+  // [slab][buffer set][side]: 0 west, 1 east (Peer::Ring); 0 south, 1 north (Peer::Rows); side 0 only (Peer::FoldPartner)
   std::vector<std::array<std::array<real*, 2>, NSETS>> send, recv;
-  size_t elems[NSETS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};      // elements per side of buffer set b in an exchange
-  size_t capacity[NSETS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // ... and allocated
+  size_t elems[NSETS] = {};      // elements per side of buffer set b in an exchange
+  size_t capacity[NSETS] = {};   // ... and allocated
   bool lookahead_in_flight = false;
   // neighbour handshake of the collective mutators (see collective_guard)
   unsigned long long *tok_dev = nullptr, *tok_host = nullptr;
@@ -885,15 +907,6 @@ struct SlabGroup {
 
 namespace {
 
-// (groups 6, 8: the partner exchanges of a folded grid -- the rows next to the pivot row; the image rows of the sub-cycle)
-inline int buffer_set(int group) {
-  if (group >= 20) return group - 12;   // (closure = CATKE: groups 20, 21, 22 -> sets 8, 9, 10)
-  if (group >= 10) return group == 10 ? 5 : ((group == 11 || group == 13) ? 6 : 7);   // (the y halos of a 2-D decomposition)
-  return group == 6 ? 3 : group == 8 ? 4 : group == 0 ? 0 : ((group == 1 || group == 3) ? 1 : 2);
-}
-// whom a buffer set travels to: 0 the west / east ring neighbours, 1 the fold partner, 2 the southern / northern neighbour
-inline int set_kind(int b) { return (b == 3 || b == 4 || b == 10) ? 1 : ((b >= 5 && b <= 7) || b == 9) ? 2 : 0; }
-inline int set_sides(int b) { return set_kind(b) == 1 ? 1 : 2; }
 // rank = ry Rx + rx: the ring neighbours within the row, the neighbours in the column, the fold partner within the top row
 struct MeshPos {
   int Rx, Ry, rx, ry;
@@ -909,14 +922,15 @@ struct MeshPos {
 // several slabs of one decomposition in this process, all on one device: a ring of device-to-device copies
 struct LocalRingTransport : Transport {
   const char* name() const override { return "local"; }
-  gb25_status exchange(SlabGroup& G, int b, size_t nbytes, hipStream_t st) override {
+  gb25_status exchange(SlabGroup& G, BufferSet b, size_t nbytes, hipStream_t st) override {
     const int P = (int)G.slabs.size();
     for (int r = 0; r < P; r++) {
       gb25_model* m = G.slabs[r];
       const MeshPos q(m);
-      if (set_kind(b) == 1) {   // zipper fold: slab rx <-> slab Rx-1-rx of the top row (the middle slab of an odd count is its own partner)
+      const Peer peer = set_info(b).peer;
+      if (peer == Peer::FoldPartner) {   // zipper fold: slab rx <-> slab Rx-1-rx of the top row (the middle slab of an odd count is its own partner)
         if (m->g.cv.north_fold) HIPCHK(hipMemcpyAsync(G.recv[q.partner()][b][0], G.send[r][b][0], nbytes, hipMemcpyDeviceToDevice, st));
-      } else if (set_kind(b) == 2) {      // my southern pack -> the southern neighbour's northern halo; my northern pack -> ... southern halo
+      } else if (peer == Peer::Rows) {    // my southern pack -> the southern neighbour's northern halo; my northern pack -> ... southern halo
         if (q.south() >= 0) HIPCHK(hipMemcpyAsync(G.recv[q.south()][b][1], G.send[r][b][0], nbytes, hipMemcpyDeviceToDevice, st));
         if (q.north() >= 0) HIPCHK(hipMemcpyAsync(G.recv[q.north()][b][0], G.send[r][b][1], nbytes, hipMemcpyDeviceToDevice, st));
       } else {                  // my west pack -> west neighbour's east halo; my east pack -> east neighbour's west halo
@@ -988,15 +1002,14 @@ RcclApi& rccl() {
 // single place that knows the protocol -- RcclTransport::exchange posts exactly this, gb25_debug_exchange_plan prints it, and the
 // CPU tests prove from it that every rank's ordered sends to a peer mirror that peer's ordered receives (tests/test_distributed_cpu.py).
 struct PlanOp { bool send; int peer; int side; };
-inline std::vector<PlanOp> exchange_plan(const MeshPos& q, bool north_fold, int b) {
+inline std::vector<PlanOp> exchange_plan(const MeshPos& q, bool north_fold, Peer peer) {
   std::vector<PlanOp> p;
-  const int kind = set_kind(b);
-  if (kind == 2) {          // 2-D decomposition: the southern and the northern neighbour, where they exist
+  if (peer == Peer::Rows) { // 2-D decomposition: the southern and the northern neighbour, where they exist
     if (q.south() >= 0) p.push_back({true, q.south(), 0});
     if (q.north() >= 0) p.push_back({true, q.north(), 1});
     if (q.north() >= 0) p.push_back({false, q.north(), 1});
     if (q.south() >= 0) p.push_back({false, q.south(), 0});
-  } else if (kind == 1) {   // zipper fold: the partner is the mirrored rank of the (top) row; a rank that is its own partner copies
+  } else if (peer == Peer::FoldPartner) {   // zipper fold: the partner is the mirrored rank of the (top) row; a rank that is its own partner copies
     const int self = q.ry * q.Rx + q.rx;
     if (north_fold && q.partner() != self) {
       p.push_back({true, q.partner(), 0});
@@ -1038,17 +1051,18 @@ struct RcclTransport : Transport {
     NCCLCHK(R.GroupEnd());
     return GB25_OK;
   }
-  gb25_status exchange(SlabGroup& G, int b, size_t nbytes, hipStream_t st) override {
+  gb25_status exchange(SlabGroup& G, BufferSet b, size_t nbytes, hipStream_t st) override {
     gb25_model* m = G.slabs[0];
     const MeshPos q(m);
-    if (set_kind(b) == 1) {
+    const Peer to = set_info(b).peer;
+    if (to == Peer::FoldPartner) {
       if (!m->g.cv.north_fold) return GB25_OK;
       if (q.partner() == rank || alone) {   // (its own partner: the middle slab of an odd count, the self-ring)
         HIPCHK(hipMemcpyAsync(G.recv[0][b][0], G.send[0][b][0], nbytes, hipMemcpyDeviceToDevice, st));
         return GB25_OK;
       }
     }
-    const std::vector<PlanOp> plan = exchange_plan(q, m->g.cv.north_fold != 0, b);
+    const std::vector<PlanOp> plan = exchange_plan(q, m->g.cv.north_fold != 0, to);
     if (plan.empty()) return GB25_OK;
     RcclApi& R = rccl();
     NCCLCHK(R.GroupStart());
@@ -1066,17 +1080,17 @@ struct CallbackTransport : Transport {
   gb25_exchange_fn fn = nullptr;
   void* user = nullptr;
   const char* name() const override { return "callback"; }
-  gb25_status exchange(SlabGroup& G, int b, size_t nbytes, hipStream_t st) override {
+  gb25_status exchange(SlabGroup& G, BufferSet b, size_t nbytes, hipStream_t st) override {
     gb25_model* m = G.slabs[0];
     HIPCHK(hipStreamSynchronize(st));   // the packs are complete
-    // (buffer sets 3, 4: to and from the fold partner rank P-1-r; the east pointers are null)
-    // (buffer sets 5 - 7: to and from the southern [west pointers] and northern [east pointers] neighbour of a 2-D
-    // decomposition; null where there is none)
-    const int kind = set_kind(b);
-    if (kind == 1 && !m->g.cv.north_fold) return GB25_OK;
+    // (Peer::FoldPartner: to and from the fold partner rank P-1-r; the east pointers are null)
+    // (Peer::Rows: to and from the southern [west pointers] and northern [east pointers] neighbour of a 2-D decomposition; null
+    // where there is none)
+    const Peer peer = set_info(b).peer;
+    if (peer == Peer::FoldPartner && !m->g.cv.north_fold) return GB25_OK;
     int rc;
-    if (kind == 1) rc = fn(user, b, G.send[0][b][0], nullptr, G.recv[0][b][0], nullptr, (int64_t)nbytes);
-    else if (kind == 2) rc = fn(user, b, m->ys_open ? G.send[0][b][0] : nullptr, m->yn_open ? G.send[0][b][1] : nullptr,
+    if (peer == Peer::FoldPartner) rc = fn(user, b, G.send[0][b][0], nullptr, G.recv[0][b][0], nullptr, (int64_t)nbytes);
+    else if (peer == Peer::Rows) rc = fn(user, b, m->ys_open ? G.send[0][b][0] : nullptr, m->yn_open ? G.send[0][b][1] : nullptr,
                              m->ys_open ? G.recv[0][b][0] : nullptr, m->yn_open ? G.recv[0][b][1] : nullptr, (int64_t)nbytes);
     else rc = fn(user, b, G.send[0][b][0], G.send[0][b][1], G.recv[0][b][0], G.recv[0][b][1], (int64_t)nbytes);
     if (rc != 0) return fail(m, GB25_ERR_COMM, "the host's exchange callback failed with code %d (buffer set %d)", rc, b);
@@ -1089,8 +1103,8 @@ struct GroupOps : StepOps {
   SlabGroup& G;
   explicit GroupOps(SlabGroup& g_) : G(g_) {}
   int n() const override { return (int)G.slabs.size(); }
-  hipStream_t st(int on) const { return on == 2 ? G.sub : on == 1 ? G.comm : G.main; }
-  gb25_status stage(int s, int stage, int euler, int c) override {
+  hipStream_t st(StreamId on) const { return on == Sub ? G.sub : on == Comm ? G.comm : G.main; }
+  gb25_status stage(int s, Stage stage, int euler, StreamId c) override {
     OnStream on(G.slabs[s], st(c));
     return slab_stage(G.slabs[s], stage, euler);
   }
@@ -1117,77 +1131,63 @@ struct GroupOps : StepOps {
   }
   bool coupled() override { return G.slabs[0]->coupled; }
   bool catke() override { return G.slabs[0]->catke; }
-  gb25_status pack(int s, int group, int c) override {
-    OnStream on(G.slabs[s], st(c));
-    const int b = buffer_set(group);
-    if ((group == 6 || group == 8 || group == 22) && !G.slabs[s]->g.cv.north_fold) return GB25_OK;
-    if (group == 6 || group == 22) return fold_pack(G.slabs[s], G.send[s][b][0], group == 22);
-    if (group == 8) return tall_rows_impl(G.slabs[s], G.send[s][b][0], true);
-    if ((group >= 10 && group < 20) || group == 21) {
-      real* rb[2] = {G.send[s][b][0], G.send[s][b][1]};
-      return move_rows(G.slabs[s], group, rb, true);
+  gb25_status move(int s, Group group, StreamId c, bool pack) {
+    gb25_model* m = G.slabs[s];
+    OnStream on(m, st(c));
+    const GroupInfo& info = group_info(group);
+    const std::array<real*, 2>& buf = (pack ? G.send : G.recv)[s][info.set];
+    switch (info.mover) {
+      case Mover::FoldRows:
+        if (!m->g.cv.north_fold) return GB25_OK;
+        return pack ? fold_pack(m, buf[0], info.closure) : fold_unpack(m, buf[0], info.closure);
+      case Mover::TallRows: return m->g.cv.north_fold ? tall_rows_impl(m, buf[0], pack) : GB25_OK;
+      case Mover::Rows: return move_rows(m, group, buf.data(), pack);
+      case Mover::Columns:
+        if (pack && group == Group::Bundle) m->valid.halo_colsums_packed();   // (every slab alike: same calls, same state)
+        return pack_unpack(m, group, buf.data(), pack);
     }
-    if (group == 0) G.slabs[s]->valid.halo_colsums_packed();   // (every slab alike: same calls, same state)
-    real* buf[2] = {G.send[s][b][0], G.send[s][b][1]};
-    return pack_unpack(G.slabs[s], group, buf, true);
+    return GB25_OK;
   }
-  gb25_status unpack(int s, int group, int c) override {
-    OnStream on(G.slabs[s], st(c));
-    const int b = buffer_set(group);
-    if ((group == 6 || group == 8 || group == 22) && !G.slabs[s]->g.cv.north_fold) return GB25_OK;
-    if (group == 6 || group == 22) return fold_unpack(G.slabs[s], G.recv[s][b][0], group == 22);
-    if (group == 8) return tall_rows_impl(G.slabs[s], G.recv[s][b][0], false);
-    if ((group >= 10 && group < 20) || group == 21) {
-      real* rb[2] = {G.recv[s][b][0], G.recv[s][b][1]};
-      return move_rows(G.slabs[s], group, rb, false);
-    }
-    real* buf[2] = {G.recv[s][b][0], G.recv[s][b][1]};
-    return pack_unpack(G.slabs[s], group, buf, false);
-  }
-  gb25_status exchange(int group, int c) override {
-    const int b = buffer_set(group);
+  gb25_status pack(int s, Group group, StreamId c) override { return move(s, group, c, true); }
+  gb25_status unpack(int s, Group group, StreamId c) override { return move(s, group, c, false); }
+  gb25_status exchange(Group group, StreamId c) override {
+    const BufferSet b = group_info(group).set;
     return G.transport->exchange(G, b, G.elems[b] * sizeof(real), st(c));
   }
-  gb25_status local(int s, int what) override {
+  gb25_status local(int s, LocalOp what) override {
     gb25_model* m = G.slabs[s];
-    if (what == 0) return initialize_impl(m);
-    if (what == 1) {
-      return fill_halos_impl(m, false);
+    gb25_status s_;
+    switch (what) {
+      case Initialize: return initialize_impl(m);
+      case FillLocal: return fill_halos_impl(m, false);
+      case UpdateStateLocal: return update_state_local_impl(m);
+      case MaskFillLocal:
+        if ((s_ = mask_impl(m))) return s_;
+        return fill_halos_impl(m, false, true);
+      case AuxiliariesTendenciesLocal:
+        if ((s_ = compute_w_impl(m))) return s_;
+        if ((s_ = compute_p_impl(m))) return s_;
+        [[fallthrough]];
+      case TendenciesLocal:
+        if ((s_ = momentum_impl(m))) return s_;
+        if ((s_ = tracers_impl(m))) return s_;
+        return m->catke ? catke_step_local(m) : GB25_OK;
+      case FirstFluxesLocal: return atmosphere_ocean_fluxes_impl(m);   // coupled model, iteration 0: fluxes of the initial state
+      case CatkeFinishLocal: return catke_finish_local(m);
     }
-    if (what == 3) {
-      gb25_status s_;
-      if ((s_ = mask_impl(m))) return s_;
-      return fill_halos_impl(m, false, true);
-    }
-    if (what == 4) {
-      gb25_status s_;
-      if ((s_ = compute_w_impl(m))) return s_;
-      if ((s_ = compute_p_impl(m))) return s_;
-      if ((s_ = momentum_impl(m))) return s_;
-      if ((s_ = tracers_impl(m))) return s_;
-      return m->catke ? catke_step_local(m) : GB25_OK;
-    }
-    if (what == 5) return atmosphere_ocean_fluxes_impl(m);   // coupled model, iteration 0: fluxes of the initial state
-    if (what == 6) {
-      gb25_status s_;
-      if ((s_ = momentum_impl(m))) return s_;
-      if ((s_ = tracers_impl(m))) return s_;
-      return m->catke ? catke_step_local(m) : GB25_OK;
-    }
-    if (what == 7) return catke_finish_local(m);
-    return update_state_local_impl(m);
+    return fail(m, GB25_ERR_INVALID_ARGUMENT, "unknown local operation %d", (int)what);
   }
   bool velocities_ready(int s) override {
     gb25_model* m = G.slabs[s];
     return m->valid.velocities_ready(m->baro_ahead);
   }
   bool subcycle_adopted(int s) override { return G.slabs[s]->baro_adopted; }
-  gb25_status record(int slot, int c) override {
+  gb25_status record(EventSlot slot, StreamId c) override {
     gb25_model* m = G.slabs[0];
     HIPCHK(hipEventRecord(G.ev[slot], st(c)));
     return GB25_OK;
   }
-  gb25_status wait(int slot, int waiter) override {
+  gb25_status wait(EventSlot slot, StreamId waiter) override {
     gb25_model* m = G.slabs[0];
     HIPCHK(hipStreamWaitEvent(st(waiter), G.ev[slot], 0));
     return GB25_OK;
@@ -1220,22 +1220,27 @@ void group_destroy(SlabGroup* G) {
   delete G;
 }
 
-// The bundle of group 0 carries more once an option adds the chunk sums of u, v to it, and a closure brings exchanges of its
-// own (CATKE: e, J^b -- sets 8 - 10): sizes again, larger buffers if needed.  Called at the head of the composites; every rank made the same (collective) setter calls.
+// Elements per side of buffer set b: what the largest slab packs (2-D decomposition: the top row of ranks folds, the others do not;
+// every slab gets buffers of the size a folded one needs)
+size_t group_set_elems(const std::vector<gb25_model*>& slabs, BufferSet b) {
+  size_t need = 0;
+  for (gb25_model* q : slabs) need = std::max(need, (size_t)set_elems(q, b));
+  return need;
+}
+// The Bundle carries more once an option adds the chunk sums of u, v to it, and a closure brings exchanges of its own (CATKE: e,
+// J^b -- switched on after the context was built, its sets grow from one element): sizes again, larger buffers if needed.  Called
+// at the head of the composites; every rank made the same (collective) setter calls.
 gb25_status group_refresh(SlabGroup* G) {
   gb25_model* m = G->slabs[0];
   const int n = (int)G->slabs.size();
-  for (int b : {0, 3, 5, 8, 9, 10}) {   // (8 - 10: closure = CATKE switched on after the context was built -- its sets grow from one element)
-    size_t need = 0;
-    for (gb25_model* q : G->slabs)
-      need = std::max(need, (size_t)(b == 0 ? halo_buffer_elems(q, 0) : b == 3 ? fold_buffer_elems(q, 3) : b == 5 ? row_buffer_elems(q, 10)
-                                     : b == 8 ? halo_buffer_elems(q, 20) : b == 10 ? fold_buffer_elems(q, 10) : row_buffer_elems(q, 21)));
+  for (BufferSet b : {SetBundle, SetFoldBundle, SetBundleRows, SetCatkeColumns, SetCatkeRows, SetCatkeFold}) {
+    const size_t need = group_set_elems(G->slabs, b);
     if (need == G->elems[b]) continue;
     HIPCHK(G->sync_side());
     HIPCHK(hipStreamSynchronize(G->main));
     if (need > G->capacity[b]) {
       for (int s = 0; s < n; s++)
-        for (int side = 0; side < set_sides(b); side++) {
+        for (int side = 0; side < set_sides((BufferSet)b); side++) {
           if (G->send[s][b][side]) hipFree(G->send[s][b][side]);
           if (G->recv[s][b][side]) hipFree(G->recv[s][b][side]);
           G->send[s][b][side] = G->recv[s][b][side] = nullptr;
@@ -1288,23 +1293,15 @@ gb25_status group_create(gb25_model* const* slabs, int n, Transport* tr) {
     for (auto& e : G->ev)
       if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) st = GB25_ERR_HIP;
     if (st) break;
-    for (int b = 0; b < 3; b++) G->elems[b] = (size_t)halo_buffer_elems(m, b);
-    // (2-D decomposition: the top row of ranks folds, the others do not; every slab gets buffers of the size a folded one needs)
-    for (int b = 3; b < 5; b++)
-      for (int s = 0; s < n; s++) G->elems[b] = std::max(G->elems[b], (size_t)fold_buffer_elems(slabs[s], b));
-    for (int b = 5; b < 8; b++) G->elems[b] = (size_t)row_buffer_elems(m, b == 5 ? 10 : (b == 6 ? 11 : 12));
-    G->elems[8] = (size_t)halo_buffer_elems(m, 20);
-    G->elems[9] = (size_t)row_buffer_elems(m, 21);
-    for (int s = 0; s < n; s++) G->elems[10] = std::max(G->elems[10], (size_t)fold_buffer_elems(slabs[s], 10));
-    for (int b = 0; b < SlabGroup::NSETS; b++) G->capacity[b] = G->elems[b];
+    for (int b = 0; b < NSETS; b++) G->capacity[b] = G->elems[b] = group_set_elems(G->slabs, (BufferSet)b);
     G->send.resize(n);
     G->recv.resize(n);
     for (int s = 0; s < n && !st; s++)
-      for (int b = 0; b < SlabGroup::NSETS && !st; b++)
+      for (int b = 0; b < NSETS && !st; b++)
         for (int side = 0; side < 2; side++) G->send[s][b][side] = G->recv[s][b][side] = nullptr;
     for (int s = 0; s < n && !st; s++)
-      for (int b = 0; b < SlabGroup::NSETS && !st; b++)
-        for (int side = 0; side < set_sides(b) && !st; side++) {
+      for (int b = 0; b < NSETS && !st; b++)
+        for (int side = 0; side < set_sides((BufferSet)b) && !st; side++) {
           G->send[s][b][side] = G->recv[s][b][side] = nullptr;
           if (hipMalloc(&G->send[s][b][side], G->elems[b] * sizeof(real)) != hipSuccess ||
               hipMalloc(&G->recv[s][b][side], G->elems[b] * sizeof(real)) != hipSuccess)

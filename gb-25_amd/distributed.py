@@ -150,7 +150,7 @@ class SlabModel(HydrostaticFreeSurfaceModel):
             dev = torch.device("cuda", device)
 
             def exchange(buffer_set, sw, se, rw, re, nbytes):
-                # whom a buffer set travels to (set_kind in csrc/slab_step.hpp): 0 - 2, 8: the west / east ring neighbours;
+                # whom a buffer set travels to (Peer in csrc/slab_protocol.hpp): 0 - 2, 8: the west / east ring neighbours;
                 # 3, 4, 10: the fold partner; 5 - 7, 9: the southern / northern neighbour (8 - 10: CATKE's e and J^b)
                 kind = 1 if buffer_set in (3, 4, 10) else 2 if buffer_set in (5, 6, 7, 9) else 0
                 if kind == 2:            # y halos: (south, north) in the place of (west, east); null where there is no neighbour

@@ -425,7 +425,8 @@ gb25_status gb25_comm_init_local(gb25_model *const *slabs, int32_t n);
  * only) are the y halos: the "west" pointers belong to the SOUTHERN neighbour (rank - Rx), the "east" pointers to the
  * NORTHERN one (rank + Rx); a side without a neighbour has NULL pointers.  buffer_set 8, 9, 10 (closure = CATKE only: the TKE
  * tracer and J^b after their step inside compute_diffusivities!) go to the ring neighbours, to the southern / northern neighbours
- * and to the fold partner respectively, with the pointer conventions above. */
+ * and to the fold partner respectively, with the pointer conventions above.  (Which exchange group uses which buffer set: the
+ * table of groups in DESIGN.md, kGroups in csrc/slab_protocol.hpp.) */
 typedef int32_t (*gb25_exchange_fn)(void *user, int32_t buffer_set, const void *send_west, const void *send_east,
                                     void *recv_west, void *recv_east, int64_t nbytes);
 gb25_status gb25_comm_init_callback(gb25_model *m, gb25_exchange_fn fn, void *user);
@@ -434,7 +435,8 @@ gb25_status gb25_comm_finalize(gb25_model *m);
  * (ncclCommCount; 0 without RCCL).  Either pointer may be NULL. */
 gb25_status gb25_comm_info(const gb25_model *m, int32_t *transport, int32_t *comm_ranks);
 /* (tests) the sends / receives one rank of an Rx x Ry decomposition posts for an exchange group, in posting order, as text;
- * returns the bytes needed incl. the terminator.  No GPU is touched. */
+ * returns the bytes needed incl. the terminator, or -1 for a rank outside the decomposition or a `group` that is not in the table
+ * of groups (0 - 4, 6, 8, 10 - 14, 20 - 22).  No GPU is touched. */
 int64_t gb25_debug_exchange_plan(int32_t Rx, int32_t Ry, int32_t rank, int32_t folded_grid, int32_t group, char *out, int64_t cap);
 /* velocities_ready: the momentum look-ahead of the next step exists (its sub-cycle can run beside the tracer kernel);
  * subcycle_adopted: the last step adopted the sub-cycle look-ahead instead of sub-cycling inside the step. */

@@ -2,6 +2,8 @@
 order in which the LIBRARY sequences one time step of a decomposition into stages, packs, exchanges, unpacks and stream
 dependencies (a dry run of csrc/slab_step.hpp's sequencer through the C ABI: no GPU needed)."""
 import ctypes
+import hashlib
+import json
 import os
 import socket
 
@@ -430,3 +432,53 @@ def test_every_rank_sends_what_its_peer_receives(Rx, Ry, folded_grid):
         assert any(g == 0 for k, v in sends.items() if k[2] == "*" for g, _ in v)
         folds = {k[0] for k, v in sends.items() for g, _ in v if g in (6, 8, 22)}
         assert all(a // Rx == Ry - 1 for a in folds) and (not folds or folded_grid)
+
+
+# ---- the whole protocol against digests recorded from the commit before the stages, groups and buffer sets got names --------------
+_PLAN_GROUPS = (0, 1, 2, 3, 4, 6, 8, 10, 11, 12, 13, 14, 20, 21, 22)
+_DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "slab_protocol_digests.json")
+
+
+def _debug_text(fn, *args):
+    need = fn(*args, None, 0)
+    assert need > 0, args
+    buf = ctypes.create_string_buffer(need)
+    assert fn(*args, buf, need) == need
+    return buf.value
+
+
+def _sequence_digests():
+    """{"<nslabs>:<flag byte>": sha256 of the gb25_debug_sequence texts of (adopted, ready) = (0,0), (0,1), (1,0), (1,1)}"""
+    fn = load_library("Float32").gb25_debug_sequence
+    return {f"{n}:{first}": hashlib.sha256(b"".join(_debug_text(fn, n, first, a, r) for a in (0, 1) for r in (0, 1))).hexdigest()
+            for n in (1, 2, 3) for first in range(256)}
+
+
+def _plan_digests():
+    """{"<Rx>x<Ry>:<folded_grid>": sha256 of the gb25_debug_exchange_plan texts, rank by rank, of every group of _PLAN_GROUPS}"""
+    fn = load_library("Float32").gb25_debug_exchange_plan
+    return {f"{Rx}x{Ry}:{fold}": hashlib.sha256(b"".join(_debug_text(fn, Rx, Ry, r, fold, g) for r in range(Rx * Ry)
+                                                           for g in _PLAN_GROUPS)).hexdigest()
+            for Rx in (1, 2, 3, 4) for Ry in (1, 2, 3) for fold in (0, 1)}
+
+
+def _compare_with_recorded(kind, got):
+    with open(_DIGESTS) as f:
+        want = json.load(f)[kind]
+    assert sorted(got) == sorted(want)
+    wrong = [k for k in want if got[k] != want[k]]
+    if wrong:
+        print(f"{kind}: {len(wrong)} of {len(want)} cases differ, the first is {wrong[0]}: {got[wrong[0]]} != {want[wrong[0]]}")
+    assert not wrong, (kind, wrong[0])
+
+
+def test_every_sequence_is_the_recorded_one():
+    """Every order of operations the sequencer can issue -- 1 to 3 slabs, every flag byte, every (adopted, ready) -- is, to the
+    byte, the one recorded before the protocol's integers were given names (768 digests)."""
+    _compare_with_recorded("sequence", _sequence_digests())
+
+
+def test_every_exchange_plan_is_the_recorded_one():
+    """What every rank of every decomposition up to 4 x 3 posts for every exchange group (4 and 14, which no sequence emits,
+    included), with and without the zipper fold, is the recorded plan (24 digests)."""
+    _compare_with_recorded("exchange_plan", _plan_digests())

@@ -222,6 +222,9 @@ struct gb25_model {
   // TRACER_CHUNK_LEVELS): fewer, longer chunks amortise the start-up of the vertical windows, more chunks fill the chip.
   // The momentum chunking is also the association of every column integral of u, v (all their producers share it).
   int mom_chunk_levels = 12, trc_chunk_levels = 12;
+  // rows per lane of the tracer tendency kernel (tracer_rows): 0 = the rule decides; 1, 2 = GB25_TRACER_ROWS in the environment of
+  // gb25_create forced it (the A/B switch of a form with the same bits; not an option: the option table is pinned)
+  int tracer_rows_forced = 0;
   // closure = VerticalScalarDiffusivity(VerticallyImplicitTimeDiscretization(), kappa, nu); both zero: closure = nothing
   double nu = 0, kappa = 0;
   bool catke = false;                // closure = CATKEVerticalDiffusivity(): the fields GB25_E .. GB25_JB exist
@@ -1247,24 +1250,41 @@ std::array<bool, MomentumKernels::n> momentum_flags(const gb25_model* m, int par
           ahead && r.kernels_carry_w() && (r.kernels_add_correction() || part == 0)};
 }
 
-struct TracerKernels {   // k_tracer_tendencies_v5; the flag O7: ORD = 7 (WENO(order = 7)), else 5
+struct TracerKernels {   // k_tracer_tendencies_v5; the flags O7: ORD = 7 (WENO(order = 7)), else 5; R2: ROWS = 2 (two rows per lane), else 1
   static constexpr int TW = sizeof(real) == 8 ? 3 : 6;    // see MomentumKernels::MW (Float32: held to 80 VGPRs, six waves per SIMD)
   static constexpr int TW7 = sizeof(real) == 8 ? 2 : 5;   // (the order-7 windows: 9 register pairs per direction; 90-96 VGPRs without a spill)
-  static constexpr int n = 8;
-  static constexpr const char* name = "tracer (AHEAD IMM FOLD CURV LAZY O7 WFLY WCORR)";
+  // (two rows per lane: three waves per SIMD.  133 VGPRs without a spill; held to four waves -- 127 VGPRs -- the headline instance
+  // reloads three spilled pairs inside the level loop and is 0.3 % slower; held to five -- 96 VGPRs, 47 spilled dwords -- the step
+  // is 32 % slower: DESIGN section 4)
+  static constexpr int TW2 = sizeof(real) == 8 ? 2 : 3;
+  static constexpr int n = 9;
+  static constexpr const char* name = "tracer (AHEAD IMM FOLD CURV LAZY O7 WFLY WCORR R2)";
   using kernel_t = decltype(&k_tracer_tendencies_v5<TW, false, false, false>);
-  static constexpr bool admits(bool a, bool i, bool f, bool c, bool l, bool o7, bool w, bool wc) {
-    return tracer_variant(a, i, f, c, l, o7 ? 7 : 5, w, wc);
+  static constexpr bool admits(bool a, bool i, bool f, bool c, bool l, bool o7, bool w, bool wc, bool r2) {
+    return tracer_variant(a, i, f, c, l, o7 ? 7 : 5, w, wc, r2 ? 2 : 1);
   }
-  template <bool A, bool I, bool F, bool C, bool L, bool O7, bool W, bool WC>
-  static kernel_t instance() { return k_tracer_tendencies_v5<O7 ? TW7 : TW, A, I, F, C, L, O7 ? 7 : 5, W, WC>; }
+  template <bool A, bool I, bool F, bool C, bool L, bool O7, bool W, bool WC, bool R2>
+  static kernel_t instance() { return k_tracer_tendencies_v5<R2 ? TW2 : O7 ? TW7 : TW, A, I, F, C, L, O7 ? 7 : 5, W, WC, R2 ? 2 : 1>; }
 };
+// Rows per lane of the tracer kernel (tracer_tile_rows2, tendency_kernels.hpp).  Two where the instance exists (flat grid, order 5),
+// the launch covers a whole single domain -- a slab or a rank of a mesh keeps one, so that the bitwise comparisons of a decomposition
+// with the single domain compare the two forms --, the model is Float32 (Float64: 252 VGPRs, two waves, the launch 5 % slower) and the
+// blocks of 8 rows still number TRACER_ROWS2_MIN_BLOCKS: measured 1440 x 720 x 48 (4140 blocks) +1 % steps/s, 720 x 720 x 48 (2160)
+// +-0, 720 x 360 x 48 (2160 of 12 levels) -1.7 %, 360 x 360 x 48 -4 %.  GB25_TRACER_ROWS = 1 | 2 in the
+// environment of gb25_create forces the value wherever the instance exists.
+constexpr long TRACER_ROWS2_MIN_BLOCKS = 4096;
+int tracer_rows(const gb25_model* m, int nbx, int kchunks) {
+  const bool exists = !m->immersed && !m->g.cv.on && m->tracer_order == 5;
+  if (!exists || m->tracer_rows_forced == 1) return 1;
+  if (m->tracer_rows_forced == 2) return 2;
+  return (!m->slab && sizeof(real) == 4 && (long)nbx * ((m->g.Ny + 7) / 8) * kchunks >= TRACER_ROWS2_MIN_BLOCKS) ? 2 : 1;
+}
 // WCORR: the corrector through the tracer kernel -- it adds du, dv as it loads (LAZY) and writes the corrected u, v; the halo
 // cells of the next T, S are then left to the fill (no FOLD)
-std::array<bool, TracerKernels::n> tracer_flags(const gb25_model* m) {
+std::array<bool, TracerKernels::n> tracer_flags(const gb25_model* m, int rows) {
   const bool ahead = m->ab2_ahead && !m->valid.ptr_exposed, curv = m->g.cv.on, wcorr = m->route.tracer_kernel_corrects();
   return {ahead, m->immersed || curv, ahead && producers_fold(m) && !wcorr, curv, m->route.kernels_add_correction() || wcorr,
-          m->tracer_order == 7, ahead && m->route.kernels_carry_w(), wcorr};
+          m->tracer_order == 7, ahead && m->route.kernels_carry_w(), wcorr, rows == 2};
 }
 
 struct SingleKernels {   // k_tracer_tendencies_single (CATKE's e); O7 as in TracerKernels
@@ -1388,10 +1408,11 @@ gb25_status tracers_impl(gb25_model* m) {
   if (m->kernel_gen >= 2) {
     Timed t(m, GB25_K_TRACERS);
     nbx = (g.Nx + V3_OUT - 1) / V3_OUT;
-    const int nby = (g.Ny + 3) / 4;
     const int kchunks = trc_kchunks(m);
+    const int rows = tracer_rows(m, nbx, kchunks);
+    const int nby = (g.Ny + 4 * rows - 1) / (4 * rows);   // (a block: four waves of `rows` rows each)
     nb = nbx * nby * kchunks;
-    const std::array<bool, TracerKernels::n> flags = tracer_flags(m);
+    const std::array<bool, TracerKernels::n> flags = tracer_flags(m, rows);
     const bool ahead = flags[0], fold = flags[2];
     Ab2Ahead nx{};
     if (ahead) {   // predicted parameters of the next ab2_step!: the clock's dt and the model's chi
@@ -2559,6 +2580,11 @@ gb25_status gb25_create(const gb25_config* cfg, gb25_model** out) {
     // last bits between the two, so a bit-for-bit comparison of a wide single domain with its narrow ranks pins the options.
     const int nbx = (m->Nx + 63) / 64, nby = (m->Ny + 3) / 4;
     if ((long)nbx * nby * std::max(1, cfg->Nz / 24) >= 4096) m->mom_chunk_levels = m->trc_chunk_levels = 24;
+  }
+  if (const char* rows = getenv("GB25_TRACER_ROWS")) {
+    if (strcmp(rows, "1") != 0 && strcmp(rows, "2") != 0)
+      return fail(m, GB25_ERR_INVALID_ARGUMENT, "GB25_TRACER_ROWS must be 1 or 2 (unset: the library's rule)");
+    m->tracer_rows_forced = rows[0] - '0';
   }
   if (m->Nx < cfg->halo) return fail(m, GB25_ERR_INVALID_ARGUMENT, "slab narrower than the halo");
   if (m->Ry > 1) {

@@ -713,9 +713,10 @@ struct Ab2Ahead {
 // Az w(k+1) = Az w(k) - [(Axu(i+1) - Axu(i)) + (Ayn - Ays)], the east face's transport from the next lane -- starting from
 // lz.wbase at the chunk's first level (k_w_bases).  Continuity and advection then see the very same transports.
 // The variants that exist: tracer_tile's static_assert and the host's choice of instance (tracers_impl) both use this rule.
-constexpr bool tracer_variant(bool AHEAD, bool IMM, bool FOLD, bool CURV, bool LAZY, int ORD, bool WFLY, bool WCORR) {
+constexpr bool tracer_variant(bool AHEAD, bool IMM, bool FOLD, bool CURV, bool LAZY, int ORD, bool WFLY, bool WCORR, int ROWS = 1) {
   return (!CURV || IMM) && (!FOLD || AHEAD) && (!WFLY || AHEAD) && (ORD == 5 || (ORD == 7 && !FOLD && !LAZY && !WCORR)) &&
-         (!LAZY || (AHEAD && (!IMM || WCORR))) && (!WCORR || (LAZY && WFLY && IMM && !FOLD));
+         (!LAZY || (AHEAD && (!IMM || WCORR))) && (!WCORR || (LAZY && WFLY && IMM && !FOLD)) &&
+         (ROWS == 1 || (ROWS == 2 && !IMM && !CURV && ORD == 5));   // (ROWS = 2: tracer_tile_rows2, below)
 }
 template <bool AHEAD, bool IMM, bool FOLD, bool CURV = false, bool LAZY = false, int ORD = 5, bool WFLY = false, bool WCORR = false>
 __device__ __forceinline__ void tracer_tile(const Grid& g, const real* __restrict__ u, const real* __restrict__ v,
@@ -907,14 +908,222 @@ __device__ __forceinline__ void tracer_tile(const Grid& g, const real* __restric
 #undef CY
 #undef CX
 }
-template <int MINW, bool AHEAD, bool IMM, bool FOLD = false, bool CURV = false, bool LAZY = false, int ORD = 5, bool WFLY = false, bool WCORR = false>
+// ---------------------------------------------------------------------------------------------
+// ROWS = 2: TWO ROWS PER LANE (flat grid, order 5).  A wave owns 63 cells of two consecutive rows, j and j + 1.  Each row has its
+// own vertical window, carried top flux, Az w, velocities, metrics and stores; the y window is loaded once (8 rows) and the flux
+// through the face between the two rows is reconstructed once -- it is the north face of row j and the south face of row j + 1,
+// operand for operand: seven two-wide reconstructions per level for two cells instead of eight, 8 window rows instead of 14,
+// three v faces instead of four, and the level's loop, scalar loads and order logic issued once.  A block covers 8 rows.  With
+// Ny odd the last wave's upper row is a clamped duplicate of its lower one whose stores are masked; the wave leaves as one.
+// tracer_tile (one row) is left exactly as it was: its instances serve every other grid and every launch of a decomposition.
+// SAME BITS as tracer_tile: every expression keeps its operands and their order.  One of them rests on the compiler there: in
+// tracer_tile `fn - fs` is contracted into one fused multiply-add with the north product inside and the south flux rounded on its
+// own (tools/kernel_isa.py: v_pk_fma_f32 behind a v_pk_mul_f32).  A product with two uses -- the shared face -- would not be
+// contracted, so here that fused multiply-add is spelled out.  After a compiler upgrade rerun tests/test_gpu_tracer_rows.py (and the
+// full-size slab-against-single-domain tests): they compare the two forms bit for bit and would show a changed contraction.
+// ---------------------------------------------------------------------------------------------
+template <bool AHEAD, bool FOLD, bool LAZY, bool WFLY>
+__device__ __forceinline__ void tracer_tile_rows2(const Grid& g, const real* __restrict__ u, const real* __restrict__ v,
+                                                  const real* __restrict__ w, const real* __restrict__ T,
+                                                  const real* __restrict__ S, real* __restrict__ GT, real* __restrict__ GS,
+                                                  int nbx, int kchunks, const Ab2Ahead& next, const int L, const LazyCorr& lz) {
+  static_assert(tracer_variant(AHEAD, false, FOLD, false, LAZY, 5, WFLY, false, 2), "no such variant of the tracer kernel");
+  constexpr int ROWS = 2, R = 3, SZ = (int)sizeof(real);
+  const int bx = L % nbx, r = L / nbx;
+  const int kc = r % kchunks, by = r / kchunks;
+  const int klen = (g.Nz + kchunks - 1) / kchunks;
+  const int k0 = kc * klen, k1 = min(g.Nz, k0 + klen);
+  const int lane = threadIdx.x;
+  const int i = bx * V3_OUT + lane, j = (by * blockDim.y + threadIdx.y) * ROWS;
+  if (j >= g.Ny) return;                       // whole wave (both rows) leaves together: no barriers in this kernel
+  const bool writes = (lane < V3_OUT) && (i < g.Nx);
+  const int sx = g.sx, pc = g.pl_c, pv = g.pl_v;
+  // row t of the lane is row j + up[t]; its cells lie rs[t] bytes behind the lower row's (wave-uniform: they ride in the scalar
+  // offset of every access, the lane keeps ONE byte offset).  Past the last row the upper row is the lower one again.
+  int up[ROWS], rs[ROWS];
+  bool wr[ROWS];
+#pragma unroll
+  for (int t = 0; t < ROWS; t++) {
+    up[t] = (j + t < g.Ny) ? t : 0;
+    rs[t] = up[t] * sx * SZ;
+    wr[t] = writes && up[t] == t;
+  }
+  const int om = i2(g, min(i, g.Nx), j);
+  const real dy = g.dy;
+  real Az[ROWS], razc_j[ROWS], dxf_f[ROWS + 1];   // (dxf_f, dv_f, oy, v_f, Ay, fy: the y faces j .. j + 2, south to north)
+#pragma unroll
+  for (int t = 0; t < ROWS; t++) {
+    Az[t] = g.azc[j + up[t]];
+    razc_j[t] = g.razc[j + up[t]];
+  }
+#pragma unroll
+  for (int f = 0; f <= ROWS; f++) dxf_f[f] = g.dxf[j + f];
+  real du_l[ROWS], dv_f[ROWS + 1];
+  if (LAZY) {
+#pragma unroll
+    for (int t = 0; t < ROWS; t++) du_l[t] = lz.du[om + up[t] * sx];
+#pragma unroll
+    for (int f = 0; f <= ROWS; f++) dv_f[f] = lz.dv[om + f * sx];
+  }
+  const int jw_ = j - g.jws, Nyw_ = g.jwn - g.jws;   // (rows counted from the global southern wall)
+  int oy[ROWS + 1];
+#pragma unroll
+  for (int f = 0; f <= ROWS; f++) oy[f] = biased_order_face(jw_ + f, Nyw_);
+
+  // buffer views and the corner-biased byte offsets: as in tracer_tile
+  const long nzp = g.Nz + 2 * g.H;
+  const long pb = k0 + g.H - R;                 // first plane of the views (>= 0: H >= R)
+  const Buf bT = make_buf(T + pc * pb, pc * (nzp - pb)), bS = make_buf(S + pc * pb, pc * (nzp - pb)),
+            bu = make_buf(u + pc * pb, pc * (nzp - pb)), bw = make_buf(w + pc * pb, pc * (nzp + 1 - pb)),
+            bv = make_buf(v + pv * (pb + R), pv * (nzp - pb - R)), bGT = make_buf(GT + pc * pb, pc * (nzp - pb)),
+            bGS = make_buf(GS + pc * pb, pc * (nzp - pb));
+  Buf bGmT = bT, bGmS = bT, bTn = bT, bSn = bT;
+  if (AHEAD) {
+    bGmT = make_buf(next.GmT + pc * pb, pc * (nzp - pb)); bGmS = make_buf(next.GmS + pc * pb, pc * (nzp - pb));
+    bTn = make_buf(next.Tn + pc * pb, pc * (nzp - pb));   bSn = make_buf(next.Sn + pc * pb, pc * (nzp - pb));
+  }
+  const int cc = (R * pc + R * sx + R) * SZ;                    // corner -> cell
+  int vo = ic(g, min(i, g.Nx), j, R - g.H) * SZ - cc;   // (level k0 is plane R of the views)
+  int vov = iv(g, min(i, g.Nx), j, -g.H) * SZ;           // (... and plane 0 of v's)
+#define CZ(m) (((m) * pc + R * sx + R) * SZ)                     // (0, 0, m-R)
+#define CY(m) ((R * pc + (m) * sx + R) * SZ)                     // (0, m-R, 0)
+  auto recon = [](int order, bool left, const real2v* w) { return biased6<false, real2v>(order, left, w, w, w); };
+  real2v cz[ROWS][2 * R + 1];                  // vertical window of (T, S), per row
+#pragma unroll
+  for (int t = 0; t < ROWS; t++)
+#pragma unroll
+    for (int m = 0; m < 2 * R + 1; m++) cz[t][m] = v2(bload(bT, vo, CZ(m) + rs[t]), bload(bS, vo, CZ(m) + rs[t]));
+  real2v fz[ROWS];
+  real Azw_cur[ROWS];                          // WFLY: Az w on the bottom face of the current level
+#pragma unroll
+  for (int t = 0; t < ROWS; t++) {
+    const real Azw = WFLY ? Az[t] * lz.wbase[(long)kc * lz.wplane + om + up[t] * sx] : Az[t] * bload(bw, vo, cc + rs[t]);
+    Azw_cur[t] = Azw;
+    fz[t] = Azw * recon(biased_order_face(k0, g.Nz), Azw > real(0.), cz[t]);
+  }
+  // FOLD: does this wave hold cells with a periodic x image or a y layer to write?
+  const bool fold_row = FOLD && (j == 0 || j + ROWS >= g.Ny || bx * V3_OUT < g.H || bx * V3_OUT + V3_OUT > g.Nx - g.H);
+  for (int k = k0; k < k1; k++) {
+    const real dz = uniform_at(g.dzc, k), rdz = uniform_at(g.rdzc, k);   // (scalar loads: device_common.hpp)
+    // every load of the level of BOTH rows is issued here, ahead of the first wait (see tracer_tile)
+    real u_l[ROWS], v_f[ROWS + 1];
+#pragma unroll
+    for (int t = 0; t < ROWS; t++) u_l[t] = bload(bu, vo, cc + rs[t]);
+#pragma unroll
+    for (int f = 0; f <= ROWS; f++) v_f[f] = bload(bv, vov, f * sx * SZ);
+    real2v cz_next[ROWS];
+    real gmT[ROWS], gmS[ROWS];
+#pragma unroll
+    for (int t = 0; t < ROWS; t++) {
+      cz_next[t] = v2(bload(bT, vo, CZ(2 * R) + pc * SZ + rs[t]), bload(bS, vo, CZ(2 * R) + pc * SZ + rs[t]));
+      gmT[t] = gmS[t] = real(0.);
+      if (AHEAD) {
+        gmT[t] = bload(bGmT, vo, cc + rs[t]);
+        gmS[t] = bload(bGmS, vo, cc + rs[t]);
+      }
+    }
+    if (LAZY) {
+#pragma unroll
+      for (int t = 0; t < ROWS; t++) u_l[t] = u_l[t] + du_l[t];
+#pragma unroll
+      for (int f = 0; f <= ROWS; f++) v_f[f] = v_f[f] + dv_f[f];
+    }
+    real Axu[ROWS], Ay[ROWS + 1], Azw[ROWS];
+#pragma unroll
+    for (int t = 0; t < ROWS; t++) Axu[t] = dy * dz * u_l[t];
+#pragma unroll
+    for (int f = 0; f <= ROWS; f++) Ay[f] = dxf_f[f] * dz * v_f[f];
+#pragma unroll
+    for (int t = 0; t < ROWS; t++) {
+      if constexpr (WFLY) {
+        Azw[t] = Azw_cur[t] - ((__shfl_down(Axu[t], 1) - Axu[t]) + (Ay[t + 1] - Ay[t]));
+        Azw_cur[t] = Azw[t];
+      } else {
+        Azw[t] = Az[t] * bload(bw, vo, cc + pc * SZ + rs[t]);
+      }
+    }
+    real2v q[2 * R + ROWS], fx[ROWS], fy[ROWS + 1], ft[ROWS], fe[ROWS];
+#pragma unroll
+    for (int t = 0; t < ROWS; t++) {
+#pragma unroll
+      for (int m = 0; m < 2 * R; m++)
+        q[m] = v2(bload(bT, vo + m * SZ, (R * pc + R * sx) * SZ + rs[t]), bload(bS, vo + m * SZ, (R * pc + R * sx) * SZ + rs[t]));
+      fx[t] = Axu[t] * recon(5, Axu[t] > real(0.), q);
+    }
+#pragma unroll
+    for (int m = 0; m < 2 * R + ROWS; m++) q[m] = v2(bload(bT, vo, CY(m)), bload(bS, vo, CY(m)));
+    asm volatile("" : "+v"(q[0]), "+v"(q[2 * R + ROWS - 1]));   // (no load sunk into a branch of one reconstruction: see tracer_tile)
+#pragma unroll
+    for (int f = 0; f <= ROWS; f++) fy[f] = recon(oy[f], Ay[f] > real(0.), q + f);   // (the face VALUES; the fluxes are Ay fy)
+    const int ozt = biased_order_face(k + 1, g.Nz);
+#pragma unroll
+    for (int t = 0; t < ROWS; t++) {
+      ft[t] = Azw[t] * recon(ozt, Azw[t] > real(0.), cz[t] + 1);                    // top face from the vertical window
+      fe[t] = v2(__shfl_down(fx[t].x, 1), __shfl_down(fx[t].y, 1));                 // east faces = west faces of the next lane
+    }
+#pragma unroll
+    for (int t = 0; t < ROWS; t++) {
+      if (wr[t]) {
+        const real rV = razc_j[t] * rdz;
+        // fn - fs as tracer_tile's compiled code forms it (the header of this function)
+        const real2v dfy = __builtin_elementwise_fma(real2v(Ay[t + 1]), fy[t + 1], -(Ay[t] * fy[t]));
+        real2v G = -(((fe[t] - fx[t]) + dfy + (ft[t] - fz[t])) * rV);
+        if (k == g.Nz - 1 && (g.top_flux[2] || g.top_flux[3])) {
+          // compute_hydrostatic_boundary_tendency_contributions!: top flux boundary conditions (heat, fresh water)
+          const int o2 = i2(g, i, j + t);
+          if (g.top_flux[2]) G.x = G.x - g.top_flux[2][o2] * rdz;
+          if (g.top_flux[3]) G.y = G.y - g.top_flux[3][o2] * rdz;
+        }
+        bstore(bGT, vo, cc + rs[t], G.x);
+        bstore(bGS, vo, cc + rs[t], G.y);
+        if (AHEAD) {   // T, S of the NEXT step while T, S (cz[t][R]) and the new tendency are in registers
+          const real tn = ab2_advance(cz[t][R].x, G.x, gmT[t], next.dt, next.C1, next.C2);
+          const real sn = ab2_advance(cz[t][R].y, G.y, gmS[t], next.dt, next.C1, next.C2);
+          bstore(bTn, vo, cc + rs[t], tn);
+          bstore(bSn, vo, cc + rs[t], sn);
+          if (FOLD && (fold_row || k == 0 || k == g.Nz - 1)) {   // (wave-uniform: most waves and levels skip all of it)
+            const int NxB = g.Nx * SZ;
+            const bool xw = i < g.H, xe = i >= g.Nx - g.H;
+            auto images = [&](int so, bool self) {   // the cell displaced by `so` bytes (a y / z layer) and its x images
+              so += rs[t];
+              if (self) { bstore(bTn, vo, cc + so, tn); bstore(bSn, vo, cc + so, sn); }
+              if (xw) { bstore(bTn, vo + NxB, cc + so, tn); bstore(bSn, vo + NxB, cc + so, sn); }
+              if (xe) { bstore(bTn, vo - NxB, cc + so, tn); bstore(bSn, vo - NxB, cc + so, sn); }
+            };
+            images(0, false);
+            if (j + t == 0) images(-sx * SZ, true);
+            if (j + t == g.Ny - 1) images(sx * SZ, true);
+            if (k == 0) images(-pc * SZ, true);
+            if (k == g.Nz - 1) images(pc * SZ, true);
+          }
+        }
+      }
+    }
+    vo += pc * SZ;
+    vov += pv * SZ;
+#pragma unroll
+    for (int t = 0; t < ROWS; t++) {
+      fz[t] = ft[t];
+#pragma unroll
+      for (int m = 0; m < 2 * R; m++) cz[t][m] = cz[t][m + 1];
+      cz[t][2 * R] = cz_next[t];
+    }
+  }
+#undef CZ
+#undef CY
+}
+template <int MINW, bool AHEAD, bool IMM, bool FOLD = false, bool CURV = false, bool LAZY = false, int ORD = 5, bool WFLY = false, bool WCORR = false, int ROWS = 1>
 __global__ __launch_bounds__(256, MINW) void k_tracer_tendencies_v5(Grid g, const real* __restrict__ u,
                                                               const real* __restrict__ v,
                                                               const real* __restrict__ w,
                                                               const real* __restrict__ T, const real* __restrict__ S,
                                                               real* __restrict__ GT, real* __restrict__ GS, int nbx,
                                                               int kchunks, int nb, Ab2Ahead next, LazyCorr lz) {
-  tracer_tile<AHEAD, IMM, FOLD, CURV, LAZY, ORD, WFLY, WCORR>(g, u, v, w, T, S, GT, GS, nbx, kchunks, next, xcd_remap(blockIdx.x, nb), lz);
+  static_assert(tracer_variant(AHEAD, IMM, FOLD, CURV, LAZY, ORD, WFLY, WCORR, ROWS), "no such variant of the tracer kernel");
+  if constexpr (ROWS == 2)
+    tracer_tile_rows2<AHEAD, FOLD, LAZY, WFLY>(g, u, v, w, T, S, GT, GS, nbx, kchunks, next, xcd_remap(blockIdx.x, nb), lz);
+  else
+    tracer_tile<AHEAD, IMM, FOLD, CURV, LAZY, ORD, WFLY, WCORR>(g, u, v, w, T, S, GT, GS, nbx, kchunks, next, xcd_remap(blockIdx.x, nb), lz);
 }
 
 // =============================================================================================

@@ -185,6 +185,10 @@ typedef enum {
                                     lines fit 160 KB, else global memory); 1 = global memory */
   GB25_OPT_COUNT
 } gb25_option;
+/* One more schedule switch is not an option but an environment variable, read once by gb25_create: GB25_TRACER_ROWS = 1 | 2, the
+ * rows a lane of the tracer tendency kernel carries (2: the flux through the y face between them is reconstructed once; flat
+ * lat-lon grids with WENO(order = 5) only, elsewhere it is ignored).  Unset: 2 for a whole Float32 single domain of at least 4096 blocks
+ * of 63 x 8 cells per chunk of levels, 1 otherwise (every slab and every rank of a mesh).  The same bits from both. */
 
 /* Metric identifiers for gb25_get_metric (diagnostics / tests). */
 typedef enum {

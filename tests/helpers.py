@@ -29,6 +29,18 @@ def set_noisy_velocities(model, amplitude=1e-3, seed=42):
     return ui, vi
 
 
+def set_noisy_state_with_halos(model, amplitude=0.05):
+    """The baroclinic-instability state, noisy velocities of `amplitude`, and 1e-3 of counter-rng noise on every cell of the parent
+    arrays of T, S, u, v, eta, V -- EVERY halo layer included (tests/test_step_spec.py, tests/test_gpu_step_identities.py)."""
+    dtype = model.backend.dtype
+    gb.set_baroclinic_instability(model)
+    set_noisy_velocities(model, amplitude)
+    for n, seed in (("T", 5), ("S", 4), ("u", 6), ("v", 7), ("eta", 8), ("V", 9)):
+        a = model.backend.get_field(n, True)
+        a += (1e-3 * counter_rng(a.shape, seed, 1)).astype(dtype)
+        model.backend.set_field(n, a, True)
+
+
 # What the GPU tests of the diagnostics (tests/test_gpu_{diagnostics,integrals,derived,transports,averages,classes,particles}.py) share
 EPS = float(np.finfo(np.float64).eps)
 GRID_NAMES = {0: "simple_lat_lon", 1: "gaussian_islands_lat_lon", 3: "tripolar", 4: "gaussian_islands"}

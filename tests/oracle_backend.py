@@ -156,7 +156,12 @@ class OracleBackend:
         if name in ("u", "v", "T", "S", "U", "V") and self._fn("is_immersed")(C.c_void_p(self.h)):
             self._call("mask_immersed_fields")
 
-    def metric(self, name, index):
+    def metric(self, name, index=1):
+        if name == "dy":               # (one number: the spacing of a regular latitude grid, as HipBackend.metric has it)
+            f = self._fn("dy")
+            f.restype = C.c_double
+            f.argtypes = [C.c_void_p]
+            return f(self.h)
         return self._fn("metric")(self.h, METRIC_IDS[name], index)
 
     def set_catke(self, on=True):

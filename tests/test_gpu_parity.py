@@ -155,8 +155,9 @@ def test_momentum_tendencies_without_pressure_noise():
     assert rel(r.velocities.w.interior, v.velocities.w.interior) < 1e-5
 
 
-def test_smooth_flow_tendencies_elementwise():
-    """Smooth large-scale flow (all WENO stencils near their linear weights): element-wise agreement."""
+def test_smooth_flow_tendencies_normwise():
+    """Smooth large-scale flow (all WENO stencils near their linear weights): agreement of every tendency in the relative L2 norm
+    over the field (one number per field; what holds cell by cell around the tendencies is in tests/test_gpu_step_identities.py)."""
     Nx, Ny, Nz = 64, 48, 8
     r, v = make_pair(Nx, Ny, Nz, dt=60.0)
     lam = (np.arange(Nx) + 0.5) * 2 * np.pi / Nx

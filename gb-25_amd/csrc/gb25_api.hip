@@ -16,6 +16,7 @@
 #include "diagnostics_state.hpp"
 #include "validity.hpp"
 #include "step_route.hpp"
+#include "subcycle_plan.hpp"
 
 #include <cmath>
 #include <cstdarg>
@@ -179,7 +180,7 @@ struct gb25_model {
   int fold_fills = 1;
   bool composite = false;            // inside gb25_time_step / gb25_loop (the phase entry points leave halos alone, as the
                                      // reference's phases do: there the producers do not fold)
-  bool ahead_ts_folded = false, ahead_eta_folded = false, last_baro_folded = false;
+  bool ahead_ts_folded = false, ahead_eta_folded = false;
   int split_tendencies = 1;          // slab of a decomposition: interior tile columns before the x-halo bundle has arrived
   int baro_whole = 1;                // narrow slab: the whole sub-cycle in one launch (option SUBCYCLE_WHOLE)
   int sub_priority = 0;              // slab: the stream of the look-ahead's substeps is a high-priority one (read when the exchange context is built)
@@ -233,7 +234,7 @@ struct gb25_model {
   Field catke_src;                   // 2-D: the top boundary condition of e (surface TKE flux / dz of the top cell)
   real* catke_e_star = nullptr;   // where the last k_catke_tke_step left e* (e, or catke_scratch)
   bool implicit_lds_raised[2] = {false, false};   // k_implicit_vertical's dynamic-LDS attribute (Nz > 128), likewise
-  bool whole_attr_set[2][2] = {{false, false}, {false, false}};   // k_barotropic_whole's dynamic-LDS attribute, per instance, on THIS model's device
+  bool whole_attr_set[4] = {false, false, false, false};   // k_barotropic_whole's dynamic-LDS attribute, per instance (SubcyclePlan::instance()), on THIS model's device
   int comm_timeout_s = 180;          // option COMM_TIMEOUT_SECONDS
   int roctx_ranges = 1;              // option ROCTX_RANGES
   int substep_order = 0;             // option SUBSTEP_ORDER
@@ -1658,10 +1659,118 @@ gb25_status tall_rows_impl(gb25_model* m, real* buf, bool pack) {
   return GB25_OK;
 }
 
-// own: (slab) the interior columns of eta, U, V, G.U, G.V still sit in the canonical arrays -- copied into the work arrays here,
-// or read in place by the one-launch kernel; layers_done: set when the kernel also wrote the y layers of the new eta, U, V
-gb25_status barotropic_impl(gb25_model* m, real dt, bool ahead = false, const InteriorCopies* own = nullptr,
-                            bool* layers_done = nullptr) {
+// ---- WHAT the sub-cycle runs is decided in one place, plan_subcycle (subcycle_plan.hpp; DESIGN.md, "The forms of the sub-cycle").
+// barotropic_impl builds the plan's setting from the model, binds the model's buffers to the plan, and carries the plan out.
+
+// the argument of k_copy_interior_columns, built piece by piece (up to five), and its launch
+struct ColumnCopies {
+  InteriorCopies C{};
+  int rmax = 0;   // the most rows of any piece
+  void add(real* dst, int dsx, int dxo, const real* src, int ssx, int sxo, int rows) {
+    const int q = C.n++;
+    C.dst[q] = dst; C.dsx[q] = dsx; C.dxo[q] = dxo;
+    C.src[q] = src; C.ssx[q] = ssx; C.sxo[q] = sxo; C.rows[q] = rows;
+    rmax = std::max(rmax, rows);
+  }
+  void launch(gb25_model* m, int rows) const {
+    hipLaunchKernelGGL(k_copy_interior_columns, dim3((m->g.Nx + 255) / 256, rows, C.n), dim3(256), 0, m->stream, C, m->g.Nx);
+  }
+};
+// the kernel instances of a form, in the order of SubcyclePlan::instance()
+struct SubstepKernels {   // k_barotropic_substep<IMM, ORDER>
+  using kernel_t = void (*)(Grid, Baro, real, real);
+  static kernel_t at(int i) {
+    static const kernel_t table[4] = {k_barotropic_substep<false, 0>, k_barotropic_substep<false, 1>,
+                                      k_barotropic_substep<true, 0>, k_barotropic_substep<true, 1>};
+    return table[i];
+  }
+};
+struct BlockedKernels {   // k_barotropic_multi<S, TY, IMM>
+  using kernel_t = void (*)(Grid, BaroMulti, real);
+  static kernel_t at(int i) {
+    static const kernel_t table[6] = {k_barotropic_multi<3, 16, false>, k_barotropic_multi<5, 17, false>, k_barotropic_multi<7, 16, false>,
+                                      k_barotropic_multi<3, 16, true>, k_barotropic_multi<5, 17, true>, k_barotropic_multi<7, 16, true>};
+    return table[i];
+  }
+};
+struct WholeKernels {   // k_barotropic_whole<BW_NS, IMM, TY>
+  using kernel_t = void (*)(Grid, BaroMulti, real);
+  static kernel_t at(int i) {
+    static const kernel_t table[4] = {k_barotropic_whole<BW_NS, false, 17>, k_barotropic_whole<BW_NS, false, 24>,
+                                      k_barotropic_whole<BW_NS, true, 17>, k_barotropic_whole<BW_NS, true, 24>};
+    return table[i];
+  }
+};
+
+// own: (slab) the pieces of the interior columns of eta, U, V, G.U, G.V, which still sit in the canonical arrays
+SubcycleSetting subcycle_setting(const gb25_model* m, bool ahead, const ColumnCopies* own) {
+  const Grid& g = m->g;
+  SubcycleSetting c{};
+  c.Nx = g.Nx; c.Ny = g.Ny; c.H = g.H; c.W = m->W; c.Wy = m->Wy; c.Wys = m->Wys;
+  c.slab = m->slab; c.curv = g.cv.on; c.north_fold = g.cv.north_fold; c.ys_open = m->ys_open; c.yn_open = m->yn_open;
+  c.immersed = m->immersed;
+  c.Ns = m->Ns;
+  c.subcycle_block = m->baro_block; c.substep_order = m->substep_order; c.subcycle_whole = m->baro_whole;
+  c.n_cu = m->n_cu; c.real_bytes = (int)sizeof(real);
+  c.ahead = ahead; c.own_given = own != nullptr; c.own_five = own && own->C.n == 5;
+  c.composite = m->composite; c.producers_fold = producers_fold(m);
+  return c;
+}
+
+// the model's buffers in the roles of the plan, each chosen by the array set and by `ahead` (the look-ahead reads G.U, G.V of the
+// momentum look-ahead and writes the partner buffers of eta, U, V and of the filtered state)
+struct SubcycleBuffers {
+  // eta, U, V: what the next launch reads and writes, the second scratch set, and where the results go.  The state the sub-cycle
+  // starts from is only read; the launches alternate between two scratch sets
+  real *cur[3], *nxt[3], *other[3], *out[3];
+  real* bar[3];         // the running averages ...
+  size_t bar_elems;     // (one allocation)
+  Field* filtered[3];   // ... and the canonical filtered-state arrays (compared by compare_states), where the wide ones are published
+  const real *GU, *GV, *Hfc, *Hcf;
+  CurvBaro cb;
+  void rotate() {
+    for (int q = 0; q < 3; q++) { real* w_ = nxt[q]; nxt[q] = other[q]; other[q] = w_; cur[q] = w_; }
+  }
+  Baro baro(const SubcyclePlan& p) const {
+    Baro b;
+    b.eta0 = cur[0]; b.U0 = cur[1]; b.V0 = cur[2];
+    b.eta1 = nxt[0]; b.U1 = nxt[1]; b.V1 = nxt[2];
+    b.etab = bar[0]; b.Ub = bar[1]; b.Vb = bar[2];
+    b.GU = GU; b.GV = GV; b.Hfc = Hfc; b.Hcf = Hcf;
+    b.sx = p.sx; b.xo = p.xo; b.ilo = p.ilo; b.ihi = p.ihi; b.wrap = p.wrap;
+    b.jlo = p.jlo; b.jhi = p.jhi; b.yo = p.yo; b.top_open = p.top_open;
+    return b;
+  }
+};
+SubcycleBuffers bind_subcycle(gb25_model* m, const SubcyclePlan& p, bool ahead) {
+  const Grid& g = m->g;
+  const bool wide = p.arrays == SubcycleArrays::Wide;
+  SubcycleBuffers B{};
+  for (int q = 0; q < 3; q++) {
+    B.cur[q] = wide ? m->wide[0][q].d : m->f[GB25_ETA + q].d;
+    B.nxt[q] = wide ? m->wide[1][q].d : m->pp[q].d;
+    B.other[q] = wide ? m->wide[0][q].d : m->pp2[q].d;
+    B.out[q] = ahead ? m->ahead_eta[q].d : m->f[GB25_ETA + q].d;
+    B.filtered[q] = ahead ? &m->ahead_bar[q] : &m->f[GB25_ETA_BAR + q];
+    B.bar[q] = wide ? m->wideBar[q].d : B.filtered[q]->d;
+    B.bar_elems += wide ? m->wideBar[q].elems() : B.filtered[q]->elems();
+  }
+  B.GU = wide ? m->wideG[0].d : (ahead ? m->ahead_G[0].d : m->f[GB25_GN_BT_U].d);
+  B.GV = wide ? m->wideG[1].d : (ahead ? m->ahead_G[1].d : m->f[GB25_GN_BT_V].d);
+  B.Hfc = wide ? m->d_wideH[0] : m->d_H[0];
+  B.Hcf = wide ? m->d_wideH[1] : m->d_H[1];
+  B.cb = wide ? CurvBaro{m->d_wideM[0], m->d_wideM[1], m->d_wideM[2], m->d_wideM[3], m->d_wideM[4]}
+              : CurvBaro{g.cv.dyfc, g.cv.dxcf, g.cv.razcc, g.cv.rdxfc, g.cv.rdycf};
+  return B;
+}
+
+struct SubcycleDone {   // what barotropic_impl did (a failure has done neither)
+  gb25_status status;
+  bool halo_images_written;   // the last launch wrote every halo cell of the new eta, U, V: no fill for them in the step
+  bool layers_written;        // the kernel wrote the y layers of the new eta, U, V: no fill after the sub-cycle of a slab
+  SubcycleDone(gb25_status s, bool h = false, bool l = false) : status(s), halo_images_written(h), layers_written(l) {}
+};
+SubcycleDone barotropic_impl(gb25_model* m, real dt, bool ahead = false, const ColumnCopies* own = nullptr) {
   const Grid& g = m->g;
   if (m->baro_inflight && !ahead) {
     // a look-ahead that is not being adopted (changed dt, ...) may still be running on the side stream, and it uses
@@ -1670,204 +1779,82 @@ gb25_status barotropic_impl(gb25_model* m, real dt, bool ahead = false, const In
     m->baro_inflight = false;
   }
   Timed t(m, GB25_K_BAROTROPIC);
-  m->last_baro_folded = false;
-  // (option SUBSTEP_ORDER = 1 exists in the one-substep-per-launch kernel only: the temporally blocked ones keep the default order)
-  const int bblock = m->substep_order ? 1 : m->baro_block;
-  // work arrays: a slab's are widened in x (filled by the exchange of group 1 / 3 before this is called), a folded grid's are
-  // tall (image rows beyond the pivot row: a slab's come from its partner before this is called, a single domain's below)
-  const bool wide = m->slab || g.cv.north_fold;
+  const SubcyclePlan p = plan_subcycle(subcycle_setting(m, ahead, own));
+  SubcycleBuffers B = bind_subcycle(m, p, ahead);
   const real dtau = (real)m->dtau_frac * dt;
-  dim3 b(64, 4);
-  Baro bb;
-  real *cur[3], *nxt[3], *other[3], *out[3];
-  bb.jlo = -m->Wys;
-  bb.jhi = g.Ny + m->Wy;
-  bb.yo = g.H + m->Wys;
-  bb.top_open = (g.cv.north_fold || m->yn_open) ? 1 : 0;
-  if (!wide) {
-    size_t nbar = m->f[GB25_ETA_BAR].elems() + m->f[GB25_U_BAR].elems() + m->f[GB25_V_BAR].elems();
-    if (bblock <= 1)   // (the blocked kernels start their averages from zero themselves)
-      HIPCHK(hipMemsetAsync(ahead ? m->bars_ahead : m->bars, 0, nbar * sizeof(real), m->stream));
-    // the state the sub-cycle starts from is only read; the substeps alternate between two scratch sets
-    for (int q = 0; q < 3; q++) {
-      cur[q] = m->f[GB25_ETA + q].d; nxt[q] = m->pp[q].d; other[q] = m->pp2[q].d;
-      out[q] = ahead ? m->ahead_eta[q].d : m->f[GB25_ETA + q].d;
+  // ---- before the kernels
+  if (p.copy_state_in) {
+    ColumnCopies C;
+    for (int q = 0; q < 5; q++) {
+      const Field& src = q < 3 ? m->f[GB25_ETA + q] : (ahead ? m->ahead_G[q - 3] : m->f[GB25_GN_BT_U + q - 3]);
+      C.add(q < 3 ? m->wide[0][q].d : m->wideG[q - 3].d, p.sx, p.xo, src.d, g.sx, g.H, src.ny);
     }
-    const Field* bar = ahead ? m->ahead_bar : &m->f[GB25_ETA_BAR];
-    bb.etab = bar[0].d; bb.Ub = bar[1].d; bb.Vb = bar[2].d;
-    bb.GU = ahead ? m->ahead_G[0].d : m->f[GB25_GN_BT_U].d;
-    bb.GV = ahead ? m->ahead_G[1].d : m->f[GB25_GN_BT_V].d;
-    bb.sx = g.sx; bb.xo = g.H; bb.ilo = 0; bb.ihi = g.Nx; bb.wrap = 1;
-    bb.Hfc = m->d_H[0]; bb.Hcf = m->d_H[1];
-  } else {
-    const int wsx = g.Nx + 2 * m->W;
-    if (!m->slab) {
-      // single folded domain: the state and the forcing into the work arrays, then the image rows beyond the pivot row
-      InteriorCopies C{};
-      int rmax = 0;
-      for (int q = 0; q < 5; q++) {
-        const Field& src = q < 3 ? m->f[GB25_ETA + q] : (ahead ? m->ahead_G[q - 3] : m->f[GB25_GN_BT_U + q - 3]);
-        C.dst[q] = q < 3 ? m->wide[0][q].d : m->wideG[q - 3].d; C.dsx[q] = wsx; C.dxo[q] = m->W;
-        C.src[q] = src.d; C.ssx[q] = g.sx; C.sxo[q] = g.H; C.rows[q] = src.ny;
-        rmax = std::max(rmax, src.ny);
-      }
-      C.n = 5;
-      hipLaunchKernelGGL(k_copy_interior_columns, dim3((g.Nx + 255) / 256, rmax, C.n), dim3(256), 0, m->stream, C, g.Nx);
-      gb25_status s;
-      if ((s = tall_rows_impl(m, m->tall_buf, true))) return s;
-      if ((s = tall_rows_impl(m, m->tall_buf, false))) return s;
-    }
-    if (bblock <= 1)
-      HIPCHK(hipMemsetAsync(m->wideBar[0].d, 0,
-                            (m->wideBar[0].elems() + m->wideBar[1].elems() + m->wideBar[2].elems()) * sizeof(real),
-                            m->stream));
-    for (int q = 0; q < 3; q++) {
-      cur[q] = m->wide[0][q].d; nxt[q] = m->wide[1][q].d; other[q] = m->wide[0][q].d;
-      out[q] = ahead ? m->ahead_eta[q].d : m->f[GB25_ETA + q].d;
-    }
-    bb.etab = m->wideBar[0].d; bb.Ub = m->wideBar[1].d; bb.Vb = m->wideBar[2].d;
-    bb.GU = m->wideG[0].d; bb.GV = m->wideG[1].d;
-    bb.sx = wsx; bb.xo = m->W;
-    if (m->slab) { bb.ilo = -m->W + 1; bb.ihi = g.Nx + m->W - 1; bb.wrap = 0; }
-    else { bb.ilo = 0; bb.ihi = g.Nx; bb.wrap = 1; }
-    bb.Hfc = m->d_wideH[0]; bb.Hcf = m->d_wideH[1];
+    C.launch(m, C.rmax);
+    gb25_status s;
+    if ((s = tall_rows_impl(m, m->tall_buf, true))) return s;
+    if ((s = tall_rows_impl(m, m->tall_buf, false))) return s;
   }
-  const bool imm = m->immersed;
-  bool finalize_after = false;
-  // temporally blocked: the lat-lon kernel (row metrics) or its curvilinear sibling (per-point metrics); on canonical arrays
-  // (single domain), widened slabs and the tall arrays of a folded grid alike
-  const bool blocked_curv = bblock > 1 && g.cv.on;
-  const bool blocked = bblock > 1;
-  const CurvBaro cb = wide ? CurvBaro{m->d_wideM[0], m->d_wideM[1], m->d_wideM[2], m->d_wideM[3], m->d_wideM[4]}
-                           : CurvBaro{g.cv.dyfc, g.cv.dxcf, g.cv.razcc, g.cv.rdxfc, g.cv.rdycf};
-  const int rows = bb.jhi - bb.jlo + (bb.top_open ? 1 : 0);   // (no wall: the face row behind the last advanced row is carried along)
-  auto fill_multi = [&](BaroMulti& bm, int s, int Sk) {
-    bb.eta0 = cur[0]; bb.U0 = cur[1]; bb.V0 = cur[2];
-    bb.eta1 = nxt[0]; bb.U1 = nxt[1]; bb.V1 = nxt[2];
-    bm.b = bb;
-    bm.ns = std::min(Sk, m->Ns - s);
-    bm.first = s == 0;
-    bm.last = s + Sk >= m->Ns;
-    if (bm.first && bm.last && !wide && !ahead) {
-      // a sub-cycle short enough for ONE launch would read and write the canonical eta, U, V in the same launch
-      bm.last = 0;
-      finalize_after = true;
-    }
-    bm.eta_out = out[0]; bm.U_out = out[1]; bm.V_out = out[2];
-    bm.eb_out = bm.ub_out = bm.vb_out = nullptr;
-    bm.fold = 0;
-    bm.out_halo = m->slab ? g.H : 0;   // (a widened slab also writes the x halo columns of the new eta, U, V)
-    bm.out_js = m->ys_open ? -g.H : 0;   // (... and a rank of a 2-D decomposition the halo rows of its open sides)
-    bm.out_jn = m->yn_open ? g.Ny + g.H : g.Ny;
-    for (int q = 0; q < 5; q++) bm.own_src[q] = nullptr;
-    bm.layers = 0;
-    if (wide) {
-      const Field* fb = ahead ? m->ahead_bar : &m->f[GB25_ETA_BAR];
-      bm.eb_out = fb[0].d; bm.ub_out = fb[1].d; bm.vb_out = fb[2].d;
-    }
-    for (int q = 0; q < BT_SMAX; q++) bm.w[q] = (s + q < m->Ns) ? (real)m->weights[s + q] : real(0.);
-  };
-  // a narrow slab: fewer tiles than the chip has CUs -- the whole sub-cycle in ONE launch (k_barotropic_whole)
-  constexpr int NSW = 21;   // (the substeps of SplitExplicitFreeSurface(substeps = 30); other counts take the blocked launches)
-  const int wcols = (bb.ihi - bb.ilo + BT_TX - 1) / BT_TX, wrows = bb.jhi - bb.jlo;
-  // rows per tile: 17 (125 KB of LDS) or, when only that brings the tile count under the number of CUs, 24 (140 KB)
-  const int wty = wcols * ((wrows + 16) / 17) <= m->n_cu ? 17 : 24;
-  const int wtiles = wcols * ((wrows + wty - 1) / wty);
-  // (Float32: the Float64 build would need twice the LDS)
-  const bool whole = blocked && !g.cv.on && m->slab && m->baro_whole && m->Ns == NSW && wtiles <= m->n_cu && sizeof(real) == 4;
-  // (the one-launch kernel reads the own columns in place only when it writes elsewhere -- the look-ahead's partner buffers;
-  // inside its own step the results go into the very arrays other blocks are still loading their rings from)
-  const bool in_place = whole && own && own->n == 5 && ahead;
-  if (own && !in_place)
-    hipLaunchKernelGGL(k_copy_interior_columns, dim3((g.Nx + 255) / 256, g.sy_v, own->n), dim3(256), 0, m->stream, *own, g.Nx);
-  if (whole) {
-    void (*kern)(Grid, BaroMulti, real) =
-        wty == 17 ? (imm ? k_barotropic_whole<NSW, true, 17> : k_barotropic_whole<NSW, false, 17>)
-                  : (imm ? k_barotropic_whole<NSW, true, 24> : k_barotropic_whole<NSW, false, 24>);
-    const size_t lds = (size_t)5 * (BT_TX + 2 * NSW) * (wty + 2 * NSW) * sizeof(real);
-    // (the attribute belongs to the DEVICE: kept per model, not per process -- a host driving several GPUs from one process, or
-    // two threads, must not skip it on the second device)
-    if (!m->whole_attr_set[imm ? 1 : 0][wty == 17 ? 0 : 1]) {
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      m->whole_attr_set[imm ? 1 : 0][wty == 17 ? 0 : 1] = true;
-    }
+  if (p.zero_averages) HIPCHK(hipMemsetAsync(B.bar[0], 0, B.bar_elems * sizeof(real), m->stream));
+  if (p.copy_own_first) own->launch(m, g.sy_v);
+  // ---- the kernels
+  auto multi = [&](int i) {
+    const SubcycleLaunch L = p.launch(i);
     BaroMulti bm;
-    fill_multi(bm, 0, NSW);
-    if (in_place)
-      for (int q = 0; q < 5; q++) bm.own_src[q] = own->src[q];
-    if (own) {
-      bm.layers = 1;
-      if (layers_done) *layers_done = true;
-    }
-    dim3 gm(wcols, (wrows + wty - 1) / wty);
-    hipLaunchKernelGGL(kern, gm, dim3(BW_NT), lds, m->stream, g, bm, dtau);
-    LAUNCHCHK();
-    return GB25_OK;
+    bm.b = B.baro(p);
+    for (int q = 0; q < BT_SMAX; q++) bm.w[q] = (L.s0 + q < m->Ns) ? (real)m->weights[L.s0 + q] : real(0.);
+    bm.ns = L.ns; bm.first = L.first; bm.last = L.last;
+    bm.eta_out = B.out[0]; bm.U_out = B.out[1]; bm.V_out = B.out[2];
+    bm.eb_out = p.publish_through_eb_out ? B.filtered[0]->d : nullptr;
+    bm.ub_out = p.publish_through_eb_out ? B.filtered[1]->d : nullptr;
+    bm.vb_out = p.publish_through_eb_out ? B.filtered[2]->d : nullptr;
+    bm.fold = (p.halo_images_on_last && L.last) ? 1 : 0;
+    bm.out_halo = p.out_halo; bm.out_js = p.out_js; bm.out_jn = p.out_jn;
+    for (int q = 0; q < 5; q++) bm.own_src[q] = p.own_in_place ? own->C.src[q] : nullptr;
+    bm.layers = p.write_layers ? 1 : 0;
+    return bm;
+  };
+  const dim3 grid(p.grid_x, p.grid_y), block(p.block_x, p.block_y);
+  // (the attribute belongs to the DEVICE: kept per model, not per process -- a host driving several GPUs from one process, or
+  // two threads, must not skip it on the second device)
+  if (p.form == SubcycleForm::Whole && !m->whole_attr_set[p.instance()]) {
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(WholeKernels::at(p.instance())),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
+    m->whole_attr_set[p.instance()] = true;
   }
-  if (blocked_curv) {
-    constexpr int Sk = 5, TYc = 17;
-    dim3 gm((bb.ihi - bb.ilo + BT_TX - 1) / BT_TX, (rows + TYc - 1) / TYc);
-    for (int s = 0; s < m->Ns; s += Sk) {
-      BaroMulti bm;
-      fill_multi(bm, s, Sk);
-      hipLaunchKernelGGL((k_barotropic_multi_curv<Sk, TYc>), gm, dim3(BT_NT), 0, m->stream, g, bm, cb, dtau);
-      for (int q = 0; q < 3; q++) { real* w_ = nxt[q]; nxt[q] = other[q]; other[q] = w_; cur[q] = w_; }
+  for (int i = 0; i < p.n_launches; i++) {
+    switch (p.form) {
+      case SubcycleForm::PerSubstep:
+        hipLaunchKernelGGL(SubstepKernels::at(p.instance()), grid, block, 0, m->stream, g, B.baro(p), dtau, (real)m->weights[i]);
+        break;
+      case SubcycleForm::PerSubstepCurv:
+        hipLaunchKernelGGL(k_barotropic_substep_curv, grid, block, 0, m->stream, g, B.baro(p), B.cb, dtau, (real)m->weights[i]);
+        break;
+      case SubcycleForm::Blocked:
+        hipLaunchKernelGGL(BlockedKernels::at(p.instance()), grid, block, 0, m->stream, g, multi(i), dtau);
+        break;
+      case SubcycleForm::BlockedCurv:
+        hipLaunchKernelGGL((k_barotropic_multi_curv<5, 17>), grid, block, 0, m->stream, g, multi(i), B.cb, dtau);
+        break;
+      case SubcycleForm::Whole:
+        hipLaunchKernelGGL(WholeKernels::at(p.instance()), grid, block, p.lds_bytes, m->stream, g, multi(i), dtau);
+        break;
     }
-  } else if (blocked) {
-    // temporally blocked: S substeps per launch on (64 x TY) tiles
-    const int S = std::min(bblock, (int)BT_SMAX);
-    constexpr int TYb = 16, TY5 = 17;   // (5 substeps per launch: 64 x 17 tiles keep LDS under 40 KB -- four blocks per CU)
-    const int tyb = (S > 3 && S <= 5) ? TY5 : TYb;
-    dim3 gm((bb.ihi - bb.ilo + BT_TX - 1) / BT_TX, (bb.jhi - bb.jlo + tyb - 1) / tyb);
-    void (*kern)(Grid, BaroMulti, real) =
-        imm ? (S <= 3 ? k_barotropic_multi<3, TYb, true> : (S <= 5 ? k_barotropic_multi<5, TY5, true> : k_barotropic_multi<7, TYb, true>))
-            : (S <= 3 ? k_barotropic_multi<3, TYb, false> : (S <= 5 ? k_barotropic_multi<5, TY5, false> : k_barotropic_multi<7, TYb, false>));
-    const int Sk = S <= 3 ? 3 : (S <= 5 ? 5 : 7);
-    for (int s = 0; s < m->Ns; s += Sk) {
-      BaroMulti bm;
-      fill_multi(bm, s, Sk);
-      bm.fold = (!wide && producers_fold(m) && m->composite && bm.last) ? 1 : 0;
-      if (bm.last) m->last_baro_folded = bm.fold != 0;
-      hipLaunchKernelGGL(kern, gm, dim3(BT_NT), 0, m->stream, g, bm, dtau);
-      for (int q = 0; q < 3; q++) { real* w_ = nxt[q]; nxt[q] = other[q]; other[q] = w_; cur[q] = w_; }
-    }
-  } else {
-    dim3 gr = grid2(bb.ihi - bb.ilo, g.cv.on ? rows : bb.jhi - bb.jlo, b);
-    for (int s = 0; s < m->Ns; s++) {
-      bb.eta0 = cur[0]; bb.U0 = cur[1]; bb.V0 = cur[2];
-      bb.eta1 = nxt[0]; bb.U1 = nxt[1]; bb.V1 = nxt[2];
-      if (g.cv.on)
-        hipLaunchKernelGGL(k_barotropic_substep_curv, gr, b, 0, m->stream, g, bb, cb, dtau, (real)m->weights[s]);
-      else
-        hipLaunchKernelGGL(m->substep_order ? (imm ? k_barotropic_substep<true, 1> : k_barotropic_substep<false, 1>)
-                                            : (imm ? k_barotropic_substep<true> : k_barotropic_substep<false>),
-                           gr, b, 0, m->stream, g, bb, dtau, (real)m->weights[s]);
-      for (int q = 0; q < 3; q++) { real* w_ = nxt[q]; nxt[q] = other[q]; other[q] = w_; cur[q] = w_; }
-    }
+    B.rotate();
   }
-  if (blocked && !finalize_after) {   // the last blocked launch wrote eta, U, V and published the averages
-    LAUNCHCHK();
-    return GB25_OK;
+  // ---- after them (the last launch of several substeps wrote eta, U, V and published the averages itself)
+  if (p.finalize_after) {
+    const dim3 b(64, 4);
+    hipLaunchKernelGGL(k_barotropic_finalize, grid2(p.fin_nx, p.fin_ny, b), b, 0, m->stream, g, B.out[0], B.out[1], B.out[2],
+                       B.bar[0], B.bar[1], B.bar[2], p.sx, p.xo, p.fin_yo, p.out_halo, p.out_js, p.out_jn);
   }
-  const int fjs = m->ys_open ? -g.H : 0, fjn = m->yn_open ? g.Ny + g.H : g.Ny;
-  dim3 gi = grid2(g.Nx, fjn - fjs, b);
-  if (m->slab) gi = grid2(g.Nx + 2 * g.H, fjn - fjs, b);   // (with the x halo columns: nothing is exchanged after the sub-cycle)
-  hipLaunchKernelGGL(k_barotropic_finalize, gi, b, 0, m->stream, g, out[0], out[1], out[2], bb.etab, bb.Ub, bb.Vb,
-                     bb.sx, bb.xo, wide ? bb.yo : g.H, m->slab ? g.H : 0, fjs, fjn);
-  if (wide) {  // publish the averages in the canonical filtered-state arrays (compared by compare_states)
-    InteriorCopies C{};
-    int rmax = 0;
-    for (int q = 0; q < 3; q++) {
-      Field& dst = ahead ? m->ahead_bar[q] : m->f[GB25_ETA_BAR + q];
-      C.dst[q] = dst.d; C.dsx[q] = dst.nx; C.dxo[q] = g.H;
-      C.src[q] = m->wideBar[q].d + (size_t)m->Wys * bb.sx; C.ssx[q] = bb.sx; C.sxo[q] = bb.xo; C.rows[q] = dst.ny;
-      rmax = std::max(rmax, dst.ny);
-    }
-    C.n = 3;
-    hipLaunchKernelGGL(k_copy_interior_columns, dim3((g.Nx + 255) / 256, rmax, C.n), dim3(256), 0, m->stream, C, g.Nx);
+  if (p.publish_after) {
+    ColumnCopies C;
+    for (int q = 0; q < 3; q++)
+      C.add(B.filtered[q]->d, B.filtered[q]->nx, g.H, B.bar[q] + (size_t)m->Wys * p.sx, p.sx, p.xo, B.filtered[q]->ny);
+    C.launch(m, C.rmax);
   }
   LAUNCHCHK();
-  return GB25_OK;
+  return {GB25_OK, p.halo_images_on_last, p.write_layers};
 }
 
 // cache_previous_tendencies!: G^- <- G^n is a pointer exchange; the next tendency evaluation overwrites the (old G^-) buffers
@@ -2196,7 +2183,7 @@ gb25_status ab2_step_impl(gb25_model* m, double dt, int euler) {
   if ((s = ab2_local_impl(m, (real)dt, chi))) return s;
   Halo2 hG = halo2_G(m);
   if ((s = fill_halos_2d(m, hG))) return s;
-  return barotropic_impl(m, (real)dt);
+  return barotropic_impl(m, (real)dt).status;
 }
 
 // u, v <- u + du, v + dv: ends the state in which the corrector lives inside its consumers (before a composite call returns)
@@ -2344,16 +2331,18 @@ gb25_status time_step_impl(gb25_model* m, int euler, bool more = false) {
   }
   HIPCHK(hipEventRecord(m->ev_join, side));
   // ---- velocity branch (main stream)
+  bool eta_halos_fresh;   // the last launch of this step's sub-cycle wrote the halo cells of eta, U, V
   if (baro_adopted) {
     // the sub-cycle of this step ran in the previous one: adopt eta, U, V and the filtered state
     if (m->baro_inflight) HIPCHK(hipStreamWaitEvent(main, m->ev_baro, 0));
     m->baro_inflight = false;
     adopt_subcycle(m);
-    m->last_baro_folded = m->ahead_eta_folded;
-  } else if ((s = barotropic_impl(m, (real)dt))) {
-    return s;
+    eta_halos_fresh = m->ahead_eta_folded;
+  } else {
+    const SubcycleDone done = barotropic_impl(m, (real)dt);
+    if (done.status) return done.status;
+    eta_halos_fresh = done.halo_images_written;
   }
-  const bool eta_halos_fresh = m->last_baro_folded;   // the last launch of this step's sub-cycle wrote them
   m->time += dt;
   m->iteration += 1;
   // The reference fills the halos of u, v, eta, U, V here as well as after the corrector.  On a single slab the
@@ -2438,8 +2427,9 @@ gb25_status time_step_impl(gb25_model* m, int euler, bool more = false) {
       HIPCHK(hipStreamWaitEvent(m->baro_stream, m->ev_mom, 0));
       {
         OnStream on(m, m->baro_stream);
-        s = barotropic_impl(m, m->valid.ahead_uv_dt, true);
-        m->ahead_eta_folded = m->last_baro_folded;
+        const SubcycleDone done = barotropic_impl(m, m->valid.ahead_uv_dt, true);
+        s = done.status;
+        m->ahead_eta_folded = done.halo_images_written;
       }
       if (s) return s;
       HIPCHK(hipEventRecord(m->ev_baro, m->baro_stream));
@@ -2447,8 +2437,9 @@ gb25_status time_step_impl(gb25_model* m, int euler, bool more = false) {
     } else {
       // ... on the main stream, between the momentum and the tracer tendencies: three launches of 60 us with the GPU to
       // themselves, no cross-stream dependency at all.
-      if ((s = barotropic_impl(m, m->valid.ahead_uv_dt, true))) return s;
-      m->ahead_eta_folded = m->last_baro_folded;
+      const SubcycleDone done = barotropic_impl(m, m->valid.ahead_uv_dt, true);
+      if (done.status) return done.status;
+      m->ahead_eta_folded = done.halo_images_written;
     }
     m->valid.record_subcycle_lookahead();
   }

@@ -9,6 +9,7 @@
 // (i,j) column and march in k.
 #pragma once
 #include "device_common.hpp"
+#include "subcycle_plan.hpp"   // the tile constants of the sub-cycle kernels: BT_TX, BT_NT, BT_SMAX, BW_NT
 
 namespace gb25 {
 
@@ -1225,7 +1226,6 @@ __global__ __launch_bounds__(256) void k_barotropic_substep_curv(Grid g, Baro b,
 // ring absorbs the one-cell-per-substep growth of the dependency cone), keeps the running averages in registers
 // and writes everything back once.  Per-point arithmetic and summation order are those of k_barotropic_substep.
 // ---------------------------------------------------------------------------------------------
-constexpr int BT_TX = 64, BT_NT = 256, BT_SMAX = 24;   // (24: the whole sub-cycle in one launch, k_barotropic_whole)
 struct BaroMulti {
   Baro b;
   real w[BT_SMAX];
@@ -1429,7 +1429,6 @@ __global__ __launch_bounds__(BT_NT, (BT_S <= 5 ? 4 : 3)) void k_barotropic_multi
 // point updates of the full ring).  Per-point arithmetic, summation order and outputs are those of k_barotropic_multi's
 // first-and-last launch.  Dynamic LDS: 5 (64 + 2 NS) (BW_TY + 2 NS) reals.
 // (BW_TY rows per tile: 17, or 24 -- 140 KB of LDS -- when that brings a wider slab's tile count under the number of CUs)
-constexpr int BW_NT = 1024;
 template <int NS, bool IMM, int BW_TY = 17>
 __global__ __launch_bounds__(BW_NT) void k_barotropic_whole(Grid g, BaroMulti bm, real dtau) {
   constexpr int RX = BT_TX + 2 * NS, RY = BW_TY + 2 * NS, NP = RX * RY, PPT = (NP + BW_NT - 1) / BW_NT;

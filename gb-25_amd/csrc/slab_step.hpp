@@ -379,38 +379,29 @@ gb25_status stage_subcycle(gb25_model* m, bool ahead, bool substeps_only) {
   int nc = 0;
   group_pieces(m, ahead ? Group::BaroWideAhead : Group::BaroWide, ps, &nc);
   const bool two_halves = g.cv.north_fold || m->Ry > 1;
-  InteriorCopies C{};
+  ColumnCopies C;
   if (!substeps_only) {
-    int rmax = 0;
-    for (auto& p : ps) {
-      const int q = C.n++;
-      C.dst[q] = p.dst; C.dsx[q] = p.dst_sx; C.dxo[q] = p.dst_xo;
-      C.src[q] = p.src; C.ssx[q] = p.src_sx; C.sxo[q] = p.src_xo; C.rows[q] = (int)p.rows;
-      rmax = std::max(rmax, (int)p.rows);
-    }
+    for (auto& p : ps) C.add(p.dst, p.dst_sx, p.dst_xo, p.src, p.src_sx, p.src_xo, (int)p.rows);
     // (a plain slab hands the copy to the sub-cycle: its one-launch kernel reads the own columns where they are)
-    if (two_halves)
-      hipLaunchKernelGGL(k_copy_interior_columns, dim3((g.Nx + 255) / 256, rmax, C.n), dim3(256), 0, m->stream, C, g.Nx);
+    if (two_halves) C.launch(m, C.rmax);
   }
   LAUNCHCHK();
   if (two_halves && !substeps_only) return GB25_OK;
-  const InteriorCopies* own = two_halves ? nullptr : &C;
-  bool layers_done = false;
+  const SubcycleDone done = barotropic_impl(m, ahead ? m->valid.ahead_uv_dt : (real)dt, ahead, two_halves ? nullptr : &C);
+  if (done.status) return done.status;
   if (ahead) {
-    if ((s = barotropic_impl(m, m->valid.ahead_uv_dt, true, own, &layers_done))) return s;
     Halo2 h2{};
     for (int q = 0; q < 3; q++) { h2.p[q] = m->ahead_eta[q].d; h2.is_v[q] = q == 2; }
     h2.n = 3;
     // y layer, x halo columns included: the widened sub-cycle computed those like the neighbour did (no BaroHaloAhead)
-    if (!layers_done && (s = fill_halos_impl(m, false, true, 2, 3, nullptr, true, &h2))) return s;
+    if (!done.layers_written && (s = fill_halos_impl(m, false, true, 2, 3, nullptr, true, &h2))) return s;
     m->valid.record_subcycle_lookahead();
     return GB25_OK;
   }
-  if ((s = barotropic_impl(m, (real)dt, false, own, &layers_done))) return s;
   m->time += dt;
   m->iteration += 1;
   // y layer of the new eta, U, V, x halo columns included (computed by the widened sub-cycle: no BaroHalo)
-  return layers_done ? GB25_OK : fill_halos_impl(m, false, true, 2);
+  return done.layers_written ? GB25_OK : fill_halos_impl(m, false, true, 2);
 }
 
 // OwnColumns: everything that needs nothing from the neighbours runs while the exchanges are in flight: the barotropic corrector

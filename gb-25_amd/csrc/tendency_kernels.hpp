@@ -845,12 +845,22 @@ __device__ __forceinline__ void tracer_tile(const Grid& g, const real* __restric
     } else {
       Azw = Az * bload(bw, vo, cc + pc * SZ);
     }
+    // The lane's own cell, element R of the x and of the y window, is cz[R]: T and S are not written by this kernel, so the register
+    // holds the bits a load would bring.  Order 5 only: with order 7 and an immersed boundary the compiler, seeing one value in
+    // three windows, forms its sums differently (one more v_pk_add_f32 per instance) and the last bits of the tendencies change.
+    constexpr bool OWN = ORD == 5;
     real2v q[2 * R + 1];
 #pragma unroll
-    for (int m = 0; m < 2 * R; m++) q[m] = v2(bload(bT, vo + m * SZ, (R * pc + R * sx) * SZ), bload(bS, vo + m * SZ, (R * pc + R * sx) * SZ));
+    for (int m = 0; m < 2 * R; m++) {
+      if (OWN && m == R) q[m] = cz[R];
+      else q[m] = v2(bload(bT, vo + m * SZ, (R * pc + R * sx) * SZ), bload(bS, vo + m * SZ, (R * pc + R * sx) * SZ));
+    }
     const real2v fx = Axu * recon(IMM ? ox : ORD, Axu > real(0.), q);
 #pragma unroll
-    for (int m = 0; m < 2 * R + 1; m++) q[m] = v2(bload(bT, vo, CY(m)), bload(bS, vo, CY(m)));
+    for (int m = 0; m < 2 * R + 1; m++) {
+      if (OWN && m == R) q[m] = cz[R];
+      else q[m] = v2(bload(bT, vo, CY(m)), bload(bS, vo, CY(m)));
+    }
     // (the two ends of the window are used by the full-order branch of one reconstruction each: left alone, the compiler sinks
     // their loads INTO that branch -- the common one -- and waits for each separately: two more sleeps per level)
     asm volatile("" : "+v"(q[0]), "+v"(q[2 * R]));
@@ -910,12 +920,13 @@ __device__ __forceinline__ void tracer_tile(const Grid& g, const real* __restric
 }
 // ---------------------------------------------------------------------------------------------
 // ROWS = 2: TWO ROWS PER LANE (flat grid, order 5).  A wave owns 63 cells of two consecutive rows, j and j + 1.  Each row has its
-// own vertical window, carried top flux, Az w, velocities, metrics and stores; the y window is loaded once (8 rows) and the flux
+// own vertical window, carried top flux, Az w, velocities, metrics and stores; the y window is loaded once (8 rows: six loaded, the
+// rows j and j + 1 taken from the vertical windows, as is the own cell of either x window: 45 loads per level, not 53) and the flux
 // through the face between the two rows is reconstructed once -- it is the north face of row j and the south face of row j + 1,
 // operand for operand: seven two-wide reconstructions per level for two cells instead of eight, 8 window rows instead of 14,
 // three v faces instead of four, and the level's loop, scalar loads and order logic issued once.  A block covers 8 rows.  With
 // Ny odd the last wave's upper row is a clamped duplicate of its lower one whose stores are masked; the wave leaves as one.
-// tracer_tile (one row) is left exactly as it was: its instances serve every other grid and every launch of a decomposition.
+// tracer_tile (one row) serves every other grid and every launch of a decomposition.
 // SAME BITS as tracer_tile: every expression keeps its operands and their order.  One of them rests on the compiler there: in
 // tracer_tile `fn - fs` is contracted into one fused multiply-add with the north product inside and the south flux rounded on its
 // own (tools/kernel_isa.py: v_pk_fma_f32 behind a v_pk_mul_f32).  A product with two uses -- the shared face -- would not be
@@ -1001,6 +1012,8 @@ __device__ __forceinline__ void tracer_tile_rows2(const Grid& g, const real* __r
     Azw_cur[t] = Azw;
     fz[t] = Azw * recon(biased_order_face(k0, g.Nz), Azw > real(0.), cz[t]);
   }
+  // is the upper row a row of its own (not the clamped duplicate)?  In a scalar register: the choice below is the wave's
+  const bool upper_real = __builtin_amdgcn_readfirstlane(up[ROWS - 1]) != 0;
   // FOLD: does this wave hold cells with a periodic x image or a y layer to write?
   const bool fold_row = FOLD && (j == 0 || j + ROWS >= g.Ny || bx * V3_OUT < g.H || bx * V3_OUT + V3_OUT > g.Nx - g.H);
   for (int k = k0; k < k1; k++) {
@@ -1046,12 +1059,20 @@ __device__ __forceinline__ void tracer_tile_rows2(const Grid& g, const real* __r
 #pragma unroll
     for (int t = 0; t < ROWS; t++) {
 #pragma unroll
-      for (int m = 0; m < 2 * R; m++)
-        q[m] = v2(bload(bT, vo + m * SZ, (R * pc + R * sx) * SZ + rs[t]), bload(bS, vo + m * SZ, (R * pc + R * sx) * SZ + rs[t]));
+      for (int m = 0; m < 2 * R; m++) {
+        if (m == R) q[m] = cz[t][R];   // (the lane's own cell: held in the vertical window, not loaded again)
+        else q[m] = v2(bload(bT, vo + m * SZ, (R * pc + R * sx) * SZ + rs[t]), bload(bS, vo + m * SZ, (R * pc + R * sx) * SZ + rs[t]));
+      }
       fx[t] = Axu[t] * recon(5, Axu[t] > real(0.), q);
     }
 #pragma unroll
-    for (int m = 0; m < 2 * R + ROWS; m++) q[m] = v2(bload(bT, vo, CY(m)), bload(bS, vo, CY(m)));
+    for (int m = 0; m < 2 * R + ROWS; m++)
+      if (m < R || m >= R + ROWS) q[m] = v2(bload(bT, vo, CY(m)), bload(bS, vo, CY(m)));
+    // rows j and j + 1 of the y window are the two own cells -- unless the upper row is the clamped duplicate (Ny odd, last wave):
+    // the window's row j + 1 is then the halo row, which no vertical window holds
+    q[R] = cz[0][R];
+    if (upper_real) q[R + 1] = cz[1][R];
+    else q[R + 1] = v2(bload(bT, vo, CY(R + 1)), bload(bS, vo, CY(R + 1)));
     asm volatile("" : "+v"(q[0]), "+v"(q[2 * R + ROWS - 1]));   // (no load sunk into a branch of one reconstruction: see tracer_tile)
 #pragma unroll
     for (int f = 0; f <= ROWS; f++) fy[f] = recon(oy[f], Ay[f] > real(0.), q + f);   // (the face VALUES; the fluxes are Ay fy)

@@ -13,6 +13,7 @@ from .averages import (AveragesHost, average_terms, eddy_flux, eddy_kinetic_ener
 from .model import (CATKEVerticalDiffusivity, default_ocean_closure, Field, HydrostaticFreeSurfaceModel, VerticalScalarDiffusivity,
                     baroclinic_instability_model, budget, density_anomaly, first_time_step, initialize, kinetic_energy,
                     mixed_layer_depth, potential_density, vorticity,
+                    at_depths, isosurface_depth, layer_thickness, on_isosurface,
                     heat_transport, meridional_transport, overturning, section_transport,
                     overturning_in_classes, water_mass_census, zonal_power_spectrum, zonal_spectrum,
                     Averages, averages, run_averaged,
@@ -29,6 +30,7 @@ from .classes import (class_bins, class_edges, class_sums_host, class_terms, cla
                       total_classes)
 from .spectra import (combine_spectra, cospectrum, dominant_wavenumber, host_table, power_spectrum, spectrum_host,
                       zonal_coefficients)
+from .surfaces import gather_surfaces, on_surfaces_host, surfaces_of_profiles
 # (the submodule first, as for the averages: the name `particles` of the package is the function)
 from .particles import (Particles, ParticlesHost, advance_host, exchange_particles, particle_rates, particles, run_with_particles,
                         sample_host, seed_particles, seed_positions)

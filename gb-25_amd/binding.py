@@ -61,6 +61,7 @@ ABI_SYMBOLS = [
     "gb25_transport_bytes", "gb25_get_transport",
     "gb25_class_sum_bytes", "gb25_get_class_sums",
     "gb25_spectral_coefficient_bytes", "gb25_get_spectrum_table", "gb25_get_zonal_spectrum", "gb25_get_derived_zonal_spectrum",
+    "gb25_compute_on_surfaces", "gb25_get_on_surfaces",
     "gb25_averages_info_bytes", "gb25_averages_begin", "gb25_averages_accumulate", "gb25_averages_get_info", "gb25_average_dims",
     "gb25_get_average", "gb25_average_device_ptr", "gb25_averages_end",
     "gb25_particles_info_bytes", "gb25_particles_begin", "gb25_particles_set", "gb25_particles_get", "gb25_particles_advance",
@@ -75,6 +76,11 @@ CLASS_WHAT = {"faces_y": 0, "cells": 1}                                   # gb25
 CLASS_VARIABLES = {"T": 0, "S": 1, "potential_density": 2}                # gb25_class_variable
 CLASS_SHAPES = {"rows": 0, "cumulative": 1, "total": 2}                   # gb25_class_shape
 CLASS_MAX_BINS = 256                                                      # GB25_CLASS_MAX_BINS
+# gb25_surface_variable, gb25_surface_carried, gb25_surface_status, GB25_SURFACE_MAX_VALUES
+SURFACE_VARIABLES = {"T": 0, "S": 1, "potential_density": 2, "depth": 3}
+SURFACE_CARRIED = {"depth": 0, "T": 1, "S": 2, "e": 3, "kinetic_energy": 4, "density_anomaly": 5, "potential_density": 6}
+SURFACE_STATUS = {"found": 0, "outcrop": 1, "grounded": 2, "dry": 3}
+SURFACE_MAX_VALUES = 64
 AVERAGE_GROUPS = {"means": 1, "squares": 2, "fluxes": 4}              # gb25_average_group
 # gb25_average: name -> id; the first six are the MEANS, the next five the SQUARES, the last six the FLUXES
 AVERAGE_IDS = {n: q for q, n in enumerate(["u", "v", "w", "T", "S", "eta", "uu", "vv", "TT", "SS", "etaeta",
@@ -394,6 +400,8 @@ def load_library(float_type="Float32"):
     lib.gb25_get_zonal_spectrum.argtypes = [P, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64, C.POINTER(C.c_int64)]
     lib.gb25_get_derived_zonal_spectrum.argtypes = [P, C.c_int, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P, C.c_int64,
                                                     C.POINTER(C.c_int64)]
+    lib.gb25_compute_on_surfaces.argtypes = [P, C.c_int, C.c_int, P, C.c_int32, C.POINTER(P), C.POINTER(P), C.POINTER(C.c_int32)]
+    lib.gb25_get_on_surfaces.argtypes = [P, C.c_int, C.c_int, P, C.c_int32, P, P]
     lib.gb25_averages_begin.argtypes = [P, C.c_int32, C.c_int32, C.c_int32]
     lib.gb25_averages_accumulate.argtypes = [P, C.c_double]
     lib.gb25_averages_get_info.argtypes = [P, C.POINTER(AveragesInfo)]
@@ -681,6 +689,33 @@ class HipBackend:
         else:
             self._call("gb25_get_zonal_spectrum", FIELD_IDS[source], *tail)
         return out, int(bad.value)
+
+    # ---- fields on surfaces on the device (include/gb25.h: "fields on surfaces"; gb-25_amd/surfaces.py).  variable: "T", "S",
+    #      "potential_density", "depth"; carried: "depth", "T", "S", "e", "kinetic_energy", "density_anomaly", "potential_density"
+    #      (or the ids of the header); values: 1 .. 64 finite targets, in any order
+    @staticmethod
+    def _surface_args(variable, carried, values):
+        values = np.ascontiguousarray(np.atleast_1d(np.asarray(values, np.float64)).reshape(-1))
+        return (int(SURFACE_VARIABLES.get(variable, variable)), int(SURFACE_CARRIED.get(carried, carried)),
+                values.ctypes.data_as(C.c_void_p), values.size), values
+
+    def compute_on_surfaces(self, variable, carried, values):
+        """(device pointer of the results, device pointer of the status bytes, dims): both packed [Nx, Ny, n], i fastest, the
+        results of this backend's dtype; read-only, valid until the next call on this model."""
+        args, _keep = self._surface_args(variable, carried, values)
+        p, ps, d = C.c_void_p(), C.c_void_p(), (C.c_int32 * 3)()
+        self._call("gb25_compute_on_surfaces", *args, C.byref(p), C.byref(ps), d)
+        return p.value, ps.value, tuple(d)
+
+    def get_on_surfaces(self, variable, carried, values):
+        """(result [i, j, n], status uint8 [i, j, n]): for every column and every value the depth of the surface `variable` =
+        value (carried "depth") or the carried quantity interpolated onto it; status: SURFACE_STATUS."""
+        args, _keep = self._surface_args(variable, carried, values)
+        Nx, Ny, _ = self.field_dims("T", False)
+        out = np.empty((args[3], Ny, Nx), dtype=self.dtype)
+        status = np.empty((args[3], Ny, Nx), dtype=np.uint8)
+        self._call("gb25_get_on_surfaces", *args, out.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p))
+        return out.transpose(2, 1, 0), status.transpose(2, 1, 0)
 
     # ---- time averages accumulated on the device (include/gb25.h: "time averages and eddy fluxes"); names: AVERAGE_IDS
     def averages_begin(self, groups=("means", "squares", "fluxes"), levels=None):

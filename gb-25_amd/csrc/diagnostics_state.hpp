@@ -1,7 +1,8 @@
 // diagnostics_state.hpp -- every piece of memory and bookkeeping the read-only diagnostics own (diagnostics_host.hpp,
-// averages_host.hpp, classes_host.hpp, particles_host.hpp), as ONE member of gb25_model.  Host only; included by gb25_api.hip
-// behind the kernel headers (PartState: particle_kernels.hpp; GB25_A_COUNT and the info structs: include/gb25.h); like Field it is
-// local to that translation unit, so the libraries export nothing of it.
+// averages_host.hpp, classes_host.hpp, particles_host.hpp, spectrum_host.hpp, surfaces_host.hpp), as ONE member of gb25_model.
+// Host only; included by gb25_api.hip behind the kernel headers (PartState: particle_kernels.hpp; SURF_MAX: surface_kernels.hpp;
+// GB25_A_COUNT and the info structs: include/gb25.h); like Field it is local to that translation unit, so the libraries export
+// nothing of it.
 // No stepping kernel reads or writes anything here.  release() is the one place that frees it (gb25_destroy), its two parts
 // serve gb25_averages_end and gb25_particles_end; invalidate_tables() is what a rebuild of the grid or of the bottom calls.
 #pragma once
@@ -50,6 +51,13 @@ struct DiagState {
   unsigned spec_skipped = 0;
   double* spec_table = nullptr;
   bool spec_valid = false, spec_lds_raised = false;
+  // fields on surfaces (gb25_compute_on_surfaces, gb25_get_on_surfaces): ONE allocation -- the padded targets (SURF_MAX doubles),
+  // then the values and the status bytes of one call --, made by the first call, made anew when a call asks for more values.
+  // The host copy of the padded targets the upload reads (a word of the model: no copy is ever pending from a frame that has
+  // returned)
+  void* surfaces = nullptr;
+  size_t surf_values = 0;
+  double surf_targets[gb25::SURF_MAX] = {};
   // time averages (gb25_averages_*): the accumulators of the active groups and the array a normalized read-out is divided into
   // -- ONE allocation (avg_acc[0] is its base: MEANS is always active), made by gb25_averages_begin, freed by gb25_averages_end
   // and gb25_destroy --, the window, the sample count and weight_sum (avg_info)
@@ -113,6 +121,7 @@ struct DiagState {
     drop(transport);
     drop(class_sums);
     drop(spectrum);
+    drop(surfaces);
     release_tables();
     release_averages();
     release_particles();

@@ -13,6 +13,7 @@
 #include "class_kernels.hpp"
 #include "particle_kernels.hpp"
 #include "spectrum_kernels.hpp"
+#include "surface_kernels.hpp"
 #include "diagnostics_state.hpp"
 #include "validity.hpp"
 #include "step_route.hpp"
@@ -3699,3 +3700,4 @@ gb25_status gb25_profile_get(gb25_model* m, gb25_kernel k, int64_t* launches, do
 #include "classes_host.hpp"
 #include "particles_host.hpp"
 #include "spectrum_host.hpp"
+#include "surfaces_host.hpp"

@@ -259,6 +259,11 @@ class LocalSlabEnsemble:
         offsets = [(b.rx * self.Nx_loc, b.ry * self.Ny_loc) for b in self.backends]
         return combine_spectra([p[0] for p in parts], offsets), sum(p[1] for p in parts)
 
+    # fields on surfaces: every slab searches its own columns, the results are placed by global offset (gb-25_amd/surfaces.py)
+    def on_surfaces(self, variable, carried, values):
+        from .surfaces import gather_surfaces
+        return gather_surfaces(self, variable, carried, values)
+
     # time averages: likewise (gb-25_amd/averages.py); every slab accumulates its own interior, the read-out is placed by
     # global offset
     def averages_begin(self, groups=("means", "squares", "fluxes"), levels=None):

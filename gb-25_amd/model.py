@@ -70,6 +70,11 @@ class Field:
         """The top interior level, [i, j, 1]: `indices = (:, :, Nz)` of the reference's surface writer."""
         return self.levels(self._b.field_dims(self.name, False)[2] - 1, 1)
 
+    def at_depths(self, depths):
+        """(values [i, j, n], status uint8 [i, j, n]): this field (T, S or e) interpolated to the fixed depths `depths` [m,
+        positive] between cell centres, on the device (at_depths of this module)."""
+        return _on_surfaces(self._b, "depth", self.name, depths)
+
     def zonal_spectrum(self, wavenumbers=None, levels=None):
         """(X [level, row, m] complex128, nonfinite_lines): the zonal wavenumber coefficients of every interior line, computed
         where the field lives (zonal_spectrum of this module)."""
@@ -254,6 +259,40 @@ def mixed_layer_depth(model, threshold=0.03):
     """Depth [m, positive] at which the potential density exceeds the top cell's by `threshold` kg/m^3, linearly interpolated
     between cell centres; the column's depth where it never does, 0 over land.  [i, j]."""
     return _derived(model, "mixed_layer_depth", threshold)[:, :, 0]
+
+
+def _on_surfaces(b, variable, carried, values):
+    from .surfaces import on_surfaces                # (the kernel, or the numpy restatement on a backend without it)
+    return on_surfaces(b, variable, carried, values)
+
+
+def isosurface_depth(model, variable, values):
+    """(depth [i, j, n], status uint8 [i, j, n]): the depth [m, positive] at which `variable` -- "potential_density", "T" or
+    "S" -- first takes each of `values` (1 .. 64 of them, in any order), marching down from the top and interpolating linearly
+    between cell centres, on the device (include/gb25.h, gb25_get_on_surfaces): a sloping isopycnal is the baroclinic
+    instability.  status: binding.SURFACE_STATUS -- found; outcrop: the surface lies above the top cell, depth = the top face;
+    grounded: below the bottom cell, depth = the column's bottom face; dry: land, 0."""
+    return _on_surfaces(model.backend, variable, "depth", values)
+
+
+def on_isosurface(model, carried, of="potential_density", values=()):
+    """(values [i, j, n], status): the quantity `carried` -- "T", "S", "e", "kinetic_energy", "density_anomaly",
+    "potential_density" -- on the surfaces where `of` takes each of `values`; where a surface outcrops or is grounded, the value
+    of the top or of the bottom cell."""
+    return _on_surfaces(model.backend, of, carried, values)
+
+
+def at_depths(model, carried, depths):
+    """(values [i, j, n], status): `carried` at the fixed depths `depths` [m, positive], interpolated between cell centres -- the
+    exponential vertical grid has no level at 300 m.  A depth at a cell centre returns that cell's value unchanged."""
+    return _on_surfaces(model.backend, "depth", carried, depths)
+
+
+def layer_thickness(model, variable, edges):
+    """Thickness [m] of the layers between consecutive surfaces `variable` = edges[e], [i, j, len(edges) - 1]: differences of
+    isosurface_depth (surfaces.layer_thickness)."""
+    from .surfaces import layer_thickness as thickness
+    return thickness(isosurface_depth(model, variable, edges)[0])
 
 
 def _transport(model, faces, shape, window=None):

@@ -763,6 +763,61 @@ gb25_status gb25_get_derived_zonal_spectrum(gb25_model *m, gb25_derived d, doubl
                                             int32_t k_first, int32_t k_count, gb25_spectral_coefficient *out, int64_t count,
                                             int64_t *nonfinite_lines);
 
+/* ---- fields on surfaces on the device (csrc/surface_kernels.hpp, k_on_surfaces): where a surface lies and what is on it -- the
+ *      depth of an isopycnal, an isotherm or an isohaline, temperature, salinity or kinetic energy on it, the thickness of the
+ *      layer between two of them (differences of two depths: gb-25_amd/surfaces.py layer_thickness), and a field at fixed depths,
+ *      which on the exponential vertical grid are no model levels -- without whole parent arrays crossing PCIe for a loop over
+ *      columns.  Same contract as the derived fields: the state gb25_get_field would return, READ-ONLY for the schedule (nothing
+ *      pinned, every look-ahead alive), LOCAL on a rank (a rank's interior; gather by global_offset: gb-25_amd/surfaces.py
+ *      gather_surfaces), bitwise repeatable, launches under GB25_K_DIAGNOSTICS on the model's stream.
+ *
+ *      DEFINITIONS.  Per (c,c) column: kb = the first wet level (0 on a grid without a bottom table), ks = Nz - 1, k increases
+ *      upward; zc = GB25_M_ZC, zf = GB25_M_ZF as gb25_get_metric returns them.
+ *      THE SEARCH VARIABLE q(k), a double:
+ *        GB25_SV_T, GB25_SV_S           (double) of the stored value
+ *        GB25_SV_POTENTIAL_DENSITY      (double) of the value gb25_get_derived(GB25_D_POTENTIAL_DENSITY) hands out: rounded to the
+ *                                       float type first, the same bits
+ *        GB25_SV_DEPTH                  -zc(k)
+ *      THE CARRIED QUANTITY f(k):
+ *        GB25_SC_DEPTH                  none: the result is the depth of the surface in metres, positive
+ *        GB25_SC_T, GB25_SC_S           the stored value
+ *        GB25_SC_E                      the stored value; GB25_ERR_INVALID_ARGUMENT unless closure = CATKEVerticalDiffusivity()
+ *        GB25_SC_KINETIC_ENERGY, GB25_SC_DENSITY_ANOMALY, GB25_SC_POTENTIAL_DENSITY
+ *                                       the value gb25_get_derived hands out, rounded to the float type, then (double)
+ *      THE TARGETS: values[0 .. n), 1 <= n <= GB25_SURFACE_MAX_VALUES, every one finite, in any order; each is handled
+ *      independently of the others.  Anything else is GB25_ERR_INVALID_ARGUMENT.
+ *      THE SEARCH for one value c: for k = Nz - 2 down to kb, with qa = q(k+1), qb = q(k), fa = f(k+1), fb = f(k): the pair CROSSES
+ *      when qa and qb are finite and (qa <= c && c <= qb) || (qb <= c && c <= qa) (with a NaN both comparisons are false by
+ *      themselves; a pair with an infinity is skipped as well).  At the FIRST crossing from the top
+ *              frac  = (qa == qb) ? 0 : (c - qa) / (qb - qa)          g = 1 - frac
+ *              depth = -(zc(k+1) * g + zc(k) * frac)                  value = fa * g + fb * frac
+ *      -- the two-product form is exact at both ends of a pair: a depth slice taken at a level's centre returns that level's value
+ *      unchanged.  Every operation in fp64, in the written order, NO fused multiply-adds, an IEEE division, the result rounded
+ *      once to the float type (gb-25_amd/surfaces.py restates it with numpy bit for bit).  Status GB25_SURF_FOUND.
+ *      NO CROSSING: with down = (q(kb) >= q(ks)),
+ *              (c > q(ks)) == down     GB25_SURF_GROUNDED   depth = -zf(kb)   value = f(kb)    (the surface lies below the bottom)
+ *              otherwise               GB25_SURF_OUTCROP    depth = -zf(Nz)   value = f(ks)    (it lies above the top)
+ *              a dry column (no wet level)   GB25_SURF_DRY      depth = 0         value = 0
+ *
+ *      RESULTS: PACKED, out[i + Nx (j + Ny n)] in the library's float type -- the depth for GB25_SC_DEPTH, the value for every other
+ *      carried quantity --, and a status byte (gb25_surface_status) per element in an array of the same shape.  They live in a
+ *      buffer the model owns (made by the first call, made anew when a call asks for more values -- refused with
+ *      GB25_ERR_OUT_OF_MEMORY before the allocation when the device has less free --, freed by gb25_destroy).
+ *      gb25_compute_on_surfaces: *dev, *dev_status (may be NULL) point into it, device_dims (may be NULL) = Nx, Ny, n; read-only,
+ *      complete when the call returns, valid until the next call on m.  gb25_get_on_surfaces: the same and one device-to-host
+ *      copy of each array; host_status may be NULL. */
+#define GB25_SURFACE_MAX_VALUES 64
+typedef enum { GB25_SV_T = 0, GB25_SV_S, GB25_SV_POTENTIAL_DENSITY, GB25_SV_DEPTH, GB25_SV_COUNT } gb25_surface_variable;
+typedef enum {
+  GB25_SC_DEPTH = 0, GB25_SC_T, GB25_SC_S, GB25_SC_E, GB25_SC_KINETIC_ENERGY, GB25_SC_DENSITY_ANOMALY, GB25_SC_POTENTIAL_DENSITY,
+  GB25_SC_COUNT
+} gb25_surface_carried;
+typedef enum { GB25_SURF_FOUND = 0, GB25_SURF_OUTCROP = 1, GB25_SURF_GROUNDED = 2, GB25_SURF_DRY = 3 } gb25_surface_status;
+gb25_status gb25_compute_on_surfaces(gb25_model *m, gb25_surface_variable v, gb25_surface_carried c, const double *values, int32_t n,
+                                     const void **dev, const uint8_t **dev_status, int32_t device_dims[3]);
+gb25_status gb25_get_on_surfaces(gb25_model *m, gb25_surface_variable v, gb25_surface_carried c, const double *values, int32_t n,
+                                 void *host, uint8_t *host_status /* may be NULL */);
+
 /* ---- time averages and eddy fluxes accumulated on the device (csrc/averages_kernels.hpp, k_averages_accumulate): what the other
  *      diagnostics cannot do -- remember something between two calls.  The time-mean state, eddy kinetic energy and tracer
  *      variance, the eddy heat and salt fluxes <v'T'>, <u'T'>, <w'T'>: Oceananigans' AveragedTimeInterval, without five parent arrays

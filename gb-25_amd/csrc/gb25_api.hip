@@ -1527,8 +1527,10 @@ gb25_status implicit_vertical_impl(gb25_model* m, int kind, real dt) {
   }
   // deeper columns: the column and the per-thread elimination factors in LDS
   int T = 256;
-  while (T > 64 && (size_t)(2 * T + 2) * g.Nz * sizeof(real) > 64 * 1024) T /= 2;
-  const size_t lds = (size_t)(2 * T + 2) * g.Nz * sizeof(real);
+  auto lds_of = [&](int t) { return (size_t)(2 * t + 2) * g.Nz * sizeof(real); };
+  while (T > 64 && lds_of(T) > 64 * 1024) T /= 2;
+  if (lds_of(T) > 160 * 1024) T = 32;   // (half a wave per block before the solve is refused: Float64 fits 157 levels at 64 threads, 310 at 32)
+  const size_t lds = lds_of(T);
   if (lds > 160 * 1024) return fail(m, GB25_ERR_INVALID_ARGUMENT, "the implicit vertical solve keeps a column in LDS: Nz = %d is too deep", g.Nz);
   auto kern = m->immersed ? k_implicit_vertical<true> : k_implicit_vertical<false>;
   // (a function attribute is set per device: the flag lives in the model, not in the process)

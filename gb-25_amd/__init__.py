@@ -14,6 +14,8 @@ from .model import (CATKEVerticalDiffusivity, default_ocean_closure, Field, Hydr
                     baroclinic_instability_model, budget, density_anomaly, first_time_step, initialize, kinetic_energy,
                     mixed_layer_depth, potential_density, vorticity,
                     at_depths, isosurface_depth, layer_thickness, on_isosurface,
+                    baroclinic_wave_speed, buoyancy_frequency, deformation_radius, eady_growth_rate, eddy_resolution, ertel_pv,
+                    richardson_number, shear_squared,
                     heat_transport, meridional_transport, overturning, section_transport,
                     overturning_in_classes, water_mass_census, zonal_power_spectrum, zonal_spectrum,
                     Averages, averages, run_averaged,
@@ -31,6 +33,7 @@ from .classes import (class_bins, class_edges, class_sums_host, class_terms, cla
 from .spectra import (combine_spectra, cospectrum, dominant_wavenumber, host_table, power_spectrum, spectrum_host,
                       zonal_coefficients)
 from .surfaces import gather_surfaces, on_surfaces_host, surfaces_of_profiles
+from .stability import gather_stability, stability_host, stability_of_columns
 # (the submodule first, as for the averages: the name `particles` of the package is the function)
 from .particles import (Particles, ParticlesHost, advance_host, exchange_particles, particle_rates, particles, run_with_particles,
                         sample_host, seed_particles, seed_positions)

@@ -62,6 +62,7 @@ ABI_SYMBOLS = [
     "gb25_class_sum_bytes", "gb25_get_class_sums",
     "gb25_spectral_coefficient_bytes", "gb25_get_spectrum_table", "gb25_get_zonal_spectrum", "gb25_get_derived_zonal_spectrum",
     "gb25_compute_on_surfaces", "gb25_get_on_surfaces",
+    "gb25_stability_dims", "gb25_compute_stability", "gb25_get_stability", "gb25_get_stability_stats",
     "gb25_averages_info_bytes", "gb25_averages_begin", "gb25_averages_accumulate", "gb25_averages_get_info", "gb25_average_dims",
     "gb25_get_average", "gb25_average_device_ptr", "gb25_averages_end",
     "gb25_particles_info_bytes", "gb25_particles_begin", "gb25_particles_set", "gb25_particles_get", "gb25_particles_advance",
@@ -81,6 +82,9 @@ SURFACE_VARIABLES = {"T": 0, "S": 1, "potential_density": 2, "depth": 3}
 SURFACE_CARRIED = {"depth": 0, "T": 1, "S": 2, "e": 3, "kinetic_energy": 4, "density_anomaly": 5, "potential_density": 6}
 SURFACE_STATUS = {"found": 0, "outcrop": 1, "grounded": 2, "dry": 3}
 SURFACE_MAX_VALUES = 64
+# gb25_stability (include/gb25.h); the floor each takes as param when none is given (the Richardson number's 1e-12 s^-2 is a convention)
+STABILITY_IDS = {"n2": 0, "shear2": 1, "richardson": 2, "eady_rate": 3, "ertel_pv": 4, "wave_speed": 5}
+STABILITY_DEFAULT_PARAM = {"richardson": 1e-12}
 AVERAGE_GROUPS = {"means": 1, "squares": 2, "fluxes": 4}              # gb25_average_group
 # gb25_average: name -> id; the first six are the MEANS, the next five the SQUARES, the last six the FLUXES
 AVERAGE_IDS = {n: q for q, n in enumerate(["u", "v", "w", "T", "S", "eta", "uu", "vv", "TT", "SS", "etaeta",
@@ -402,6 +406,10 @@ def load_library(float_type="Float32"):
                                                     C.POINTER(C.c_int64)]
     lib.gb25_compute_on_surfaces.argtypes = [P, C.c_int, C.c_int, P, C.c_int32, C.POINTER(P), C.POINTER(P), C.POINTER(C.c_int32)]
     lib.gb25_get_on_surfaces.argtypes = [P, C.c_int, C.c_int, P, C.c_int32, P, P]
+    lib.gb25_stability_dims.argtypes = [P, C.c_int, C.POINTER(C.c_int32)]
+    lib.gb25_compute_stability.argtypes = [P, C.c_int, C.c_double, C.c_int32, C.c_int32, C.POINTER(P), C.POINTER(C.c_int32)]
+    lib.gb25_get_stability.argtypes = [P, C.c_int, C.c_double, C.c_int32, C.c_int32, P]
+    lib.gb25_get_stability_stats.argtypes = [P, C.c_int, C.c_double, C.POINTER(FieldStats)]
     lib.gb25_averages_begin.argtypes = [P, C.c_int32, C.c_int32, C.c_int32]
     lib.gb25_averages_accumulate.argtypes = [P, C.c_double]
     lib.gb25_averages_get_info.argtypes = [P, C.POINTER(AveragesInfo)]
@@ -716,6 +724,46 @@ class HipBackend:
         status = np.empty((args[3], Ny, Nx), dtype=np.uint8)
         self._call("gb25_get_on_surfaces", *args, out.ctypes.data_as(C.c_void_p), status.ctypes.data_as(C.c_void_p))
         return out.transpose(2, 1, 0), status.transpose(2, 1, 0)
+
+    # ---- stability diagnostics on the device (include/gb25.h: "stability diagnostics"; gb-25_amd/stability.py).  kind: "n2",
+    #      "shear2", "richardson", "eady_rate", "ertel_pv" at (c,c,f), "wave_speed" 2-D (or the ids of the header); param: the floor
+    #      of the Richardson number (on S2, > 0) or of the Eady rate (on N2, >= 0); levels = (k_first, k_count) of the Nz + 1
+    #      faces, 0-based, k_count = -1 or levels = None: all
+    def stability_dims(self, kind):
+        d = (C.c_int32 * 3)()
+        self._call("gb25_stability_dims", int(STABILITY_IDS.get(kind, kind)), d)
+        return tuple(d)
+
+    @staticmethod
+    def _stability_args(kind, param, levels):
+        if param is None:
+            param = STABILITY_DEFAULT_PARAM.get(kind, 0.0)
+        k_first, k_count = (0, -1) if levels is None else levels
+        return int(STABILITY_IDS.get(kind, kind)), float(param), int(k_first), int(k_count)
+
+    def compute_stability(self, kind, param=None, levels=None):
+        """(device pointer, dims) of the packed result, elements of this backend's dtype, i fastest; read-only, valid until
+        the next call on this model."""
+        p, d = C.c_void_p(), (C.c_int32 * 3)()
+        self._call("gb25_compute_stability", *self._stability_args(kind, param, levels), C.byref(p), d)
+        return p.value, tuple(d)
+
+    def get_stability(self, kind, param=None, levels=None):
+        """numpy array [i, j, face] of the requested faces (the wave speed: [i, j, 1]); only those are computed and copied."""
+        q, param, k_first, k_count = self._stability_args(kind, param, levels)
+        Nx, Ny, Nz = self.field_dims("T", False)
+        nf = 1 if q == STABILITY_IDS["wave_speed"] else Nz + 1
+        nk = nf - k_first if k_count == -1 else k_count
+        out = np.empty((max(nk, 0), Ny, Nx), dtype=self.dtype)
+        self._call("gb25_get_stability", q, param, k_first, k_count, out.ctypes.data_as(C.c_void_p))
+        return out.transpose(2, 1, 0)
+
+    def stability_stats(self, kind, param=None):
+        """gb25_get_stability_stats: gb25_field_stats of the whole diagnostic."""
+        out = FieldStats()
+        q, param, _, _ = self._stability_args(kind, param, None)
+        self._call("gb25_get_stability_stats", q, param, C.byref(out))
+        return out
 
     # ---- time averages accumulated on the device (include/gb25.h: "time averages and eddy fluxes"); names: AVERAGE_IDS
     def averages_begin(self, groups=("means", "squares", "fluxes"), levels=None):

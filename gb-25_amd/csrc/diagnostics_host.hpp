@@ -201,10 +201,11 @@ gb25_status moments_tables(gb25_model* m) {
   if (gb25_status s = diag_upload(m, zt, &D.zt)) return s;
   if (m->g.cv.on) {
     // of a curvilinear grid: the derived fields' AZFF, the integrals' areas by location, the transports' lengths of the y faces
-    // (DXCF) and of the x faces (DYFC)
+    // (DXCF) and of the x faces (DYFC), the stability diagnostics' Coriolis parameter at (f,f)
     const struct { int id; const char* name; real** dst; } metrics[] = {
         {GB25_M2_AZFF, "AZFF", &D.azff},    {GB25_M2_AZCC, "AZCC", &D.area[0]},        {GB25_M2_AZFC, "AZFC", &D.area[1]},
-        {GB25_M2_AZCF, "AZCF", &D.area[2]}, {GB25_M2_DXCF, "DXCF", &D.face_length[0]}, {GB25_M2_DYFC, "DYFC", &D.face_length[1]}};
+        {GB25_M2_AZCF, "AZCF", &D.area[2]}, {GB25_M2_DXCF, "DXCF", &D.face_length[0]}, {GB25_M2_DYFC, "DYFC", &D.face_length[1]},
+        {GB25_M2_FFF, "FFF", &D.fff}};
     for (const auto& c : metrics) {
       if (m->h_curv[c.id].size() != n2) return fail(m, GB25_ERR_STATE, "diagnostics: the curvilinear metric %s is not built", c.name);
       if (gb25_status s = diag_upload(m, m->h_curv[c.id], c.dst)) return s;
@@ -224,6 +225,14 @@ gb25_status moments_tables(gb25_model* m) {
       }
       if (gb25_status s = diag_upload(m, f, &D.first_wet[q])) return s;
     }
+    // the stability diagnostics' own: the (c,c) columns and the ring around them, [-1, Nx] x [-1, Ny]
+    std::fill(f.begin(), f.end(), MOMENTS_DRY);
+    for (int j = -1; j <= Ny; j++)
+      for (int i = -1; i <= Nx; i++) {
+        const int k = kb(i, j);
+        f[(size_t)(i + H) + (size_t)sx * (j + H)] = k < Nz ? (unsigned short)k : MOMENTS_DRY;
+      }
+    if (gb25_status s = diag_upload(m, f, &D.first_wet_ring)) return s;
   }
   D.tables_valid = true;
   return GB25_OK;

@@ -1,5 +1,5 @@
 // diagnostics_state.hpp -- every piece of memory and bookkeeping the read-only diagnostics own (diagnostics_host.hpp,
-// averages_host.hpp, classes_host.hpp, particles_host.hpp, spectrum_host.hpp, surfaces_host.hpp), as ONE member of gb25_model.
+// averages_host.hpp, classes_host.hpp, particles_host.hpp, spectrum_host.hpp, surfaces_host.hpp, stability_host.hpp), as ONE member of gb25_model.
 // Host only; included by gb25_api.hip behind the kernel headers (PartState: particle_kernels.hpp; SURF_MAX: surface_kernels.hpp;
 // GB25_A_COUNT and the info structs: include/gb25.h); like Field it is local to that translation unit, so the libraries export
 // nothing of it.
@@ -21,10 +21,14 @@ struct DiagState {
   size_t moments_rows = 0, moments_levels = 0;
   // diagnostics' own tables, made by the first call that needs them (moments_tables), dropped whenever the grid or the bottom
   // is rebuilt: by horizontal location the areas (curvilinear grids) and the first wet levels (grids with a bottom table); the
-  // derived fields' AZFF (curvilinear grids) and (double) zc | zf; the transports' DXCF and DYFC (curvilinear grids)
+  // derived fields' AZFF (curvilinear grids) and (double) zc | zf; the transports' DXCF and DYFC (curvilinear grids); the
+  // stability diagnostics' Coriolis parameter at (f,f) (curvilinear grids) and the first wet levels of the (c,c) columns WITH
+  // the ring of columns around the interior (grids with a bottom table)
   gb25::real* area[3] = {nullptr, nullptr, nullptr};
   unsigned short* first_wet[3] = {nullptr, nullptr, nullptr};
+  unsigned short* first_wet_ring = nullptr;
   gb25::real* azff = nullptr;
+  gb25::real* fff = nullptr;
   double* zt = nullptr;
   gb25::real* face_length[2] = {nullptr, nullptr};
   bool tables_valid = false;
@@ -58,6 +62,9 @@ struct DiagState {
   void* surfaces = nullptr;
   size_t surf_values = 0;
   double surf_targets[gb25::SURF_MAX] = {};
+  // stability diagnostics (gb25_compute_stability, gb25_get_stability): the packed result array, room for Nx x Ny x (Nz + 1)
+  // values, made by the first call
+  gb25::real* stability = nullptr;
   // time averages (gb25_averages_*): the accumulators of the active groups and the array a normalized read-out is divided into
   // -- ONE allocation (avg_acc[0] is its base: MEANS is always active), made by gb25_averages_begin, freed by gb25_averages_end
   // and gb25_destroy --, the window, the sample count and weight_sum (avg_info)
@@ -91,7 +98,9 @@ struct DiagState {
     for (auto& p : area) drop(p);
     for (auto& p : first_wet) drop(p);
     for (auto& p : face_length) drop(p);
+    drop(first_wet_ring);
     drop(azff);
+    drop(fff);
     drop(zt);
     drop(spec_table);
     tables_valid = spec_valid = false;
@@ -122,6 +131,7 @@ struct DiagState {
     drop(class_sums);
     drop(spectrum);
     drop(surfaces);
+    drop(stability);
     release_tables();
     release_averages();
     release_particles();

@@ -14,6 +14,7 @@
 #include "particle_kernels.hpp"
 #include "spectrum_kernels.hpp"
 #include "surface_kernels.hpp"
+#include "stability_kernels.hpp"
 #include "diagnostics_state.hpp"
 #include "validity.hpp"
 #include "step_route.hpp"
@@ -3703,3 +3704,4 @@ gb25_status gb25_profile_get(gb25_model* m, gb25_kernel k, int64_t* launches, do
 #include "particles_host.hpp"
 #include "spectrum_host.hpp"
 #include "surfaces_host.hpp"
+#include "stability_host.hpp"

@@ -264,6 +264,11 @@ class LocalSlabEnsemble:
         from .surfaces import gather_surfaces
         return gather_surfaces(self, variable, carried, values)
 
+    # stability diagnostics: every slab computes its own columns, the results are placed by global offset (gb-25_amd/stability.py)
+    def stability(self, kind, param=None, levels=None):
+        from .stability import gather_stability
+        return gather_stability(self, kind, param, levels)
+
     # time averages: likewise (gb-25_amd/averages.py); every slab accumulates its own interior, the read-out is placed by
     # global offset
     def averages_begin(self, groups=("means", "squares", "fluxes"), levels=None):

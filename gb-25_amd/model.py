@@ -295,6 +295,64 @@ def layer_thickness(model, variable, edges):
     return thickness(isosurface_depth(model, variable, edges)[0])
 
 
+def _stability(model, kind, param, levels, host):
+    from .stability import stability                 # (the kernel, or the numpy restatement on a backend without it)
+    return stability(model.backend, kind, param, levels, **host)
+
+
+def buoyancy_frequency(model, levels=None, **host):
+    """N^2 [s^-2] at (Center, Center, Face), [i, j, face] with Nz + 1 faces, on the device (include/gb25.h, GB25_ST_N2): the
+    stratification of the potential density referenced to the surface, -(g / rho0) d sigma / dz between two cell centres.  Faces
+    0 and Nz and every face at or below the bottom are 0.  levels = (k_first, k_count) of the faces, 0-based (k_count = -1: all
+    from k_first on); only those are computed and copied.  host: sigma = ... for a backend without the kernel and without
+    get_derived (stability.stability_host)."""
+    return _stability(model, "n2", None, levels, host)
+
+
+def shear_squared(model, levels=None, **host):
+    """The squared vertical shear (du/dz)^2 + (dv/dz)^2 [s^-2] of the velocities averaged to the cell centres, at (c,c,f)."""
+    return _stability(model, "shear2", None, levels, host)
+
+
+def richardson_number(model, shear_floor=1e-12, levels=None, **host):
+    """Ri = N^2 / max(S^2, shear_floor) at (c,c,f).  shear_floor [s^-2] > 0 keeps a resting column finite; its default is a
+    convention, not a measured number."""
+    return _stability(model, "richardson", shear_floor, levels, host)
+
+
+def eady_growth_rate(model, n2_floor=0.0, levels=None, **host):
+    """The Eady growth rate 0.31 |f| / sqrt(Ri) = 0.31 |f| sqrt(S^2) / sqrt(N^2) [s^-1] at (c,c,f) where N^2 > n2_floor, 0
+    elsewhere: how fast the baroclinic instability grows."""
+    return _stability(model, "eady_rate", n2_floor, levels, host)
+
+
+def ertel_pv(model, levels=None, **host):
+    """The Ertel potential vorticity (f + zeta) N^2 + (du/dz db/dy - dv/dz db/dx) [s^-3] at (c,c,f); host: sigma = ...,
+    vorticity = ... for a backend without the kernel."""
+    return _stability(model, "ertel_pv", None, levels, host)
+
+
+def baroclinic_wave_speed(model, **host):
+    """The first baroclinic gravity-wave speed c1 = (1 / pi) integral of N dz [m/s] (WKB), [i, j]; 0 over land."""
+    return _stability(model, "wave_speed", None, None, host)[:, :, 0]
+
+
+def deformation_radius(model, **host):
+    """The first baroclinic deformation radius [m], [i, j]: c1 / |f| poleward of 5 degrees, sqrt(c1 / (2 beta)) within 5 degrees
+    of the equator, beta = 2 Omega cos(phi) / R, from baroclinic_wave_speed and the latitude of the cell centres.  An
+    element-wise step in float64 on the HOST: it is not part of the bit-for-bit contract of the device diagnostics."""
+    from .stability import cell_latitudes, deformation_radius_of
+    b = model.backend
+    return deformation_radius_of(baroclinic_wave_speed(model, **host), cell_latitudes(b), b.cfg.Omega, b.cfg.radius)
+
+
+def eddy_resolution(model, **host):
+    """deformation_radius / max(dx, dy) of every cell, [i, j]: the grid resolves the eddies where this is about 2 or more.
+    Host arithmetic like deformation_radius."""
+    from .stability import cell_spacings
+    return deformation_radius(model, **host) / cell_spacings(model.backend)
+
+
 def _transport(model, faces, shape, window=None):
     b = model.backend
     if hasattr(b, "transport"):

@@ -818,6 +818,63 @@ gb25_status gb25_compute_on_surfaces(gb25_model *m, gb25_surface_variable v, gb2
 gb25_status gb25_get_on_surfaces(gb25_model *m, gb25_surface_variable v, gb25_surface_carried c, const double *values, int32_t n,
                                  void *host, uint8_t *host_status /* may be NULL */);
 
+/* ---- stability diagnostics on the device (csrc/stability_kernels.hpp, k_stability_faces / k_stability_wave_speed): what the flow
+ *      is about to do -- the stratification N^2, the squared vertical shear, the Richardson number, the Eady growth rate
+ *      0.31 |f| / sqrt(Ri), the Ertel potential vorticity, and the first baroclinic gravity-wave speed, which gives the deformation
+ *      radius and so tells whether the grid resolves the instability -- without T, S, u and v of whole columns crossing PCIe for an
+ *      equation of state on the host.  Same contract as the derived fields and the fields on surfaces: the state gb25_get_field
+ *      would return, READ-ONLY for the schedule (nothing pinned, every look-ahead alive, a stale GB25_PHY neither needed nor
+ *      touched), LOCAL on a rank (a rank's interior; gather by global_offset: gb-25_amd/stability.py gather_stability), bitwise
+ *      repeatable, no floating-point atomics, launches under GB25_K_DIAGNOSTICS on the model's stream.
+ *
+ *      DEFINITIONS.  Values are read from the parent arrays as gb25_get_field(f, host, 1) returns them at that moment, halo cells
+ *      included; metrics are the numbers gb25_get_metric / gb25_get_metric2 return.  Every operation in fp64 on (double) of the
+ *      stored values, in the written order, IEEE divisions and square roots, NO fused multiply-adds, the result rounded once to
+ *      the float type -- gb-25_amd/stability.py restates them with numpy bit for bit.  Indices below are 1-based interior; i-1,
+ *      j-1, i+1, j+1 reach one halo column or row.
+ *        sigma(i,j,k)  (double) of the value gb25_get_derived(GB25_D_POTENTIAL_DENSITY) hands out in a wet cell: rounded to the float
+ *            type first, the same bits; evaluated on the fly by the same device function, in the halo column and row too.
+ *        b = -(g / rho0) * sigma, g and rho0 of gb25_config; the quotient g / rho0 is formed once.  This is stratification
+ *            referenced to the SURFACE: it is not the locally referenced N^2 that CATKE forms from alpha and beta at the face.
+ *        Face k lies between the cells k-1 and k; dz = zc(k) - zc(k-1), zc = GB25_M_ZC.
+ *        GB25_ST_N2          N2 = (-(g / rho0) * (sigma(k) - sigma(k-1))) / dz
+ *        GB25_ST_SHEAR2      ub(k) = 0.5 * (u(i) + u(i+1)), vb(k) = 0.5 * (v(j) + v(j+1)) -- v(j+1) as stored, be it a wall's, the
+ *            fold's or a halo row --; du = (ub(k) - ub(k-1)) / dz, dv = (vb(k) - vb(k-1)) / dz; S2 = du * du + dv * dv
+ *        GB25_ST_RICHARDSON  Ri = N2 / (S2 > param ? S2 : param).  param: a floor on S2 in s^-2, > 0 (the Python layer's default
+ *            1e-12 is a convention, not a measured number)
+ *        GB25_ST_EADY_RATE   N2 > param ? ((0.31 * |fc|) * sqrt(S2)) / sqrt(N2) : 0.  param: a floor on N2 in s^-2, >= 0.
+ *            fc = 0.25 * ((f(i,j) + f(i+1,j)) + (f(i,j+1) + f(i+1,j+1))), f = GB25_M2_FFF; on the LatitudeLongitudeGrid the same
+ *            expression with f(.,j) = GB25_M_FCOR(j)
+ *        GB25_ST_ERTEL_PV    q = (fc + zb) * N2 + (du * by - dv * bx)
+ *            zb = 0.125 * (Z(k-1) + Z(k)), Z(l) = (z(i,j,l) + z(i+1,j,l)) + (z(i,j+1,l) + z(i+1,j+1,l)), z = (double) of
+ *                GB25_D_VORTICITY as rounded to the float type (its expression, evaluated at the four corners of the cell)
+ *            bx = 0.25 * ((gx(i,k-1) + gx(i+1,k-1)) + (gx(i,k) + gx(i+1,k))), gx(i,l) = (b(i,j,l) - b(i-1,j,l)) / dx(i),
+ *                dx = DXFC(i,j) on the grids with 2-D metrics, GB25_M_DXC(j) on the LatitudeLongitudeGrid; gx = 0 when either
+ *                cell is immersed (l < kbot of it)
+ *            by = 0.25 * ((gy(j,k-1) + gy(j+1,k-1)) + (gy(j,k) + gy(j+1,k))), gy(j,l) = (b(i,j,l) - b(i,j-1,l)) / dy(j),
+ *                dy = DYCF(i,j), GB25_M_DY on the LatitudeLongitudeGrid; gy = 0 when either cell is immersed and across the
+ *                southern and the northern edge of the GLOBAL grid -- a wall, or the fold, beyond which no bottom is tabulated
+ *        GB25_ST_WAVE_SPEED  c1 = (sum over the wet interior faces k, bottom to top, of sqrt(N2(k) > 0 ? N2(k) : 0) * dz(k))
+ *            / 3.141592653589793 -- the WKB speed of the first baroclinic mode; the one division comes last.  2-D, (c,c).
+ *      A value that is not finite yields what this arithmetic yields; there is no masking beyond the following.
+ *
+ *      LOCATIONS, FACES AND MASKING.  The first five live at (Center, Center, Face): Nx x Ny x (Nz + 1).  k_first, k_count select
+ *      faces, 0-based; k_count = -1: all from k_first on; only the requested faces are computed and copied.  The wave speed
+ *      takes 0, 1 or 0, -1.  Faces 0 and Nz are 0.  In a column whose first wet cell is kb (= kbot), every face k <= kb is 0; a dry
+ *      column is 0 throughout, its wave speed too.
+ *      gb25_compute_stability: into an array the model owns (made by the first call, Nx x Ny x (Nz + 1) values, freed by
+ *      gb25_destroy); *dev: elements of the library's float type, PACKED, device_dims = Nx, Ny, the faces of the window, i fastest;
+ *      read-only, complete when the call returns, valid until the next call on m.  gb25_get_stability: the same and one
+ *      device-to-host copy of exactly those elements.  gb25_get_stability_stats: gb25_field_stats of the whole diagnostic,
+ *      positions relative to its box. */
+typedef enum { GB25_ST_N2 = 0, GB25_ST_SHEAR2, GB25_ST_RICHARDSON, GB25_ST_EADY_RATE,
+               GB25_ST_ERTEL_PV, GB25_ST_WAVE_SPEED, GB25_ST_COUNT } gb25_stability;
+gb25_status gb25_stability_dims(const gb25_model *m, gb25_stability q, int32_t dims[3]);   /* needs no device */
+gb25_status gb25_compute_stability(gb25_model *m, gb25_stability q, double param, int32_t k_first, int32_t k_count,
+                                   const void **dev, int32_t device_dims[3]);
+gb25_status gb25_get_stability(gb25_model *m, gb25_stability q, double param, int32_t k_first, int32_t k_count, void *host);
+gb25_status gb25_get_stability_stats(gb25_model *m, gb25_stability q, double param, gb25_field_stats *out);
+
 /* ---- time averages and eddy fluxes accumulated on the device (csrc/averages_kernels.hpp, k_averages_accumulate): what the other
  *      diagnostics cannot do -- remember something between two calls.  The time-mean state, eddy kinetic energy and tracer
  *      variance, the eddy heat and salt fluxes <v'T'>, <u'T'>, <w'T'>: Oceananigans' AveragedTimeInterval, without five parent arrays

@@ -21,6 +21,7 @@ export Config, Model, create, destroy!, first_time_step!, time_step!, loop!, ini
        Moments, Budget, integrate_field, budget, SUM_ROWS, SUM_LEVELS, SUM_TOTAL,
        Transport, transport, overturning, ACROSS_Y, ACROSS_X, TR_LINES, TR_PROFILE, TR_STREAMFUNCTION,
        DERIVED, derived_dims, compute_derived, get_derived, derived_stats, field_levels,
+       STABILITY, stability_dims, compute_stability, get_stability, stability_stats,
        AVG_MEANS, AVG_SQUARES, AVG_FLUXES, AVERAGE, AveragesInfo, averages_begin, averages_accumulate, averages_info, average_dims,
        get_average, averages_end
 
@@ -448,6 +449,41 @@ function derived_stats(m::Model, d::Integer; param::Real = 0.0)
     out = Ref{FieldStats}()
     check(m, ccall((:gb25_get_derived_stats, m.lib), Cint, (Ptr{Cvoid}, Cint, Float64, Ref{FieldStats}), m.ptr, d, param, out),
           "gb25_get_derived_stats")
+    return out[]
+end
+# ---- stability diagnostics on the device (gb25_stability_dims / gb25_compute_stability / gb25_get_stability /
+#      gb25_get_stability_stats): definitions in include/gb25.h.  k_first counts FACES, 0-based like the ABI; k_count = -1: all from
+#      k_first on.  param: the floor of the Richardson number (on S2, > 0) or of the Eady rate (on N2, >= 0).
+const STABILITY = (n2 = Cint(0), shear2 = Cint(1), richardson = Cint(2), eady_rate = Cint(3), ertel_pv = Cint(4),
+                   wave_speed = Cint(5))
+"extents of a stability diagnostic: (Nx, Ny, Nz + 1), the wave speed (Nx, Ny, 1)"
+function stability_dims(m::Model, q::Integer)
+    out = zeros(Int32, 3)
+    check(m, ccall((:gb25_stability_dims, m.lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Int32}), m.ptr, q, out), "gb25_stability_dims")
+    return Tuple(Int.(out))
+end
+"(device pointer, dims) of the packed result; read-only, valid until the next call on m"
+function compute_stability(m::Model{FT}, q::Integer; param::Real = (q == STABILITY.richardson ? 1e-12 : 0.0), k_first::Integer = 0,
+                           k_count::Integer = -1) where {FT}
+    p, dims = Ref{Ptr{Cvoid}}(C_NULL), zeros(Int32, 3)
+    check(m, ccall((:gb25_compute_stability, m.lib), Cint, (Ptr{Cvoid}, Cint, Float64, Int32, Int32, Ref{Ptr{Cvoid}}, Ptr{Int32}),
+                   m.ptr, q, param, k_first, k_count, p, dims), "gb25_compute_stability")
+    return Ptr{FT}(p[]), Tuple(Int.(dims))
+end
+"a stability diagnostic's requested faces as an Array{FT, 3}; only those faces are computed and copied"
+function get_stability(m::Model{FT}, q::Integer; param::Real = (q == STABILITY.richardson ? 1e-12 : 0.0), k_first::Integer = 0,
+                       k_count::Integer = -1) where {FT}
+    nx, ny, nf = stability_dims(m, q)
+    out = Array{FT}(undef, nx, ny, k_count == -1 ? nf - k_first : k_count)
+    check(m, ccall((:gb25_get_stability, m.lib), Cint, (Ptr{Cvoid}, Cint, Float64, Int32, Int32, Ptr{Cvoid}),
+                   m.ptr, q, param, k_first, k_count, out), "gb25_get_stability")
+    return out
+end
+function stability_stats(m::Model, q::Integer; param::Real = (q == STABILITY.richardson ? 1e-12 : 0.0))
+    check_diagnostic_structs(m)
+    out = Ref{FieldStats}()
+    check(m, ccall((:gb25_get_stability_stats, m.lib), Cint, (Ptr{Cvoid}, Cint, Float64, Ref{FieldStats}), m.ptr, q, param, out),
+          "gb25_get_stability_stats")
     return out[]
 end
 "interior levels of an ordinary field, gathered on the device: field_levels(m, FIELD.T, Nz - 1, 1) is interior(T)[:, :, Nz:Nz]"

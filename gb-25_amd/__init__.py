@@ -16,6 +16,7 @@ from .model import (CATKEVerticalDiffusivity, default_ocean_closure, Field, Hydr
                     at_depths, isosurface_depth, layer_thickness, on_isosurface,
                     baroclinic_wave_speed, buoyancy_frequency, deformation_radius, eady_growth_rate, eddy_resolution, ertel_pv,
                     richardson_number, shear_squared,
+                    coarsen, column_integral, depth_mean, heat_content, subgrid_variance,
                     heat_transport, meridional_transport, overturning, section_transport,
                     overturning_in_classes, water_mass_census, zonal_power_spectrum, zonal_spectrum,
                     Averages, averages, run_averaged,
@@ -34,6 +35,7 @@ from .spectra import (combine_spectra, cospectrum, dominant_wavenumber, host_tab
                       zonal_coefficients)
 from .surfaces import gather_surfaces, on_surfaces_host, surfaces_of_profiles
 from .stability import gather_stability, stability_host, stability_of_columns
+from .blocks import BlockSums, block_sums_host, depth_weights, gather_blocks, sums_of_blocks
 # (the submodule first, as for the averages: the name `particles` of the package is the function)
 from .particles import (Particles, ParticlesHost, advance_host, exchange_particles, particle_rates, particles, run_with_particles,
                         sample_host, seed_particles, seed_positions)

@@ -63,6 +63,8 @@ ABI_SYMBOLS = [
     "gb25_spectral_coefficient_bytes", "gb25_get_spectrum_table", "gb25_get_zonal_spectrum", "gb25_get_derived_zonal_spectrum",
     "gb25_compute_on_surfaces", "gb25_get_on_surfaces",
     "gb25_stability_dims", "gb25_compute_stability", "gb25_get_stability", "gb25_get_stability_stats",
+    "gb25_block_info_bytes", "gb25_block_dims", "gb25_derived_block_dims", "gb25_get_block_sums", "gb25_compute_block_sums",
+    "gb25_get_derived_block_sums",
     "gb25_averages_info_bytes", "gb25_averages_begin", "gb25_averages_accumulate", "gb25_averages_get_info", "gb25_average_dims",
     "gb25_get_average", "gb25_average_device_ptr", "gb25_averages_end",
     "gb25_particles_info_bytes", "gb25_particles_begin", "gb25_particles_set", "gb25_particles_get", "gb25_particles_advance",
@@ -192,6 +194,19 @@ class Moments(_Record):
 
 MOMENTS_DTYPE = np.dtype([("measure", np.float64), ("first", np.float64), ("second", np.float64),
                           ("points", np.int64), ("nonfinite", np.int64)])
+
+
+class Blocks(C.Structure):
+    """gb25_blocks (include/gb25.h): the extents of a block and the window of levels."""
+    _fields_ = [("bx", C.c_int32), ("by", C.c_int32), ("bz", C.c_int32), ("k_first", C.c_int32), ("k_count", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class BlockInfo(_Record):
+    """gb25_block_info (include/gb25.h): the result's dims, the counted and the skipped points of all blocks, the blocks whose
+    measure is 0, the global offset of the rank's fine interior."""
+    _fields_ = [("dims", C.c_int32 * 3), ("reserved", C.c_int32), ("points", C.c_int64), ("nonfinite", C.c_int64),
+                ("empty_blocks", C.c_int64), ("global_offset", C.c_int32 * 3), ("reserved2", C.c_int32)]
 
 
 class Transport(_Record):
@@ -410,6 +425,11 @@ def load_library(float_type="Float32"):
     lib.gb25_compute_stability.argtypes = [P, C.c_int, C.c_double, C.c_int32, C.c_int32, C.POINTER(P), C.POINTER(C.c_int32)]
     lib.gb25_get_stability.argtypes = [P, C.c_int, C.c_double, C.c_int32, C.c_int32, P]
     lib.gb25_get_stability_stats.argtypes = [P, C.c_int, C.c_double, C.POINTER(FieldStats)]
+    lib.gb25_block_dims.argtypes = [P, C.c_int, C.POINTER(Blocks), C.POINTER(C.c_int32)]
+    lib.gb25_derived_block_dims.argtypes = [P, C.c_int, C.POINTER(Blocks), C.POINTER(C.c_int32)]
+    lib.gb25_get_block_sums.argtypes = [P, C.c_int, C.POINTER(Blocks), P, P, P, P, C.POINTER(BlockInfo)]
+    lib.gb25_compute_block_sums.argtypes = [P, C.c_int, C.POINTER(Blocks), P, C.POINTER(BlockInfo), C.POINTER(P), C.POINTER(C.c_int32)]
+    lib.gb25_get_derived_block_sums.argtypes = [P, C.c_int, C.c_double, C.POINTER(Blocks), P, P, P, P, C.POINTER(BlockInfo)]
     lib.gb25_averages_begin.argtypes = [P, C.c_int32, C.c_int32, C.c_int32]
     lib.gb25_averages_accumulate.argtypes = [P, C.c_double]
     lib.gb25_averages_get_info.argtypes = [P, C.POINTER(AveragesInfo)]
@@ -445,7 +465,8 @@ def load_library(float_type="Float32"):
                        ("gb25_state_monitor_bytes", StateMonitor), ("gb25_moments_bytes", Moments),
                        ("gb25_budget_bytes", Budget), ("gb25_transport_bytes", Transport),
                        ("gb25_class_sum_bytes", ClassSum), ("gb25_spectral_coefficient_bytes", SpectralCoefficient),
-                       ("gb25_averages_info_bytes", AveragesInfo), ("gb25_particles_info_bytes", ParticlesInfo)):
+                       ("gb25_averages_info_bytes", AveragesInfo), ("gb25_particles_info_bytes", ParticlesInfo),
+                       ("gb25_block_info_bytes", BlockInfo)):
         getattr(lib, fn).restype = C.c_int32
         if getattr(lib, fn)() != C.sizeof(struct):
             raise GB25Error(f"{path}: {fn}() = {getattr(lib, fn)()} there, {C.sizeof(struct)} bytes in this binding: "
@@ -764,6 +785,72 @@ class HipBackend:
         q, param, _, _ = self._stability_args(kind, param, None)
         self._call("gb25_get_stability_stats", q, param, C.byref(out))
         return out
+
+    # ---- block sums on the device (include/gb25.h: "block sums"; gb-25_amd/blocks.py).  source: a field name or a derived name at
+    #      (c,c) ("kinetic_energy", "density_anomaly", "potential_density", "mixed_layer_depth" with param = the threshold);
+    #      block = (bx, by, bz); levels = (k_first, k_count) of the field's own levels, k_count = -1 or levels = None: all;
+    #      level_weights: one float64 per level of the field, or None
+    @staticmethod
+    def _block_args(block, levels, level_weights):
+        k_first, k_count = (0, -1) if levels is None else levels
+        bx, by, bz = block
+        blocks = Blocks(int(bx), int(by), int(bz), int(k_first), int(k_count), 0)
+        lw = None if level_weights is None else np.ascontiguousarray(level_weights, np.float64).reshape(-1)
+        return blocks, lw
+
+    def _block_levels(self, source):
+        if source in DERIVED_IDS:
+            return self.derived_dims(source)[2]
+        if source not in FIELD_IDS:
+            raise GB25Error(f"block sums: no field and no derived field {source!r}")
+        return self.field_dims(source, False)[2]
+
+    def _checked_weights(self, source, lw):
+        # (the library reads one weight per level of the field: a vector of another length never reaches it)
+        if lw is not None and lw.size != self._block_levels(source) and self._block_levels(source) > 1:
+            raise GB25Error(f"block sums: level_weight has {lw.size} entries, {source!r} has {self._block_levels(source)} levels")
+        return None if lw is None else lw.ctypes.data_as(C.c_void_p)
+
+    def block_dims(self, source, block, levels=None):
+        """gb25_block_dims / gb25_derived_block_dims: (Nx / bx, Ny / by, k_count / bz) after the checks of the blocks and the
+        window.  Needs no device."""
+        blocks, _ = self._block_args(block, levels, None)
+        d = (C.c_int32 * 3)()
+        if source in DERIVED_IDS:
+            self._call("gb25_derived_block_dims", DERIVED_IDS[source], C.byref(blocks), d)
+        else:
+            self._block_levels(source)
+            self._call("gb25_block_dims", FIELD_IDS[source], C.byref(blocks), d)
+        return tuple(d)
+
+    def block_sums(self, source, block, levels=None, level_weights=None, param=None, planes=("measure", "first", "second")):
+        """gb25_get_block_sums / gb25_get_derived_block_sums: blocks.BlockSums with the planes asked for, [I, J, K] float64 each
+        (the others None; only those are copied), and the info record."""
+        from .blocks import BlockSums
+        blocks, lw = self._block_args(block, levels, level_weights)
+        dims = self.block_dims(source, block, levels)
+        out = {n: (np.empty(dims[::-1], np.float64) if n in planes else None) for n in ("measure", "first", "second")}
+        ptrs = [None if a is None else a.ctypes.data_as(C.c_void_p) for a in out.values()]
+        info = BlockInfo()
+        w = self._checked_weights(source, lw)
+        if source in DERIVED_IDS:
+            q, param, _, _ = self._derived_args(source, param, None)
+            self._call("gb25_get_derived_block_sums", q, param, C.byref(blocks), w, *ptrs, C.byref(info))
+        else:
+            self._call("gb25_get_block_sums", FIELD_IDS[source], C.byref(blocks), w, *ptrs, C.byref(info))
+        m, t, s = (None if a is None else a.transpose(2, 1, 0) for a in out.values())
+        return BlockSums(m, t, s, block=block, dims=tuple(info.dims), points=info.points, nonfinite=info.nonfinite,
+                         empty_blocks=info.empty_blocks, global_offset=tuple(info.global_offset))
+
+    def compute_block_sums(self, field, block, levels=None, level_weights=None):
+        """(device pointer, dims, BlockInfo): the planes measure | first | second one after another, dims[0] dims[1] dims[2]
+        doubles each, I fastest; read-only, valid until the next call on this model."""
+        blocks, lw = self._block_args(block, levels, level_weights)
+        self._block_levels(field)
+        p, d, info = C.c_void_p(), (C.c_int32 * 3)(), BlockInfo()
+        self._call("gb25_compute_block_sums", FIELD_IDS[field], C.byref(blocks), self._checked_weights(field, lw), C.byref(info),
+                   C.byref(p), d)
+        return p.value, tuple(d), info
 
     # ---- time averages accumulated on the device (include/gb25.h: "time averages and eddy fluxes"); names: AVERAGE_IDS
     def averages_begin(self, groups=("means", "squares", "fluxes"), levels=None):

@@ -1,5 +1,5 @@
 // diagnostics_state.hpp -- every piece of memory and bookkeeping the read-only diagnostics own (diagnostics_host.hpp,
-// averages_host.hpp, classes_host.hpp, particles_host.hpp, spectrum_host.hpp, surfaces_host.hpp, stability_host.hpp), as ONE member of gb25_model.
+// averages_host.hpp, classes_host.hpp, particles_host.hpp, spectrum_host.hpp, surfaces_host.hpp, stability_host.hpp, blocks_host.hpp), as ONE member of gb25_model.
 // Host only; included by gb25_api.hip behind the kernel headers (PartState: particle_kernels.hpp; SURF_MAX: surface_kernels.hpp;
 // GB25_A_COUNT and the info structs: include/gb25.h); like Field it is local to that translation unit, so the libraries export
 // nothing of it.
@@ -7,6 +7,7 @@
 // serve gb25_averages_end and gb25_particles_end; invalidate_tables() is what a rebuild of the grid or of the bottom calls.
 #pragma once
 #include <cstring>
+#include <vector>
 
 namespace {
 
@@ -65,6 +66,14 @@ struct DiagState {
   // stability diagnostics (gb25_compute_stability, gb25_get_stability): the packed result array, room for Nx x Ny x (Nz + 1)
   // values, made by the first call
   gb25::real* stability = nullptr;
+  // block sums (gb25_get_block_sums, gb25_compute_block_sums, gb25_get_derived_block_sums): ONE allocation -- the three counts of
+  // the info record (BlockCounts, padded to 32 bytes), the level weights (Nz + 1 doubles), the planes measure | first | second
+  // of one call, then the count slots of the waves of its launch --, made by the first call, made anew when a call needs more
+  // bytes.  The host copy of the weights the upload reads (a word of the model: no copy is ever pending from a frame that has
+  // returned)
+  void* blocks = nullptr;
+  size_t block_bytes = 0;
+  std::vector<double> block_weights;
   // time averages (gb25_averages_*): the accumulators of the active groups and the array a normalized read-out is divided into
   // -- ONE allocation (avg_acc[0] is its base: MEANS is always active), made by gb25_averages_begin, freed by gb25_averages_end
   // and gb25_destroy --, the window, the sample count and weight_sum (avg_info)
@@ -132,6 +141,8 @@ struct DiagState {
     drop(spectrum);
     drop(surfaces);
     drop(stability);
+    drop(blocks);
+    block_bytes = 0;
     release_tables();
     release_averages();
     release_particles();

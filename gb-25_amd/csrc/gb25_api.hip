@@ -15,6 +15,7 @@
 #include "spectrum_kernels.hpp"
 #include "surface_kernels.hpp"
 #include "stability_kernels.hpp"
+#include "block_kernels.hpp"
 #include "diagnostics_state.hpp"
 #include "validity.hpp"
 #include "step_route.hpp"
@@ -3705,3 +3706,4 @@ gb25_status gb25_profile_get(gb25_model* m, gb25_kernel k, int64_t* launches, do
 #include "spectrum_host.hpp"
 #include "surfaces_host.hpp"
 #include "stability_host.hpp"
+#include "blocks_host.hpp"

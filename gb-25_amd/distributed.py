@@ -269,6 +269,12 @@ class LocalSlabEnsemble:
         from .stability import gather_stability
         return gather_stability(self, kind, param, levels)
 
+    # block sums: every slab reduces its own blocks -- a block that does not divide a slab's extents is that slab's error --, the
+    # planes are placed by global offset (gb-25_amd/blocks.py)
+    def block_sums(self, source, block, levels=None, level_weights=None, param=None):
+        from .blocks import block_sums, gather_blocks
+        return gather_blocks([block_sums(b, source, block, levels, level_weights, param) for b in self.backends])
+
     # time averages: likewise (gb-25_amd/averages.py); every slab accumulates its own interior, the read-out is placed by
     # global offset
     def averages_begin(self, groups=("means", "squares", "fluxes"), levels=None):

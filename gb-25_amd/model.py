@@ -75,6 +75,11 @@ class Field:
         positive] between cell centres, on the device (at_depths of this module)."""
         return _on_surfaces(self._b, "depth", self.name, depths)
 
+    def coarsen(self, block):
+        """The measure-weighted mean over boxes of block = (bx, by, bz) points, [I, J, K], reduced on the device (coarsen of
+        this module)."""
+        return _block_sums(self._b, self.name, block).mean()
+
     def zonal_spectrum(self, wavenumbers=None, levels=None):
         """(X [level, row, m] complex128, nonfinite_lines): the zonal wavenumber coefficients of every interior line, computed
         where the field lives (zonal_spectrum of this module)."""
@@ -351,6 +356,54 @@ def eddy_resolution(model, **host):
     Host arithmetic like deformation_radius."""
     from .stability import cell_spacings
     return deformation_radius(model, **host) / cell_spacings(model.backend)
+
+
+def _block_sums(b, source, block, levels=None, level_weights=None, param=None):
+    from .blocks import block_sums                    # (the kernel, or the numpy restatement on a backend without it)
+    return block_sums(b, source, block, levels, level_weights, param)
+
+
+def coarsen(model, source, block, levels=None):
+    """The measure-weighted mean of `source` -- a field name or "kinetic_energy", "density_anomaly", "potential_density",
+    "mixed_layer_depth" -- over boxes of block = (bx, by, bz) points, [I, J, K] float64, reduced on the device (include/gb25.h,
+    gb25_get_block_sums): the field on a 4x or 8x coarser grid, NaN where a box is all land.  levels = (k_first, k_count) of the
+    field's own levels."""
+    return _block_sums(model.backend, source, block, levels).mean()
+
+
+def subgrid_variance(model, source, block):
+    """The variance of `source` inside every box of block = (bx, by, bz) points, measure-weighted, [I, J, K]: what a coarser
+    grid would not resolve."""
+    return _block_sums(model.backend, source, block).variance()
+
+
+def _column(model, source, depth_range):
+    from .blocks import column_area, column_sums
+    return column_sums(model.backend, source, depth_range), column_area(model.backend, source)
+
+
+def column_integral(model, source, depth_range=None):
+    """The vertical integral of `source` over the wet part of every column, [i, j] in units of the source times metres -- the
+    column's sum of mu x over the column's area, Oceananigans' Integral(field, dims = 3) --, on the device.  depth_range = (top,
+    bottom) [m, positive] restricts it, partial cells by their fraction (blocks.depth_weights); 0 over land."""
+    sums, area = _column(model, source, depth_range)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(area > 0, sums.first[:, :, 0] / area, 0.0)
+
+
+def depth_mean(model, source, depth_range=None):
+    """The thickness-weighted mean of `source` over the wet part of every column, [i, j]; NaN where the column (or the range in
+    it) is dry."""
+    return _column(model, source, depth_range)[0].mean()[:, :, 0]
+
+
+def heat_content(model, depth_range=None, heat_capacity=3991.86795711963, reference_temperature=0.0):
+    """The heat content of every column [J m^-2], rho0 cp times the vertical integral of T - reference_temperature, [i, j]:
+    `heat_content(model, depth_range=(0, 700))` is the heat content of the upper 700 m.  0 over land."""
+    sums, area = _column(model, "T", depth_range)
+    first = sums.first[:, :, 0] - reference_temperature * sums.measure[:, :, 0]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(area > 0, (model.backend.cfg.rho0 * heat_capacity) * first / area, 0.0)
 
 
 def _transport(model, faces, shape, window=None):

@@ -875,6 +875,68 @@ gb25_status gb25_compute_stability(gb25_model *m, gb25_stability q, double param
 gb25_status gb25_get_stability(gb25_model *m, gb25_stability q, double param, int32_t k_first, int32_t k_count, void *host);
 gb25_status gb25_get_stability_stats(gb25_model *m, gb25_stability q, double param, gb25_field_stats *out);
 
+/* ---- block sums on the device (csrc/block_kernels.hpp, k_block_sums): the one reduction of the family that gb25_integrate_field
+ *      (rows, levels, the total) does not have -- a MAP.  The interior of a field, or of a derived field, is cut into boxes of
+ *      bx x by x bz points and every box gets measure = sum mu', first = sum mu' x, second = sum mu' x^2 in fp64: block means on a
+ *      4x or 8x coarser grid for an output writer, the sub-grid variance, column integrals, the heat content of the upper 700 m --
+ *      Oceananigans' Integral(field, dims = 3) and Average over boxes of cells -- without the parent array crossing PCIe.  Same
+ *      contract as every diagnostic here: the state gb25_get_field would return (a stale GB25_PHY recomputed, previous velocities
+ *      read where they live), READ-ONLY for the schedule (nothing pinned, every look-ahead alive), LOCAL on a rank (gather by
+ *      global_offset: gb-25_amd/blocks.py gather_blocks), bitwise repeatable, no floating-point atomics, launches under
+ *      GB25_K_DIAGNOSTICS on the model's stream.
+ *
+ *      BLOCKS (gb25_blocks).  bx divides the rank's interior Nx, 1 <= bx <= 256 (whole rows are what GB25_SUM_ROWS is for).  by
+ *      divides the rank's Ny, the rows of cell centres: the extra wall row Ny of a (c,f) field lies in no block (its measure is
+ *      0).  k_first, k_count select levels as in gb25_get_derived (k_count = -1: all from k_first on) in the field's OWN level
+ *      count -- Nz + 1 for w and the kappas --; bz divides the resolved k_count.  A 2-D field takes bz = 1 and levels 0, 1 or
+ *      0, -1.  The result has dims (Nx / bx, Ny / by, k_count / bz), I fastest.
+ *      mu is THE MEASURE of gb25_integrate_field above, by the field's location: the same expression from the same tables.
+ *      LEVEL WEIGHTS.  level_weight (may be NULL): one double per level of the FIELD (not of the window), finite and >= 0;
+ *      mu' = mu * level_weight[k], one fp64 multiply.  With NULL mu' = mu and no multiply is made.  A fraction per level says
+ *      "0 to 700 m" with partial cells.  A 2-D field refuses a non-NULL vector.
+ *      COUNTING.  A point counts iff mu' > 0 and x = (double) of the stored value is finite.  A point with mu' > 0 whose x is
+ *      not finite is skipped and counted in nonfinite.  A value in an immersed cell is invisible.
+ *      TERMS.  t = mu' * x, q = t * x; fp64, NO fused multiply-adds (gb25_integrate_field forms `second` with one: the two
+ *      differ in the last bits).
+ *      REDUCTION ORDER, member by member, every sum starting from +0.0; a point that does not count adds nothing:
+ *        1. the column partial  c(i, j) = the block's levels, ascending k
+ *        2. the segment         s(I, j) = c(i, j) over the block's bx columns, ascending i
+ *        3. the block           = s(I, j) over the block's by rows, ascending j
+ *      gb-25_amd/blocks.py block_sums_host restates it with numpy bit for bit.
+ *      gb25_block_info: the result's dims; points and nonfinite totalled over all blocks; empty_blocks = the blocks whose measure
+ *      is 0; global_offset as in gb25_field_stats (of the FINE interior: block I starts at fine column I bx + 1).
+ *      gb25_get_block_sums: each of measure, first, second may be NULL (all three: an error); only the planes asked for are
+ *      copied.  gb25_compute_block_sums: the three planes one after another (measure, first, second; dims[0] dims[1] dims[2]
+ *      doubles each) in an array the model owns (made by the first call, made anew when a call needs more, freed by
+ *      gb25_destroy); read-only, complete when the call returns, valid until the next call on m.
+ *      gb25_get_derived_block_sums: gb25_compute_derived into the model's packed array, then the same kernel over it; the
+ *      measure is that of (c,c,c), or of 2-D (c,c) for the mixed-layer depth.  GB25_D_VORTICITY lives at (f,f,c), which has no
+ *      measure in the table: GB25_ERR_INVALID_ARGUMENT.
+ *      ERRORS, each GB25_ERR_INVALID_ARGUMENT with a message that names the argument: a block extent <= 0 or one that does not
+ *      divide, bx > 256, a window outside the field, a weight that is negative or not finite, weights on a 2-D field, no output
+ *      requested. */
+#define GB25_BLOCK_MAX_BX 256
+typedef struct {
+  int32_t bx, by, bz;
+  int32_t k_first, k_count;          /* levels of the field; k_count = -1: all from k_first on */
+  int32_t reserved;
+} gb25_blocks;
+typedef struct {
+  int32_t dims[3], reserved;
+  int64_t points, nonfinite, empty_blocks;
+  int32_t global_offset[3], reserved2;
+} gb25_block_info;
+int32_t gb25_block_info_bytes(void);
+gb25_status gb25_block_dims(const gb25_model *m, gb25_field f, const gb25_blocks *blocks, int32_t dims[3]);   /* needs no device */
+gb25_status gb25_derived_block_dims(const gb25_model *m, gb25_derived q, const gb25_blocks *blocks, int32_t dims[3]);   /* needs no device */
+gb25_status gb25_get_block_sums(gb25_model *m, gb25_field f, const gb25_blocks *blocks, const double *level_weight /* may be NULL */,
+                                double *measure, double *first, double *second, gb25_block_info *info /* may be NULL */);
+gb25_status gb25_compute_block_sums(gb25_model *m, gb25_field f, const gb25_blocks *blocks, const double *level_weight,
+                                    gb25_block_info *info, const double **dev, int32_t device_dims[3]);
+gb25_status gb25_get_derived_block_sums(gb25_model *m, gb25_derived q, double param, const gb25_blocks *blocks,
+                                        const double *level_weight, double *measure, double *first, double *second,
+                                        gb25_block_info *info);
+
 /* ---- time averages and eddy fluxes accumulated on the device (csrc/averages_kernels.hpp, k_averages_accumulate): what the other
  *      diagnostics cannot do -- remember something between two calls.  The time-mean state, eddy kinetic energy and tracer
  *      variance, the eddy heat and salt fluxes <v'T'>, <u'T'>, <w'T'>: Oceananigans' AveragedTimeInterval, without five parent arrays

@@ -22,6 +22,7 @@ export Config, Model, create, destroy!, first_time_step!, time_step!, loop!, ini
        Transport, transport, overturning, ACROSS_Y, ACROSS_X, TR_LINES, TR_PROFILE, TR_STREAMFUNCTION,
        DERIVED, derived_dims, compute_derived, get_derived, derived_stats, field_levels,
        STABILITY, stability_dims, compute_stability, get_stability, stability_stats,
+       Blocks, BlockInfo, block_dims, block_sums, compute_block_sums, derived_block_sums,
        AVG_MEANS, AVG_SQUARES, AVG_FLUXES, AVERAGE, AveragesInfo, averages_begin, averages_accumulate, averages_info, average_dims,
        get_average, averages_end
 
@@ -485,6 +486,64 @@ function stability_stats(m::Model, q::Integer; param::Real = (q == STABILITY.ric
     check(m, ccall((:gb25_get_stability_stats, m.lib), Cint, (Ptr{Cvoid}, Cint, Float64, Ref{FieldStats}), m.ptr, q, param, out),
           "gb25_get_stability_stats")
     return out[]
+end
+# ---- block sums on the device (gb25_block_dims / gb25_derived_block_dims / gb25_get_block_sums / gb25_compute_block_sums /
+#      gb25_get_derived_block_sums): definitions in include/gb25.h.  block = (bx, by, bz); k_first counts the field's own levels,
+#      0-based like the ABI; k_count = -1: all from k_first on; level_weight: one Float64 per level of the field, or nothing.
+struct Blocks
+    bx::Int32; by::Int32; bz::Int32
+    k_first::Int32; k_count::Int32
+    reserved::Int32
+end
+struct BlockInfo
+    dims::NTuple{3, Int32}; reserved::Int32
+    points::Int64; nonfinite::Int64; empty_blocks::Int64
+    global_offset::NTuple{3, Int32}; reserved2::Int32
+end
+Blocks(block; k_first::Integer = 0, k_count::Integer = -1) = Blocks(block[1], block[2], block[3], k_first, k_count, 0)
+"dims of the block sums of a field: (Nx / bx, Ny / by, k_count / bz); needs no device"
+function block_dims(m::Model, field::Integer, block; k_first::Integer = 0, k_count::Integer = -1)
+    out = zeros(Int32, 3)
+    check(m, ccall((:gb25_block_dims, m.lib), Cint, (Ptr{Cvoid}, Cint, Ref{Blocks}, Ptr{Int32}), m.ptr, field,
+                   Blocks(block; k_first, k_count), out), "gb25_block_dims")
+    return Tuple(Int.(out))
+end
+"(measure, first, second, info) of a field's blocks: three Array{Float64, 3} [I, J, K] and a BlockInfo"
+function block_sums(m::Model, field::Integer, block; k_first::Integer = 0, k_count::Integer = -1,
+                    level_weight::Union{Nothing, Vector{Float64}} = nothing)
+    ccall((:gb25_block_info_bytes, m.lib), Int32, ()) == sizeof(BlockInfo) || error("gb25_block_info: the library and GB25HIP.jl differ")
+    dims = block_dims(m, field, block; k_first, k_count)
+    measure, first, second = (Array{Float64}(undef, dims...) for _ in 1:3)
+    info = Ref{BlockInfo}()
+    check(m, ccall((:gb25_get_block_sums, m.lib), Cint,
+                   (Ptr{Cvoid}, Cint, Ref{Blocks}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{BlockInfo}), m.ptr, field,
+                   Blocks(block; k_first, k_count), level_weight === nothing ? C_NULL : level_weight, measure, first, second, info),
+          "gb25_get_block_sums")
+    return measure, first, second, info[]
+end
+"(device pointer, dims, info): the planes measure | first | second one after another; read-only, valid until the next call on m"
+function compute_block_sums(m::Model, field::Integer, block; k_first::Integer = 0, k_count::Integer = -1,
+                            level_weight::Union{Nothing, Vector{Float64}} = nothing)
+    p, dims, info = Ref{Ptr{Float64}}(C_NULL), zeros(Int32, 3), Ref{BlockInfo}()
+    check(m, ccall((:gb25_compute_block_sums, m.lib), Cint,
+                   (Ptr{Cvoid}, Cint, Ref{Blocks}, Ptr{Float64}, Ref{BlockInfo}, Ref{Ptr{Float64}}, Ptr{Int32}), m.ptr, field,
+                   Blocks(block; k_first, k_count), level_weight === nothing ? C_NULL : level_weight, info, p, dims),
+          "gb25_compute_block_sums")
+    return p[], Tuple(Int.(dims)), info[]
+end
+"the block sums of a derived field at (c,c): DERIVED.kinetic_energy, density_anomaly, potential_density, mixed_layer_depth"
+function derived_block_sums(m::Model, d::Integer, block; param::Real = 0.0, k_first::Integer = 0, k_count::Integer = -1,
+                            level_weight::Union{Nothing, Vector{Float64}} = nothing)
+    out = zeros(Int32, 3)
+    check(m, ccall((:gb25_derived_block_dims, m.lib), Cint, (Ptr{Cvoid}, Cint, Ref{Blocks}, Ptr{Int32}), m.ptr, d,
+                   Blocks(block; k_first, k_count), out), "gb25_derived_block_dims")
+    measure, first, second = (Array{Float64}(undef, Int.(out)...) for _ in 1:3)
+    info = Ref{BlockInfo}()
+    check(m, ccall((:gb25_get_derived_block_sums, m.lib), Cint,
+                   (Ptr{Cvoid}, Cint, Float64, Ref{Blocks}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{BlockInfo}), m.ptr, d,
+                   param, Blocks(block; k_first, k_count), level_weight === nothing ? C_NULL : level_weight, measure, first, second, info),
+          "gb25_get_derived_block_sums")
+    return measure, first, second, info[]
 end
 "interior levels of an ordinary field, gathered on the device: field_levels(m, FIELD.T, Nz - 1, 1) is interior(T)[:, :, Nz:Nz]"
 function field_levels(m::Model{FT}, field::Integer, k_first::Integer = 0, k_count::Integer = -1) where {FT}

@@ -56,6 +56,14 @@ struct EventPair {
 // Every block of device memory a model allocates, remembered where it is made and freed by gb25_destroy in one loop: whichever
 // member holds a pointer by then (the look-aheads exchange them) and however many Fields share a block.  A block is remembered
 // before it is zeroed, so a failing hipMemset loses nothing.  (DiagState frees in mid-life and keeps its own memory.)
+// The zeros are IN the block when zeroed() returns: hipMemset of device memory goes to the null stream and returns before the device
+// has run it, and the model's streams are non-blocking, so nothing else orders a kernel launched next behind it -- a block allocated
+// in mid-run (the corrected velocities of a step through the tracer kernel) was zeroed AFTER its first kernels had written it
+// whenever the device was busy enough ("Reproducibility of a step").
+inline hipError_t zeroed(void* d, size_t bytes) {
+  const hipError_t e = hipMemset(d, 0, bytes);
+  return e != hipSuccess ? e : hipStreamSynchronize(nullptr);
+}
 struct DeviceBlocks {
   std::vector<void*> blocks;
   template <class T>
@@ -65,7 +73,7 @@ struct DeviceBlocks {
     if (e != hipSuccess) return e;
     blocks.push_back(d);
     *p = static_cast<T*>(d);
-    return zero ? hipMemset(d, 0, bytes) : hipSuccess;
+    return zero ? zeroed(d, bytes) : hipSuccess;
   }
   template <class T>
   void release(T*& p) {   // one block before the end (a field of the prescribed atmosphere that is taken away again)
@@ -978,7 +986,7 @@ gb25_status alloc_field(gb25_model* m, Field& F, int nx, int ny, int nz) {
   if (e != hipSuccess)
     return fail(m, GB25_ERR_OUT_OF_MEMORY, "hipMalloc of %zu bytes failed: %s", F.elems() * sizeof(real),
                 hipGetErrorString(e));
-  HIPCHK(hipMemset(F.d, 0, F.elems() * sizeof(real)));
+  HIPCHK(zeroed(F.d, F.elems() * sizeof(real)));
   return GB25_OK;
 }
 

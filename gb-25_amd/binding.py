@@ -65,6 +65,8 @@ ABI_SYMBOLS = [
     "gb25_stability_dims", "gb25_compute_stability", "gb25_get_stability", "gb25_get_stability_stats",
     "gb25_block_info_bytes", "gb25_block_dims", "gb25_derived_block_dims", "gb25_get_block_sums", "gb25_compute_block_sums",
     "gb25_get_derived_block_sums",
+    "gb25_filter_info_bytes", "gb25_filter_dims", "gb25_derived_filter_dims", "gb25_get_filter_sums", "gb25_compute_filter_sums",
+    "gb25_get_derived_filter_sums",
     "gb25_averages_info_bytes", "gb25_averages_begin", "gb25_averages_accumulate", "gb25_averages_get_info", "gb25_average_dims",
     "gb25_get_average", "gb25_average_device_ptr", "gb25_averages_end",
     "gb25_particles_info_bytes", "gb25_particles_begin", "gb25_particles_set", "gb25_particles_get", "gb25_particles_advance",
@@ -207,6 +209,19 @@ class BlockInfo(_Record):
     measure is 0, the global offset of the rank's fine interior."""
     _fields_ = [("dims", C.c_int32 * 3), ("reserved", C.c_int32), ("points", C.c_int64), ("nonfinite", C.c_int64),
                 ("empty_blocks", C.c_int64), ("global_offset", C.c_int32 * 3), ("reserved2", C.c_int32)]
+
+
+class Filter(C.Structure):
+    """gb25_filter (include/gb25.h): the radii and strides of the window and the window of levels."""
+    _fields_ = [("rx", C.c_int32), ("ry", C.c_int32), ("sx", C.c_int32), ("sy", C.c_int32), ("k_first", C.c_int32),
+                ("k_count", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FilterInfo(_Record):
+    """gb25_filter_info (include/gb25.h): the result's dims, the skipped source points, the outputs whose measure is 0, the
+    outputs whose y window was cut, the global offset of the fine interior."""
+    _fields_ = [("dims", C.c_int32 * 3), ("reserved", C.c_int32), ("nonfinite", C.c_int64), ("empty", C.c_int64),
+                ("clipped", C.c_int64), ("global_offset", C.c_int32 * 3), ("reserved2", C.c_int32)]
 
 
 class Transport(_Record):
@@ -430,6 +445,11 @@ def load_library(float_type="Float32"):
     lib.gb25_get_block_sums.argtypes = [P, C.c_int, C.POINTER(Blocks), P, P, P, P, C.POINTER(BlockInfo)]
     lib.gb25_compute_block_sums.argtypes = [P, C.c_int, C.POINTER(Blocks), P, C.POINTER(BlockInfo), C.POINTER(P), C.POINTER(C.c_int32)]
     lib.gb25_get_derived_block_sums.argtypes = [P, C.c_int, C.c_double, C.POINTER(Blocks), P, P, P, P, C.POINTER(BlockInfo)]
+    lib.gb25_filter_dims.argtypes = [P, C.c_int, C.POINTER(Filter), C.POINTER(C.c_int32)]
+    lib.gb25_derived_filter_dims.argtypes = [P, C.c_int, C.POINTER(Filter), C.POINTER(C.c_int32)]
+    lib.gb25_get_filter_sums.argtypes = [P, C.c_int, C.POINTER(Filter), P, P, P, P, P, P, C.POINTER(FilterInfo)]
+    lib.gb25_compute_filter_sums.argtypes = [P, C.c_int, C.POINTER(Filter), P, P, P, C.POINTER(FilterInfo), C.POINTER(P), C.POINTER(C.c_int32)]
+    lib.gb25_get_derived_filter_sums.argtypes = [P, C.c_int, C.c_double, C.POINTER(Filter), P, P, P, P, P, P, C.POINTER(FilterInfo)]
     lib.gb25_averages_begin.argtypes = [P, C.c_int32, C.c_int32, C.c_int32]
     lib.gb25_averages_accumulate.argtypes = [P, C.c_double]
     lib.gb25_averages_get_info.argtypes = [P, C.POINTER(AveragesInfo)]
@@ -466,7 +486,7 @@ def load_library(float_type="Float32"):
                        ("gb25_budget_bytes", Budget), ("gb25_transport_bytes", Transport),
                        ("gb25_class_sum_bytes", ClassSum), ("gb25_spectral_coefficient_bytes", SpectralCoefficient),
                        ("gb25_averages_info_bytes", AveragesInfo), ("gb25_particles_info_bytes", ParticlesInfo),
-                       ("gb25_block_info_bytes", BlockInfo)):
+                       ("gb25_block_info_bytes", BlockInfo), ("gb25_filter_info_bytes", FilterInfo)):
         getattr(lib, fn).restype = C.c_int32
         if getattr(lib, fn)() != C.sizeof(struct):
             raise GB25Error(f"{path}: {fn}() = {getattr(lib, fn)()} there, {C.sizeof(struct)} bytes in this binding: "
@@ -850,6 +870,67 @@ class HipBackend:
         p, d, info = C.c_void_p(), (C.c_int32 * 3)(), BlockInfo()
         self._call("gb25_compute_block_sums", FIELD_IDS[field], C.byref(blocks), self._checked_weights(field, lw), C.byref(info),
                    C.byref(p), d)
+        return p.value, tuple(d), info
+
+    # ---- moving-window filter on the device (include/gb25.h: "moving-window filter"; gb-25_amd/filters.py).  source: as for the
+    #      block sums; radius = (rx, ry) in grid points; stride = (sx, sy); levels = (k_first, k_count) of the field's own levels;
+    #      wx, wy: 2 rx + 1 and 2 ry + 1 float64 weights or None (the box); rx_of_row: one int32 per row or None
+    def _filter_args(self, radius, stride, levels, wx, wy, rx_of_row):
+        k_first, k_count = (0, -1) if levels is None else levels
+        (rx, ry), (sx, sy) = radius, stride
+        flt = Filter(int(rx), int(ry), int(sx), int(sy), int(k_first), int(k_count), 0)
+        # (the library reads 2 r + 1 weights and one radius per row: a vector of another length never reaches it)
+        keep = []
+        for name, w, n, dtype in (("wx", wx, 2 * flt.rx + 1, np.float64), ("wy", wy, 2 * flt.ry + 1, np.float64),
+                                  ("rx_of_row", rx_of_row, self.field_dims("T", False)[1], np.int32)):
+            if w is None:
+                keep.append(None)
+                continue
+            a = np.ascontiguousarray(w, dtype).reshape(-1)
+            if a.size != n and n > 0:
+                raise GB25Error(f"filter sums: {name} has {a.size} entries, the call needs {n}")
+            keep.append(a)
+        return flt, keep, [None if a is None else a.ctypes.data_as(C.c_void_p) for a in keep]
+
+    def filter_dims(self, source, radius, stride=(1, 1), levels=None):
+        """gb25_filter_dims / gb25_derived_filter_dims: (Nx / sx, Ny / sy, k_count) after the checks of the window.  Needs no
+        device."""
+        k_first, k_count = (0, -1) if levels is None else levels
+        flt = Filter(int(radius[0]), int(radius[1]), int(stride[0]), int(stride[1]), int(k_first), int(k_count), 0)
+        d = (C.c_int32 * 3)()
+        if source in DERIVED_IDS:
+            self._call("gb25_derived_filter_dims", DERIVED_IDS[source], C.byref(flt), d)
+        else:
+            self._block_levels(source)
+            self._call("gb25_filter_dims", FIELD_IDS[source], C.byref(flt), d)
+        return tuple(d)
+
+    def filter_sums(self, source, radius, stride=(1, 1), levels=None, wx=None, wy=None, rx_of_row=None, param=None,
+                    planes=("measure", "first", "second")):
+        """gb25_get_filter_sums / gb25_get_derived_filter_sums: filters.FilterSums with the planes asked for, [I, J, K] float64
+        each (the others None; only those are copied), and the info record."""
+        from .filters import FilterSums
+        dims = self.filter_dims(source, radius, stride, levels)
+        flt, keep, w = self._filter_args(radius, stride, levels, wx, wy, rx_of_row)
+        out = {n: (np.empty(dims[::-1], np.float64) if n in planes else None) for n in ("measure", "first", "second")}
+        ptrs = [None if a is None else a.ctypes.data_as(C.c_void_p) for a in out.values()]
+        info = FilterInfo()
+        if source in DERIVED_IDS:
+            q, param, _, _ = self._derived_args(source, param, None)
+            self._call("gb25_get_derived_filter_sums", q, param, C.byref(flt), *w, *ptrs, C.byref(info))
+        else:
+            self._call("gb25_get_filter_sums", FIELD_IDS[source], C.byref(flt), *w, *ptrs, C.byref(info))
+        m, t, s = (None if a is None else a.transpose(2, 1, 0) for a in out.values())
+        return FilterSums(m, t, s, radius=radius, stride=stride, dims=tuple(info.dims), nonfinite=info.nonfinite, empty=info.empty,
+                          clipped=info.clipped, global_offset=tuple(info.global_offset))
+
+    def compute_filter_sums(self, field, radius, stride=(1, 1), levels=None, wx=None, wy=None, rx_of_row=None):
+        """(device pointer, dims, FilterInfo): the planes measure | first | second one after another, dims[0] dims[1] dims[2]
+        doubles each, I fastest; read-only, valid until the next call on this model."""
+        self._block_levels(field)
+        flt, keep, w = self._filter_args(radius, stride, levels, wx, wy, rx_of_row)
+        p, d, info = C.c_void_p(), (C.c_int32 * 3)(), FilterInfo()
+        self._call("gb25_compute_filter_sums", FIELD_IDS[field], C.byref(flt), *w, C.byref(info), C.byref(p), d)
         return p.value, tuple(d), info
 
     # ---- time averages accumulated on the device (include/gb25.h: "time averages and eddy fluxes"); names: AVERAGE_IDS

@@ -1,6 +1,7 @@
 // block_kernels.hpp -- block sums (gb25_get_block_sums, gb25_compute_block_sums, gb25_get_derived_block_sums: include/gb25.h): the
 // interior of a field, or of a packed derived field, cut into boxes of bx x by x bz points; per box sum mu', sum mu' x and
-// sum mu' x^2 in fp64 with mu THE MEASURE of gb25_integrate_field (k_field_moments: the same tables, the same expression) and
+// sum mu' x^2 in fp64 with mu THE MEASURE of gb25_integrate_field (k_field_moments: the same tables, the same expression --
+// measure_column, measure_level of diagnostics_kernels.hpp, shared with the moving-window filter of filter_kernels.hpp) and
 // mu' = mu * level_weight[k].  Coarse fields (block means), column integrals, heat content.
 //
 //   k_block_sums<T, LOC, ONE>  a workgroup takes one tile of W = (256 / bx) bx consecutive columns of one block row J and one block
@@ -51,7 +52,6 @@ template <class T, int LOC, bool ONE>
 __global__ __launch_bounds__(BLK_THREADS) void k_block_sums(Grid g, MomentsTables tab, const T* __restrict__ a, DiagBox box, BlockArgs A) {
 #pragma clang fp contract(off)
   constexpr int HL = (LOC == LOC_FCC || LOC == LOC_FC) ? 1 : (LOC == LOC_CFC || LOC == LOC_CF) ? 2 : 0;
-  constexpr bool FLAT = LOC >= LOC_CC;
   __shared__ double lds[ONE ? 1 : 3 * BLK_THREADS];
   const int t = threadIdx.x;
   const int W = ONE ? BLK_THREADS : (BLK_THREADS / A.bx) * A.bx;
@@ -66,12 +66,8 @@ __global__ __launch_bounds__(BLK_THREADS) void k_block_sums(Grid g, MomentsTable
   for (int jj = 0; jj < A.by; jj++) {
     const int j = J * A.by + jj;
     double cm = 0.0, ct = 0.0, cq = 0.0;   // the column partial c(i, j)
-    const bool wall = HL == 2 && (j == g.jws || (j == g.jwn && !g.cv.north_fold));   // (a y face on a wall of the GLOBAL grid)
-    if (active && !wall) {
-      const double fold = (HL != 2 && j == tab.pivot_row) ? 0.5 : 1.0;
-      const int o2 = i2(g, i, j);
-      const double area = tab.area[HL] ? (double)tab.area[HL][o2] : (double)(HL == 2 ? g.azf[j] : g.azc[j]);
-      const int first_wet = tab.first[HL] ? (int)tab.first[HL][o2] : 0;
+    if (active && !measure_wall_row<HL>(g, j)) {
+      const MeasureColumn mc = measure_column<HL>(g, tab, i, j);
       const T* col = a + (box.origin + i + box.pitch * j + box.plane * ka);
       for (int kk0 = 0; kk0 < A.bz; kk0 += BLK_AHEAD) {
         T e[BLK_AHEAD];
@@ -82,9 +78,7 @@ __global__ __launch_bounds__(BLK_THREADS) void k_block_sums(Grid g, MomentsTable
         for (int s = 0; s < BLK_AHEAD; s++) {
           if (kk0 + s >= A.bz) break;
           const int k = k0 + kk0 + s;
-          const double dz = FLAT ? 1.0 : (double)uniform_at(LOC == LOC_CCF ? g.dzf : g.dzc, k);
-          const int level = FLAT ? g.Nz - 1 : k;   // wet: level >= the column's first wet level
-          double mu = level < first_wet ? 0.0 : (area * dz) * fold;
+          double mu = measure_level<LOC>(g, mc, k);
           if (A.level_weight) mu = mu * A.level_weight[k];
           if (!(mu > 0.0)) continue;
           const double x = (double)e[s];

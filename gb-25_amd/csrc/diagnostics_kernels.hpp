@@ -311,6 +311,35 @@ struct MomentsTables {
   int pivot_row;                    // local row of the GLOBAL pivot row of a folded grid on this rank, else -1
 };
 
+// THE MEASURE point by point, for the kernels that keep it apart from the value (k_block_sums, k_filter_x: ONE expression, so
+// that their planes agree bit for bit): the part of a column -- its area, its first wet level, the pivot row's 1/2 --, then the
+// level's.  HL: the horizontal location of the tables, 0 (c,c), 1 (f,c), 2 (c,f).  Pure products: nothing here can contract.
+struct MeasureColumn {
+  double area, fold;
+  int first_wet;
+};
+template <int HL>
+__device__ __forceinline__ bool measure_wall_row(const Grid& g, int j) {   // (a y face on a wall of the GLOBAL grid: mu = 0)
+  return HL == 2 && (j == g.jws || (j == g.jwn && !g.cv.north_fold));
+}
+template <int HL>
+__device__ __forceinline__ MeasureColumn measure_column(const Grid& g, const MomentsTables& tab, int i, int j) {
+  const int o2 = i2(g, i, j);
+  MeasureColumn c;
+  c.fold = (HL != 2 && j == tab.pivot_row) ? 0.5 : 1.0;
+  c.area = tab.area[HL] ? (double)tab.area[HL][o2] : (double)(HL == 2 ? g.azf[j] : g.azc[j]);
+  c.first_wet = tab.first[HL] ? (int)tab.first[HL][o2] : 0;
+  return c;
+}
+// k: the level in the field's own count, wave-uniform
+template <int LOC>
+__device__ __forceinline__ double measure_level(const Grid& g, const MeasureColumn& c, int k) {
+  constexpr bool FLAT = LOC >= LOC_CC;
+  const double dz = FLAT ? 1.0 : (double)uniform_at(LOC == LOC_CCF ? g.dzf : g.dzc, k);
+  const int level = FLAT ? g.Nz - 1 : k;   // wet: level >= the column's first wet level
+  return level < c.first_wet ? 0.0 : (c.area * dz) * c.fold;
+}
+
 template <class T, int LOC>
 __global__ __launch_bounds__(DIAG_THREADS) void k_field_moments(Grid g, MomentsTables tab, const T* __restrict__ a, DiagBox box,
                                                                 MomentsPartial* __restrict__ rows) {

@@ -1,5 +1,5 @@
 // diagnostics_state.hpp -- every piece of memory and bookkeeping the read-only diagnostics own (diagnostics_host.hpp,
-// averages_host.hpp, classes_host.hpp, particles_host.hpp, spectrum_host.hpp, surfaces_host.hpp, stability_host.hpp, blocks_host.hpp), as ONE member of gb25_model.
+// averages_host.hpp, classes_host.hpp, particles_host.hpp, spectrum_host.hpp, surfaces_host.hpp, stability_host.hpp, blocks_host.hpp, filters_host.hpp), as ONE member of gb25_model.
 // Host only; included by gb25_api.hip behind the kernel headers (PartState: particle_kernels.hpp; SURF_MAX: surface_kernels.hpp;
 // GB25_A_COUNT and the info structs: include/gb25.h); like Field it is local to that translation unit, so the libraries export
 // nothing of it.
@@ -74,6 +74,15 @@ struct DiagState {
   void* blocks = nullptr;
   size_t block_bytes = 0;
   std::vector<double> block_weights;
+  // moving-window filter (gb25_get_filter_sums, gb25_compute_filter_sums, gb25_get_derived_filter_sums): ONE allocation -- the
+  // counts of the info record (BlockCounts, padded to 32 bytes), the weights wx and wy (2 x 65 doubles), the radius of every row
+  // (Ny int32), the planes measure | first | second of one call, the x pass's scratch planes, then the count slots of the waves
+  // of its two launches --, made by the first call, made anew when a call needs more bytes.  The host copies the uploads read
+  // (words of the model: no copy is ever pending from a frame that has returned)
+  void* filters = nullptr;
+  size_t filter_bytes = 0;
+  std::vector<double> filter_wx, filter_wy;
+  std::vector<int32_t> filter_rows;
   // time averages (gb25_averages_*): the accumulators of the active groups and the array a normalized read-out is divided into
   // -- ONE allocation (avg_acc[0] is its base: MEANS is always active), made by gb25_averages_begin, freed by gb25_averages_end
   // and gb25_destroy --, the window, the sample count and weight_sum (avg_info)
@@ -143,6 +152,8 @@ struct DiagState {
     drop(stability);
     drop(blocks);
     block_bytes = 0;
+    drop(filters);
+    filter_bytes = 0;
     release_tables();
     release_averages();
     release_particles();

@@ -16,6 +16,7 @@
 #include "surface_kernels.hpp"
 #include "stability_kernels.hpp"
 #include "block_kernels.hpp"
+#include "filter_kernels.hpp"
 #include "diagnostics_state.hpp"
 #include "validity.hpp"
 #include "step_route.hpp"
@@ -3715,3 +3716,4 @@ gb25_status gb25_profile_get(gb25_model* m, gb25_kernel k, int64_t* launches, do
 #include "surfaces_host.hpp"
 #include "stability_host.hpp"
 #include "blocks_host.hpp"
+#include "filters_host.hpp"

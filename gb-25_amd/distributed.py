@@ -275,6 +275,12 @@ class LocalSlabEnsemble:
         from .blocks import block_sums, gather_blocks
         return gather_blocks([block_sums(b, source, block, levels, level_weights, param) for b in self.backends])
 
+    # moving-window filter: a window reaches beyond a slab, so the device entry refuses on a rank; the source and the measure are
+    # gathered and the definition is applied on the host (gb-25_amd/filters.py): the single domain's planes bit for bit
+    def filter_sums(self, source, radius, stride=(1, 1), levels=None, wx=None, wy=None, rx_of_row=None):
+        from .filters import ensemble_filter_sums
+        return ensemble_filter_sums(self, source, radius, stride, levels, wx, wy, rx_of_row)
+
     # time averages: likewise (gb-25_amd/averages.py); every slab accumulates its own interior, the read-out is placed by
     # global offset
     def averages_begin(self, groups=("means", "squares", "fluxes"), levels=None):

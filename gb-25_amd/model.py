@@ -80,6 +80,11 @@ class Field:
         this module)."""
         return _block_sums(self._b, self.name, block).mean()
 
+    def filtered(self, radius, kernel="box", stride=(1, 1)):
+        """The field smoothed by a moving window of radius = (rx, ry) grid points, measure-weighted, [I, J, K], on the device
+        (filtered of this module)."""
+        return _filter_sums(self._b, self.name, radius, kernel, stride).mean()
+
     def zonal_spectrum(self, wavenumbers=None, levels=None):
         """(X [level, row, m] complex128, nonfinite_lines): the zonal wavenumber coefficients of every interior line, computed
         where the field lives (zonal_spectrum of this module)."""
@@ -404,6 +409,44 @@ def heat_content(model, depth_range=None, heat_capacity=3991.86795711963, refere
     first = sums.first[:, :, 0] - reference_temperature * sums.measure[:, :, 0]
     with np.errstate(invalid="ignore", divide="ignore"):
         return np.where(area > 0, (model.backend.cfg.rho0 * heat_capacity) * first / area, 0.0)
+
+
+def _filter_sums(b, source, radius, kernel="box", stride=(1, 1), levels=None, length=None, param=None):
+    from .filters import filter_sums, kernel_weights, rows_for_length   # (the kernels, or the numpy restatement on a backend without them)
+    rx, ry = (int(q) for q in radius)
+    rows = None if length is None else rows_for_length(b, source, length)
+    wx = None if kernel == "box" or rows is not None else kernel_weights(kernel, rx)
+    wy = None if kernel == "box" else kernel_weights(kernel, ry)
+    return filter_sums(b, source, (rx, ry), stride, levels, wx, wy, rows, param)
+
+
+def filtered(model, source, radius, kernel="box", stride=(1, 1), levels=None, length=None):
+    """`source` -- a field name or "kinetic_energy", "density_anomaly", "potential_density", "mixed_layer_depth" -- smoothed level
+    by level by a moving window of radius = (rx, ry) grid points around every stride-th point, measure-weighted, [I, J, K]
+    float64, on the device (include/gb25.h, gb25_get_filter_sums): xbar of a scale separation, NaN where a window holds no wet
+    point.  kernel: "box", "gaussian" or "triangle" (filters.kernel_weights).  The window wraps in x and is clipped at the
+    southern and northern rows.  length [m]: every row gets the rx that makes its window about that wide (filters.rows_for_length;
+    rx is then ignored and x is the box).  levels = (k_first, k_count) of the field's own levels."""
+    return _filter_sums(model.backend, source, radius, kernel, stride, levels, length).mean()
+
+
+def subfilter_variance(model, source, radius, kernel="box", stride=(1, 1), levels=None, length=None):
+    """The variance of `source` inside the window of every output point, measure-weighted, [I, J, K]: what lies below the filter
+    scale (of "u" and "v": twice the eddy kinetic energy below that scale, without a time mean).  Arguments as for filtered."""
+    return _filter_sums(model.backend, source, radius, kernel, stride, levels, length).variance()
+
+
+def eddy_part(model, source, radius, kernel="box", levels=None, length=None):
+    """x' = x - xbar at every point (stride 1), [i, j, k] float64 over the rows of cell centres: the part of `source` below the
+    filter scale.  NaN where the point itself is dry (its measure is 0) or its window is empty.  Arguments as for filtered."""
+    from .filters import filter_sums, source_values
+    b = model.backend
+    sums = _filter_sums(b, source, radius, kernel, (1, 1), levels, length)
+    own = filter_sums(b, source, (0, 0), (1, 1), levels).measure          # mu of the counted points
+    k0 = 0 if levels is None else int(levels[0])
+    x = np.asarray(source_values(b, source), np.float64)[:, :sums.dims[1], k0:k0 + sums.dims[2]]
+    with np.errstate(invalid="ignore"):
+        return np.where(own > 0, x - sums.mean(), np.nan)
 
 
 def _transport(model, faces, shape, window=None):

@@ -937,6 +937,82 @@ gb25_status gb25_get_derived_block_sums(gb25_model *m, gb25_derived q, double pa
                                         const double *level_weight, double *measure, double *first, double *second,
                                         gb25_block_info *info);
 
+/* ---- moving-window filter on the device (csrc/filter_kernels.hpp, k_filter_x, k_filter_y): what the block sums cannot give --
+ *      their boxes are disjoint, so block means jump at box edges and x - mean is not defined per point.  Here every output point
+ *      has a window of its own, centred on it: the filtered field xbar on the model grid, the eddy part x' = x - xbar and the
+ *      variance below the filter scale, the first step of every scale separation of an eddying run, without the parent array
+ *      crossing PCIe.  HORIZONTAL, level by level, over the interior of a field or of a derived field at (c,c).  Same contract as
+ *      every diagnostic here: the state gb25_get_field would return (a stale GB25_PHY recomputed, previous velocities read where
+ *      they live), READ-ONLY for the schedule (nothing pinned, every look-ahead alive), bitwise repeatable, no floating-point
+ *      atomics, launches under GB25_K_DIAGNOSTICS on the model's stream.  NOT on a rank of a decomposition (below).
+ *
+ *      MEASURE AND COUNTING.  mu is THE MEASURE of gb25_integrate_field above, by the field's location: the same tables and the
+ *      same expression as the block sums (one device function serves both kernels), the pivot row's 1/2 included.  A source point
+ *      counts iff mu > 0 and x = (double) of the stored value is finite; then m = mu, t = mu * x, q = t * x in fp64, NO fused
+ *      multiply-adds; otherwise its m, t and q are +0.0.  A point with mu > 0 whose x is not finite is counted ONCE in nonfinite:
+ *      per source point of the rows 0 .. Ny - 1 of the window of levels, not per window that contains it, and whether or not
+ *      a window contains it.  A value in an immersed cell is invisible.
+ *      WINDOW (gb25_filter).  Radii 0 <= rx, ry <= GB25_FILTER_MAX_RADIUS in grid points; strides sx | Nx and sy | Ny (a filtered
+ *      field is smooth: a caller need not download every point).  Output point (I, J, K) is centred on the fine point
+ *      (I sx, J sy, k_first + K); the result has dims (Nx / sx, Ny / sy, k_count), I fastest.  k_first, k_count select levels as
+ *      in gb25_blocks (k_count = -1: all from k_first on) in the field's OWN level count; a 2-D field takes 0, 1 or 0, -1.
+ *      EDGES.  x wraps modulo Nx: every grid type of this library is periodic in x (LatitudeLongitudeGrid and the tripolar grids
+ *      alike have topology Periodic in x), so none is clipped there; 2 rx + 1 <= Nx is required, so that no point enters a window
+ *      twice.  y is clipped to the rows 0 .. Ny - 1 of cell centres: the wall row Ny of a (c,f) field is in no window, nothing
+ *      reaches across the fold; a clipped window is simply smaller, and the measure plane normalises it.
+ *      WEIGHTS (both may be NULL).  wx[2 rx + 1], wy[2 ry + 1]: fp64, finite, >= 0, each with a positive sum.  NULL is the box
+ *      filter, and no multiply is made.  A Gaussian and a triangle are vectors the host builds (gb-25_amd/filters.py
+ *      kernel_weights).
+ *      FIXED PHYSICAL WIDTH.  rx_of_row (may be NULL): Ny int32, the rx of every row j -- of the x sums s(., j), whichever y
+ *      windows they then enter --, each 0 .. GB25_FILTER_MAX_RADIUS with 2 rx + 1 <= Nx; rx of gb25_filter is then ignored (but
+ *      checked).  On the LatitudeLongitudeGrid dx at 80 degrees is 5.7 times smaller than at the equator.  Refused together with wx:
+ *      with a radius per row x is the box.
+ *      REDUCTION ORDER, plane by plane (m, t and q alike), every sum starting from +0.0:
+ *        1. s(i, j) = sum over d = -rx .. rx, ascending, of [wx[d + rx] *] a(wrap(i + d), j)
+ *        2. b(i, j) = sum over e = -ry .. ry, ascending, rows outside 0 .. Ny - 1 skipped, of [wy[e + ry] *] s(i, j + e)
+ *      A weight times a term rounds by itself, then the addition.  measure = b of m, first = b of t, second = b of q:
+ *      xbar = first / measure, the variance below the filter scale = second / measure - xbar^2.  gb-25_amd/filters.py
+ *      filter_sums_host restates it with numpy bit for bit.
+ *      gb25_filter_info: the result's dims; nonfinite (above); empty = the outputs whose measure is 0; clipped = the outputs whose
+ *      y window was cut; global_offset as in gb25_field_stats (of the FINE interior).
+ *      gb25_get_filter_sums: each of measure, first, second may be NULL (all three: an error); only the planes asked for are
+ *      computed beyond the x pass's LDS and copied.  gb25_compute_filter_sums: the three planes one after another (measure, first,
+ *      second; dims[0] dims[1] dims[2] doubles each) in an array the model owns (with the x pass's scratch planes ONE allocation,
+ *      made by the first call, made anew when a call needs more, freed by gb25_destroy; its size is checked against the free device
+ *      memory BEFORE it is allocated: GB25_ERR_OUT_OF_MEMORY leaves nothing allocated); read-only, complete when the call returns,
+ *      valid until the next call on m.  gb25_get_derived_filter_sums: gb25_compute_derived into the model's packed array, then the
+ *      same kernels over it; the measure is that of (c,c,c), or of 2-D (c,c) for the mixed-layer depth.  GB25_D_VORTICITY lives at
+ *      (f,f,c), which has no measure in the table: GB25_ERR_INVALID_ARGUMENT.
+ *      RANKS OF A DECOMPOSITION.  A window reaches beyond the rank's columns and rows, and the halo exchanges are not widened for
+ *      it: on a rank (nranks > 1 or slab_mode = 1) the three device entries return GB25_ERR_STATE and say so.  The dims need no
+ *      device and answer there too.  gb-25_amd/distributed.py LocalSlabEnsemble.filter_sums gathers on the host.
+ *      ERRORS, each GB25_ERR_INVALID_ARGUMENT with a message that names the argument, the model stays usable: a radius that is
+ *      negative or above the maximum, 2 rx + 1 > Nx, a stride that does not divide, a window of levels outside the field, a weight
+ *      that is negative or not finite, weights that sum to zero, wx together with rx_of_row, no output requested. */
+#define GB25_FILTER_MAX_RADIUS 32
+typedef struct {
+  int32_t rx, ry;                    /* radii in grid points */
+  int32_t sx, sy;                    /* strides of the output; 1, 1: every point */
+  int32_t k_first, k_count;          /* levels of the field; k_count = -1: all from k_first on */
+  int32_t reserved;
+} gb25_filter;
+typedef struct {
+  int32_t dims[3], reserved;
+  int64_t nonfinite, empty, clipped;
+  int32_t global_offset[3], reserved2;
+} gb25_filter_info;
+int32_t gb25_filter_info_bytes(void);
+gb25_status gb25_filter_dims(const gb25_model *m, gb25_field f, const gb25_filter *filter, int32_t dims[3]);   /* needs no device */
+gb25_status gb25_derived_filter_dims(const gb25_model *m, gb25_derived q, const gb25_filter *filter, int32_t dims[3]);   /* needs no device */
+gb25_status gb25_get_filter_sums(gb25_model *m, gb25_field f, const gb25_filter *filter, const double *wx /* may be NULL */,
+                                 const double *wy /* may be NULL */, const int32_t *rx_of_row /* may be NULL */, double *measure,
+                                 double *first, double *second, gb25_filter_info *info /* may be NULL */);
+gb25_status gb25_compute_filter_sums(gb25_model *m, gb25_field f, const gb25_filter *filter, const double *wx, const double *wy,
+                                     const int32_t *rx_of_row, gb25_filter_info *info, const double **dev, int32_t device_dims[3]);
+gb25_status gb25_get_derived_filter_sums(gb25_model *m, gb25_derived q, double param, const gb25_filter *filter, const double *wx,
+                                         const double *wy, const int32_t *rx_of_row, double *measure, double *first, double *second,
+                                         gb25_filter_info *info);
+
 /* ---- time averages and eddy fluxes accumulated on the device (csrc/averages_kernels.hpp, k_averages_accumulate): what the other
  *      diagnostics cannot do -- remember something between two calls.  The time-mean state, eddy kinetic energy and tracer
  *      variance, the eddy heat and salt fluxes <v'T'>, <u'T'>, <w'T'>: Oceananigans' AveragedTimeInterval, without five parent arrays

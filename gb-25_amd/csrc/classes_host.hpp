@@ -1,6 +1,6 @@
 // classes_host.hpp -- host side of gb25_get_class_sums / gb25_class_sum_bytes (include/gb25.h); included by gb25_api.hip behind
-// diagnostics_host.hpp, whose shared helpers (diag_*) and tables (moments_tables) it uses.  Kernels: class_kernels.hpp; the memory:
-// class_sums of DiagState (diagnostics_state.hpp).  Like the other diagnostics nothing here writes model memory or a schedule
+// diagnostics_host.hpp, whose shared helpers (diag_*) and tables (moments_tables, diag_measure_tables) it uses.  Kernels:
+// class_kernels.hpp; the memory: class_sums (a result buffer) of DiagState (diagnostics_state.hpp).  Like the other diagnostics nothing here writes model memory or a schedule
 // flag: the only memory written is the records' own buffer.
 #pragma once
 
@@ -9,22 +9,17 @@ namespace {
 static_assert(sizeof(ClassPartial) == sizeof(gb25_class_sum), "a class record is a gb25_class_sum");
 static_assert(CLASS_MAX_BINS == GB25_CLASS_MAX_BINS, "the kernels' cap is the header's");
 
-// the edges (CLASS_MAX_BINS doubles), then ROWS [rows B], CUMULATIVE [rows (B + 1)] and TOTAL [B] for the tallest set of rows a
-// call can ask for (v below a wall: Ny + 1) and at least B bins
-gb25_status class_buffer(gb25_model* m, int B) {
-  if (m->diag.class_sums && (size_t)B <= m->diag.class_bins) return GB25_OK;
-  if (m->diag.class_sums) HIPCHK(hipFree(m->diag.class_sums));
-  m->diag.class_sums = nullptr;
-  const size_t rows = (size_t)m->Ny + 1, records = rows * (2 * (size_t)B + 1) + (size_t)B;
-  HIPCHK(hipMalloc(&m->diag.class_sums, CLASS_MAX_BINS * sizeof(double) + records * sizeof(ClassPartial)));
-  m->diag.class_rows = rows;
-  m->diag.class_bins = (size_t)B;
-  return GB25_OK;
+// the edges (CLASS_MAX_BINS doubles), then ROWS [rows B], CUMULATIVE [rows (B + 1)] and TOTAL [B] of the call's B bins, each with
+// room for the tallest set of rows a call can ask for (v below a wall: Ny + 1)
+inline size_t class_max_rows(const gb25_model* m) { return (size_t)m->Ny + 1; }
+gb25_status class_buffer(gb25_model* m, const char* what, int B) {
+  const size_t records = class_max_rows(m) * (2 * (size_t)B + 1) + (size_t)B;
+  return m->diag.class_sums.grow(m, what, "the class records", CLASS_MAX_BINS * sizeof(double) + records * sizeof(ClassPartial));
 }
-inline double* class_edges(gb25_model* m) { return (double*)m->diag.class_sums; }
+inline double* class_edges(gb25_model* m) { return (double*)m->diag.class_sums.p; }
 inline ClassPartial* class_rows(gb25_model* m) { return (ClassPartial*)(class_edges(m) + CLASS_MAX_BINS); }
-inline ClassPartial* class_psi(gb25_model* m) { return class_rows(m) + m->diag.class_rows * m->diag.class_bins; }
-inline ClassPartial* class_total(gb25_model* m) { return class_psi(m) + m->diag.class_rows * (m->diag.class_bins + 1); }
+inline ClassPartial* class_psi(gb25_model* m, int B) { return class_rows(m) + class_max_rows(m) * (size_t)B; }
+inline ClassPartial* class_total(gb25_model* m, int B) { return class_psi(m, B) + class_max_rows(m) * ((size_t)B + 1); }
 
 struct ClassLaunch {
   const real *v, *T, *S;
@@ -85,19 +80,16 @@ gb25_status gb25_get_class_sums(gb25_model* m, gb25_class_what what, gb25_class_
     if (gb25_status s = diag_source(m, GB25_V, &a.v)) return s;
   if (gb25_status s = diag_source(m, GB25_T, &a.T)) return s;
   if (gb25_status s = diag_source(m, GB25_S, &a.S)) return s;
-  if (gb25_status s = class_buffer(m, B)) return s;
-  if ((size_t)N > m->diag.class_rows) return fail(m, GB25_ERR_STATE, "gb25_get_class_sums: more rows than the model's buffer holds");
+  if (gb25_status s = class_buffer(m, "gb25_get_class_sums", B)) return s;
+  if ((size_t)N > class_max_rows(m)) return fail(m, GB25_ERR_STATE, "gb25_get_class_sums: more rows than the model's buffer holds");
   if (gb25_status s = wait_for_model(m)) return s;
   if (gb25_status s = moments_tables(m)) return s;
   double padded[CLASS_MAX_BINS];   // (alive until the stream is synchronised below)
   for (int e = 0; e < CLASS_MAX_BINS; e++) padded[e] = e < n_edges ? edges[e] : HUGE_VAL;
   HIPCHK(hipMemcpyAsync(class_edges(m), padded, sizeof padded, hipMemcpyHostToDevice, m->stream));
-  ClassTables tab;
-  tab.metric = faces ? m->diag.face_length[0] : m->diag.area[0];
-  tab.first = m->diag.first_wet[faces ? 2 : 0];
-  tab.eos0 = m->diag.eos0;
-  tab.edges = class_edges(m);
-  tab.pivot_row = (!faces && is_folded(m)) ? m->Ny - 1 : -1;
+  const MomentsTables measure = diag_measure_tables(m, !faces);
+  const ClassTables tab = {faces ? m->diag.face_length[0] : measure.area[0], measure.first[faces ? 2 : 0], m->diag.eos0, class_edges(m),
+                           measure.pivot_row};
   {
     Timed t(m, GB25_K_DIAGNOSTICS);
     if (faces) {
@@ -111,11 +103,11 @@ gb25_status gb25_get_class_sums(gb25_model* m, gb25_class_what what, gb25_class_
     if (shape != GB25_CL_ROWS) {
       const int most = std::max(N, B);
       hipLaunchKernelGGL(k_class_fold, dim3((most + 63) / 64), dim3(64), 0, m->stream, (const ClassPartial*)class_rows(m), N, B,
-                         class_psi(m), class_total(m));
+                         class_psi(m, B), class_total(m, B));
       LAUNCHCHK();
     }
   }
-  const ClassPartial* from = shape == GB25_CL_ROWS ? class_rows(m) : shape == GB25_CL_ROWS_CUMULATIVE ? class_psi(m) : class_total(m);
+  const ClassPartial* from = shape == GB25_CL_ROWS ? class_rows(m) : shape == GB25_CL_ROWS_CUMULATIVE ? class_psi(m, B) : class_total(m, B);
   return diag_download(m, out, from, (size_t)count * sizeof(gb25_class_sum));
 }
 

@@ -4,7 +4,11 @@
 // diagnostics_kernels.hpp; the memory: DiagState (diagnostics_state.hpp), m->diag.  Nothing here writes model memory or a schedule
 // flag: the calls may sit between any two steps.  The first section holds what every diagnostic shares, averages_host.hpp,
 // classes_host.hpp and particles_host.hpp included: diag_need_device, diag_window, diag_download, diag_upload, diag_room_for /
-// diag_alloc_zeroed, diag_source; wait_for_model: gb25_api.hip (is_folded, has_north_wall and first_wet_level: gb25_api.hip, beside is_2d).
+// diag_malloc / diag_alloc_zeroed, DiagBuffer::grow, diag_source; wait_for_model: gb25_api.hip (is_folded, has_north_wall and
+// first_wet_level: gb25_api.hip, beside is_2d).  Three more pieces are written ONCE here for the families that reduce a field or a
+// derived field (integrals, block sums, filters, spectra; DESIGN.md, "The host layer of the diagnostics"): the measure of a
+// launch (diag_measure_tables, diag_with_loc), what a call reads (DiagSource: diag_source_plan without the device,
+// diag_source_resolve with it), and the copy of planes and counts to the host (diag_download_planes).
 #pragma once
 
 namespace {
@@ -47,19 +51,32 @@ gb25_status diag_room_for(gb25_model* m, const char* what, const char* of, doubl
   if (need > (double)free_bytes) return fail(m, GB25_ERR_OUT_OF_MEMORY, "%s: %s need %.0f bytes, the device has %zu free", what, of, need, free_bytes);
   return GB25_OK;
 }
-// ... and then made and zeroed; a failure leaves nothing allocated
-gb25_status diag_alloc_zeroed(gb25_model* m, const char* what, const char* of, size_t bytes, void** base) {
+// ... and then made: a failure is out of memory, not a HIP error that sticks, and leaves nothing allocated
+gb25_status diag_malloc(gb25_model* m, const char* what, const char* of, size_t bytes, void** base) {
   const hipError_t e = hipMalloc(base, bytes);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    *base = nullptr;
-    return fail(m, GB25_ERR_OUT_OF_MEMORY, "%s: hipMalloc of %zu bytes for %s failed: %s", what, bytes, of, hipGetErrorString(e));
-  }
+  if (e == hipSuccess) return GB25_OK;
+  (void)hipGetLastError();
+  *base = nullptr;
+  return fail(m, GB25_ERR_OUT_OF_MEMORY, "%s: hipMalloc of %zu bytes for %s failed: %s", what, bytes, of, hipGetErrorString(e));
+}
+// ... and zeroed
+gb25_status diag_alloc_zeroed(gb25_model* m, const char* what, const char* of, size_t bytes, void** base) {
+  if (gb25_status s = diag_malloc(m, what, of, bytes, base)) return s;
   if (hipMemsetAsync(*base, 0, bytes, m->stream) != hipSuccess || hipStreamSynchronize(m->stream) != hipSuccess) {
     (void)hipFree(*base);
     *base = nullptr;
     return fail(m, GB25_ERR_HIP, "%s: zeroing %s failed: %s", what, of, hipGetErrorString(hipGetLastError()));
   }
+  return GB25_OK;
+}
+
+// a result buffer (diagnostics_state.hpp) with room for `need` bytes: the one it has, or a new one
+gb25_status DiagBuffer::grow(gb25_model* m, const char* what, const char* of, size_t need) {
+  if (p && need <= bytes) return GB25_OK;
+  drop();
+  if (gb25_status s = diag_room_for(m, what, of, (double)need)) return s;
+  if (gb25_status s = diag_malloc(m, what, of, need, &p)) return s;
+  bytes = need;
   return GB25_OK;
 }
 
@@ -262,29 +279,40 @@ gb25_status moments_check_box(gb25_model* m, const DiagBox& b) {
   return GB25_OK;
 }
 
-template <int LOC>
-void moments_launch_loc(gb25_model* m, const MomentsTables& tab, const real* src, const DiagBox& b, MomentsPartial* rows) {
-  const long long nb = ((long long)b.by * b.bz + DIAG_THREADS / 64 - 1) / (DIAG_THREADS / 64);
-  hipLaunchKernelGGL((k_field_moments<real, LOC>), dim3((unsigned)nb), dim3(DIAG_THREADS), 0, m->stream, m->g, tab, src, b, rows);
-}
-// the row records of field id into slot `slot`
-gb25_status moments_launch(gb25_model* m, gb25_field id, const real* src, const DiagBox& b, int slot) {
+// What a kernel reads of them (moments_tables has run): the areas and the first wet levels by horizontal location, and the local
+// row of the pivot row of a folded grid.  fold_applies: the points of the launch lie ON that row (cells, x faces) -- the y faces
+// of the transports and of the class sums do not, and pass false.  (TransportTables and ClassTables take their parts from it.)
+MomentsTables diag_measure_tables(const gb25_model* m, bool fold_applies) {
   MomentsTables tab;
   for (int q = 0; q < 3; q++) {
     tab.area[q] = m->diag.area[q];
     tab.first[q] = m->diag.first_wet[q];
   }
-  tab.pivot_row = is_folded(m) ? m->Ny - 1 : -1;
-  MomentsPartial* rows = moments_rows(m, slot);
-  switch (moments_loc(id)) {
-    case LOC_CCC: moments_launch_loc<LOC_CCC>(m, tab, src, b, rows); break;
-    case LOC_FCC: moments_launch_loc<LOC_FCC>(m, tab, src, b, rows); break;
-    case LOC_CFC: moments_launch_loc<LOC_CFC>(m, tab, src, b, rows); break;
-    case LOC_CCF: moments_launch_loc<LOC_CCF>(m, tab, src, b, rows); break;
-    case LOC_CC: moments_launch_loc<LOC_CC>(m, tab, src, b, rows); break;
-    case LOC_FC: moments_launch_loc<LOC_FC>(m, tab, src, b, rows); break;
-    case LOC_CF: moments_launch_loc<LOC_CF>(m, tab, src, b, rows); break;
+  tab.pivot_row = (fold_applies && is_folded(m)) ? m->Ny - 1 : -1;
+  return tab;
+}
+// f(std::integral_constant<int, LOC>) for the location loc: how a MomentLoc becomes the template argument of a kernel
+template <class F>
+void diag_with_loc(MomentLoc loc, F&& f) {
+  switch (loc) {
+    case LOC_CCC: f(std::integral_constant<int, LOC_CCC>()); break;
+    case LOC_FCC: f(std::integral_constant<int, LOC_FCC>()); break;
+    case LOC_CFC: f(std::integral_constant<int, LOC_CFC>()); break;
+    case LOC_CCF: f(std::integral_constant<int, LOC_CCF>()); break;
+    case LOC_CC: f(std::integral_constant<int, LOC_CC>()); break;
+    case LOC_FC: f(std::integral_constant<int, LOC_FC>()); break;
+    case LOC_CF: f(std::integral_constant<int, LOC_CF>()); break;
   }
+}
+
+// the row records of field id into slot `slot`
+gb25_status moments_launch(gb25_model* m, gb25_field id, const real* src, const DiagBox& b, int slot) {
+  const MomentsTables tab = diag_measure_tables(m, true);
+  MomentsPartial* rows = moments_rows(m, slot);
+  const long long nb = ((long long)b.by * b.bz + DIAG_THREADS / 64 - 1) / (DIAG_THREADS / 64);
+  diag_with_loc(moments_loc(id), [&](auto loc) {
+    hipLaunchKernelGGL((k_field_moments<real, decltype(loc)::value>), dim3((unsigned)nb), dim3(DIAG_THREADS), 0, m->stream, m->g, tab, src, b, rows);
+  });
   LAUNCHCHK();
   return GB25_OK;
 }
@@ -393,6 +421,74 @@ gb25_status derived_window_run(gb25_model* m, const char* what, gb25_derived q, 
   return GB25_OK;
 }
 
+// ---- what a call reads: a field of the model, or a derived field with its parameter (block sums, filters, spectra)
+struct DiagSource {
+  bool is_derived;
+  gb25_field field;
+  gb25_derived derived;
+  double param;
+  DiagSource(gb25_field f) : is_derived(false), field(f), derived(GB25_D_VORTICITY), param(0.0) {}
+  DiagSource(gb25_derived q, double par) : is_derived(true), field(GB25_T), derived(q), param(par) {}
+};
+// what its plan says without the device: the interior extents of the source itself (columns; ITS rows -- a y-face field and the
+// vorticity have one more than the cells below a wall --; its levels) and where its measure lives
+struct SourcePlan {
+  int32_t dims[3];
+  MomentLoc loc;   // (of GB25_D_VORTICITY, at (f,f,c): none -- diag_source_measured)
+};
+// The checks of the source that need no device -- the id, "this model has no such field", the parameter -- and its plan
+gb25_status diag_source_plan(gb25_model* m, const char* what, const DiagSource& S, SourcePlan* P) {
+  if (S.is_derived) {
+    if (gb25_status s = derived_check(m, what, S.derived, S.param)) return s;
+    derived_extents(m, S.derived, P->dims);
+    P->loc = S.derived == GB25_D_MIXED_LAYER_DEPTH ? LOC_CC : LOC_CCC;
+    return GB25_OK;
+  }
+  const gb25_field f = S.field;
+  if (f < 0 || f >= GB25_FIELD_COUNT) return fail(m, GB25_ERR_INVALID_ARGUMENT, "%s: no field %d", what, (int)f);
+  if (m->own_stream && !m->f[f].d)
+    return fail(m, GB25_ERR_INVALID_ARGUMENT, "%s: this model has no such field (closure = CATKEVerticalDiffusivity() only)", what);
+  // (from the configuration alone, what gb25_field_dims says of the interior)
+  P->loc = moments_loc(f);
+  P->dims[0] = m->Nx;
+  P->dims[1] = m->Ny + ((is_v_shaped(f) && has_north_wall(m)) ? 1 : 0);
+  P->dims[2] = P->loc >= LOC_CC ? 1 : m->cfg.Nz + (P->loc == LOC_CCF ? 1 : 0);
+  return GB25_OK;
+}
+// ... for the families that weigh with the measure (not the spectra): every source but one has it
+gb25_status diag_source_measured(gb25_model* m, const char* what, const DiagSource& S) {
+  if (S.is_derived && S.derived == GB25_D_VORTICITY)
+    return fail(m, GB25_ERR_INVALID_ARGUMENT, "%s: derived GB25_D_VORTICITY lives at (f,f,c), for which the measure is not defined", what);
+  return GB25_OK;
+}
+// The source on the device, levels [k_first, k_first + kc) of it: *src and the box whose origin is element (0, 0, k_first).  A
+// field is read where it lies (diag_source), in its parent's pitch and plane, all its levels behind the origin, once the model
+// has been waited for; a derived field is gb25_compute_derived's launches on m->stream behind the model (derived_run) into the
+// model's packed array, which holds the kc levels of the window alone.
+gb25_status diag_source_resolve(gb25_model* m, const DiagSource& S, const SourcePlan& P, int k_first, int kc, const real** src, DiagBox* b) {
+  if (S.is_derived) {
+    if (gb25_status s = derived_run(m, S.derived, S.param, k_first, kc, src)) return s;
+    *b = DiagBox{P.dims[0], P.dims[1], kc, (long long)P.dims[0], (long long)P.dims[0] * P.dims[1], 0};
+    return GB25_OK;
+  }
+  if (gb25_status s = diag_source(m, S.field, src)) return s;
+  if (gb25_status s = diag_box(m, S.field, 0, b)) return s;
+  if (gb25_status s = wait_for_model(m)) return s;
+  b->origin += b->plane * k_first;
+  return GB25_OK;
+}
+
+// ---- planes and counts (block sums, filters): the counts' slot in front of a family's buffer, and the way to the host
+constexpr size_t COUNTS_HEAD = 32;   // bytes: BlockCounts, padded
+static_assert(sizeof(BlockCounts) <= COUNTS_HEAD, "the counts fit their slot");
+// those of the planes measure | first | second (elems doubles each, one after another from `planes`) that host[] asks for,
+// then the counts: behind the launches, and the stream is quiet when it returns
+gb25_status diag_download_planes(gb25_model* m, double* const host[3], const double* planes, size_t elems, const BlockCounts* counts, BlockCounts* c) {
+  for (int q = 0; q < 3; q++)
+    if (host[q]) HIPCHK(hipMemcpyAsync(host[q], planes + q * elems, elems * sizeof(double), hipMemcpyDeviceToHost, m->stream));
+  return diag_download(m, c, counts, sizeof *c);
+}
+
 // ---- transports
 static_assert(sizeof(TransportPartial) == sizeof(gb25_transport), "a line record is a gb25_transport");
 
@@ -444,10 +540,8 @@ gb25_status gb25_get_transport(gb25_model* m, gb25_transport_faces faces, gb25_t
   if (gb25_status s = wait_for_model(m)) return s;
   if (gb25_status s = moments_tables(m)) return s;
   const Grid& g = m->g;
-  TransportTables tab;
-  tab.length = m->diag.face_length[ay ? 0 : 1];
-  tab.first = m->diag.first_wet[ay ? 2 : 1];
-  tab.pivot_row = (!ay && is_folded(m)) ? m->Ny - 1 : -1;
+  const MomentsTables measure = diag_measure_tables(m, !ay);
+  const TransportTables tab = {m->diag.face_length[ay ? 0 : 1], measure.first[ay ? 2 : 1], measure.pivot_row};
   TransportPartial* lines = transport_lines(m);
   {
     Timed t(m, GB25_K_DIAGNOSTICS);

@@ -11,6 +11,23 @@
 
 namespace {
 
+// The results of ONE call of a family whose results grow with what the caller asks for: one allocation, made by the first call,
+// made anew (nothing is kept) when a call needs more bytes than it holds.  A call never has less room than it asked for, and it
+// finds its parts at offsets it computes from its OWN arguments, whatever else the buffer has room for.  grow() refuses before
+// hipMalloc what the device has no room for (diag_room_for) and reports a failed hipMalloc as GB25_ERR_OUT_OF_MEMORY with the
+// runtime's sticky error cleared; after either the buffer holds nothing.  (Defined in diagnostics_host.hpp: it reports through
+// fail.)  The members of DiagState of this type are "a result buffer" below.
+struct DiagBuffer {
+  void* p = nullptr;
+  size_t bytes = 0;
+  void drop() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+  gb25_status grow(gb25_model* m, const char* what, const char* of, size_t need);
+};
+
 struct DiagState {
   // field statistics (gb25_get_field_stats, gb25_compare_field, gb25_get_state_monitor): the per-block records of the reduction
   // kernels and the seven result records of a state monitor, one allocation made by the first call that needs it
@@ -42,45 +59,36 @@ struct DiagState {
   // transports (gb25_get_transport): the LINES, running sums and PROFILE records of one call, made by the first call
   void* transport = nullptr;
   size_t transport_lines = 0;
-  // class sums (gb25_get_class_sums): the padded edges, then the ROWS, CUMULATIVE and TOTAL records of one call; made by the
-  // first call, made anew when a call needs more bins
-  void* class_sums = nullptr;
-  size_t class_rows = 0, class_bins = 0;
-  // zonal spectra (gb25_get_zonal_spectrum, gb25_get_derived_zonal_spectrum): the count of skipped lines, then the coefficients of
-  // one call; made by the first call, made anew when a call needs more records.  The host word that count is copied into.  The
-  // interleaved copy of the table of the definition on the device (one of diagnostics' own tables: dropped with them, made anew
-  // after a rebuild of the grid); k_zonal_spectrum's dynamic-LDS attribute (only the instance with the table in LDS can pass
-  // 64 KB), per model as the others
-  void* spectrum = nullptr;
-  size_t spectrum_records = 0;
+  // class sums (gb25_get_class_sums): a result buffer -- the padded edges, then the ROWS, CUMULATIVE and TOTAL records of one call
+  DiagBuffer class_sums;
+  // zonal spectra (gb25_get_zonal_spectrum, gb25_get_derived_zonal_spectrum): a result buffer -- the count of skipped lines, then
+  // the coefficients of one call.  The host word that count is copied into.  The interleaved copy of the table of the definition
+  // on the device (one of diagnostics' own tables: dropped with them, made anew after a rebuild of the grid); k_zonal_spectrum's
+  // dynamic-LDS attribute (only the instance with the table in LDS can pass 64 KB), per model as the others
+  DiagBuffer spectrum;
   unsigned spec_skipped = 0;
   double* spec_table = nullptr;
   bool spec_valid = false, spec_lds_raised = false;
-  // fields on surfaces (gb25_compute_on_surfaces, gb25_get_on_surfaces): ONE allocation -- the padded targets (SURF_MAX doubles),
-  // then the values and the status bytes of one call --, made by the first call, made anew when a call asks for more values.
-  // The host copy of the padded targets the upload reads (a word of the model: no copy is ever pending from a frame that has
-  // returned)
-  void* surfaces = nullptr;
-  size_t surf_values = 0;
+  // fields on surfaces (gb25_compute_on_surfaces, gb25_get_on_surfaces): a result buffer -- the padded targets (SURF_MAX
+  // doubles), then the values and the status bytes of one call.  The host copy of the padded targets the upload reads (a word of
+  // the model: no copy is ever pending from a frame that has returned)
+  DiagBuffer surfaces;
   double surf_targets[gb25::SURF_MAX] = {};
   // stability diagnostics (gb25_compute_stability, gb25_get_stability): the packed result array, room for Nx x Ny x (Nz + 1)
-  // values, made by the first call
+  // values, made by the first call (ONE size per model, nothing grows: no result buffer)
   gb25::real* stability = nullptr;
-  // block sums (gb25_get_block_sums, gb25_compute_block_sums, gb25_get_derived_block_sums): ONE allocation -- the three counts of
+  // block sums (gb25_get_block_sums, gb25_compute_block_sums, gb25_get_derived_block_sums): a result buffer -- the three counts of
   // the info record (BlockCounts, padded to 32 bytes), the level weights (Nz + 1 doubles), the planes measure | first | second
-  // of one call, then the count slots of the waves of its launch --, made by the first call, made anew when a call needs more
-  // bytes.  The host copy of the weights the upload reads (a word of the model: no copy is ever pending from a frame that has
-  // returned)
-  void* blocks = nullptr;
-  size_t block_bytes = 0;
+  // of one call, then the count slots of the waves of its launch.  The host copy of the weights the upload reads (a word of the
+  // model: no copy is ever pending from a frame that has returned)
+  DiagBuffer blocks;
   std::vector<double> block_weights;
-  // moving-window filter (gb25_get_filter_sums, gb25_compute_filter_sums, gb25_get_derived_filter_sums): ONE allocation -- the
+  // moving-window filter (gb25_get_filter_sums, gb25_compute_filter_sums, gb25_get_derived_filter_sums): a result buffer -- the
   // counts of the info record (BlockCounts, padded to 32 bytes), the weights wx and wy (2 x 65 doubles), the radius of every row
   // (Ny int32), the planes measure | first | second of one call, the x pass's scratch planes, then the count slots of the waves
-  // of its two launches --, made by the first call, made anew when a call needs more bytes.  The host copies the uploads read
-  // (words of the model: no copy is ever pending from a frame that has returned)
-  void* filters = nullptr;
-  size_t filter_bytes = 0;
+  // of its two launches.  The host copies the uploads read (words of the model: no copy is ever pending from a frame that has
+  // returned)
+  DiagBuffer filters;
   std::vector<double> filter_wx, filter_wy;
   std::vector<int32_t> filter_rows;
   // time averages (gb25_averages_*): the accumulators of the active groups and the array a normalized read-out is divided into
@@ -146,14 +154,8 @@ struct DiagState {
     drop(moments);
     drop(derived);
     drop(transport);
-    drop(class_sums);
-    drop(spectrum);
-    drop(surfaces);
     drop(stability);
-    drop(blocks);
-    block_bytes = 0;
-    drop(filters);
-    filter_bytes = 0;
+    for (DiagBuffer* b : {&class_sums, &spectrum, &surfaces, &blocks, &filters}) b->drop();
     release_tables();
     release_averages();
     release_particles();

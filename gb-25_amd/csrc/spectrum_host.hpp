@@ -1,7 +1,7 @@
 // spectrum_host.hpp -- host side of gb25_get_spectrum_table / gb25_get_zonal_spectrum / gb25_get_derived_zonal_spectrum /
 // gb25_spectral_coefficient_bytes (include/gb25.h); included by gb25_api.hip behind diagnostics_host.hpp, whose shared helpers
-// (diag_*) and derived fields (derived_run) it uses.  Kernel: spectrum_kernels.hpp; the memory: spec_* of DiagState
-// (diagnostics_state.hpp).  Like the other diagnostics nothing here writes model memory or a schedule flag: the only memory
+// (diag_*) and sources (DiagSource: a spectrum weighs with no measure, so every source has one, the vorticity too) it uses.
+// Kernel: spectrum_kernels.hpp; the memory: spectrum (a result buffer), spec_* of DiagState (diagnostics_state.hpp).  Like the other diagnostics nothing here writes model memory or a schedule flag: the only memory
 // written is the records' own buffer.
 #pragma once
 
@@ -33,19 +33,6 @@ gb25_status spectrum_table(gb25_model* m) {
   return GB25_OK;
 }
 
-// the count, then room for `records` coefficients; made by the first call, made anew when a call asks for more
-gb25_status spectrum_buffer(gb25_model* m, const char* what, size_t records) {
-  DiagState& D = m->diag;
-  if (D.spectrum && records <= D.spectrum_records) return GB25_OK;
-  D.drop(D.spectrum);
-  D.spectrum_records = 0;
-  const size_t bytes = SPEC_HEAD + records * sizeof(SpecCoef);
-  if (gb25_status s = diag_room_for(m, what, "the coefficients", (double)bytes)) return s;
-  HIPCHK(hipMalloc(&D.spectrum, bytes));
-  D.spectrum_records = records;
-  return GB25_OK;
-}
-
 // how a block is cut (spectrum_kernels.hpp): lanes per line, lines per wave, columns per chunk
 SpecShape spectrum_shape(const gb25_model* m, int m_first, int mc, int bx) {
   SpecShape S = {};
@@ -61,11 +48,12 @@ SpecShape spectrum_shape(const gb25_model* m, int m_first, int mc, int bx) {
   return S;
 }
 
-// What the two entry points share once the source lies on the device: the buffer, the table, the launch, the copies.
+// What the sources share once they lie on the device: the buffer (the count, then the coefficients), the table, the launch, the
+// copies.
 gb25_status spectrum_run(gb25_model* m, const char* what, const real* src, const SpecLines& L, int m_first, int mc,
                          gb25_spectral_coefficient* out, int64_t* nonfinite_lines) {
   const size_t records = (size_t)L.by * L.kc * mc;
-  if (gb25_status s = spectrum_buffer(m, what, records)) return s;
+  if (gb25_status s = m->diag.spectrum.grow(m, what, "the coefficients", SPEC_HEAD + records * sizeof(SpecCoef))) return s;
   if (gb25_status s = wait_for_model(m)) return s;
   if (gb25_status s = spectrum_table(m)) return s;
   const SpecShape S = spectrum_shape(m, m_first, mc, L.bx);
@@ -79,8 +67,8 @@ gb25_status spectrum_run(gb25_model* m, const char* what, const real* src, const
     HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPEC_LDS_LIMIT));
     m->diag.spec_lds_raised = true;
   }
-  unsigned* bad = (unsigned*)m->diag.spectrum;
-  SpecCoef* rec = (SpecCoef*)((char*)m->diag.spectrum + SPEC_HEAD);
+  unsigned* bad = (unsigned*)m->diag.spectrum.p;
+  SpecCoef* rec = (SpecCoef*)((char*)m->diag.spectrum.p + SPEC_HEAD);
   const long long nlines = (long long)L.by * L.kc;
   HIPCHK(hipMemsetAsync(bad, 0, SPEC_HEAD, m->stream));
   {
@@ -108,6 +96,20 @@ gb25_status spectrum_windows(gb25_model* m, const char* what, int32_t m_first, i
   return GB25_OK;
 }
 
+// the windows over the source's own rows and levels, the source, the launch (its plan P: the entry points make it, each where
+// its checks have always stood)
+gb25_status spectrum_of(gb25_model* m, const char* what, const DiagSource& S, const SourcePlan& P, int32_t m_first, int32_t m_count,
+                        int32_t k_first, int32_t k_count, gb25_spectral_coefficient* out, int64_t count, int64_t* nonfinite_lines) {
+  int mc = 0, kc = 0;
+  if (gb25_status s = spectrum_windows(m, what, m_first, m_count, k_first, k_count, P.dims[1], P.dims[2], count, &mc, &kc)) return s;
+  if (gb25_status s = diag_need_device(m, what)) return s;
+  const real* src = nullptr;
+  DiagBox b;
+  if (gb25_status s = diag_source_resolve(m, S, P, k_first, kc, &src, &b)) return s;
+  const SpecLines L = {b.origin, b.pitch, b.plane, b.bx, b.by, kc};
+  return spectrum_run(m, what, src, L, m_first, mc, out, nonfinite_lines);
+}
+
 }  // namespace
 
 extern "C" {
@@ -125,19 +127,13 @@ gb25_status gb25_get_zonal_spectrum(gb25_model* m, gb25_field f, int32_t m_first
                                     gb25_spectral_coefficient* out, int64_t count, int64_t* nonfinite_lines) {
   if (!m) return GB25_ERR_INVALID_ARGUMENT;
   const char* what = "gb25_get_zonal_spectrum";
-  if (f < 0 || f >= GB25_FIELD_COUNT) return fail(m, GB25_ERR_INVALID_ARGUMENT, "%s: no field %d", what, (int)f);
+  const DiagSource S(f);
+  SourcePlan P;
+  if (gb25_status s = diag_source_plan(m, what, S, &P)) return s;
   if (!out) return fail(m, GB25_ERR_INVALID_ARGUMENT, "%s: out is NULL", what);
   int32_t d[3];
-  if (gb25_field_dims(m, f, 0, d)) return GB25_ERR_INVALID_ARGUMENT;
-  int mc = 0, kc = 0;
-  if (gb25_status s = spectrum_windows(m, what, m_first, m_count, k_first, k_count, d[1], d[2], count, &mc, &kc)) return s;
-  if (gb25_status s = diag_need_device(m, what)) return s;
-  const real* src = nullptr;
-  DiagBox b;
-  if (gb25_status s = diag_source(m, f, &src)) return s;
-  if (gb25_status s = diag_box(m, f, 0, &b)) return s;
-  const SpecLines L = {b.origin + b.plane * k_first, b.pitch, b.plane, b.bx, b.by, kc};
-  return spectrum_run(m, what, src, L, m_first, mc, out, nonfinite_lines);
+  if (gb25_field_dims(m, f, 0, d)) return GB25_ERR_INVALID_ARGUMENT;   // (a handle without a device has no fields: refused as ever, without a text)
+  return spectrum_of(m, what, S, P, m_first, m_count, k_first, k_count, out, count, nonfinite_lines);
 }
 
 gb25_status gb25_get_derived_zonal_spectrum(gb25_model* m, gb25_derived q, double param, int32_t m_first, int32_t m_count,
@@ -146,16 +142,10 @@ gb25_status gb25_get_derived_zonal_spectrum(gb25_model* m, gb25_derived q, doubl
   if (!m) return GB25_ERR_INVALID_ARGUMENT;
   const char* what = "gb25_get_derived_zonal_spectrum";
   if (!out) return fail(m, GB25_ERR_INVALID_ARGUMENT, "%s: out is NULL", what);
-  if (gb25_status s = derived_check(m, what, q, param)) return s;
-  int32_t e[3];
-  derived_extents(m, q, e);
-  int mc = 0, kc = 0;
-  if (gb25_status s = spectrum_windows(m, what, m_first, m_count, k_first, k_count, e[1], e[2], count, &mc, &kc)) return s;
-  if (gb25_status s = diag_need_device(m, what)) return s;
-  const real* src = nullptr;
-  if (gb25_status s = derived_run(m, q, param, k_first, kc, &src)) return s;
-  const SpecLines L = {0, (long long)e[0], (long long)e[0] * e[1], e[0], e[1], kc};   // (packed: the levels of the window alone)
-  return spectrum_run(m, what, src, L, m_first, mc, out, nonfinite_lines);
+  const DiagSource S(q, param);
+  SourcePlan P;
+  if (gb25_status s = diag_source_plan(m, what, S, &P)) return s;
+  return spectrum_of(m, what, S, P, m_first, m_count, k_first, k_count, out, count, nonfinite_lines);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // surfaces_host.hpp -- host side of gb25_compute_on_surfaces / gb25_get_on_surfaces (include/gb25.h); included by gb25_api.hip
 // behind diagnostics_host.hpp, whose shared helpers (diag_*) and tables (moments_tables: first wet levels, (double) zc | zf) it
-// uses.  Kernel: surface_kernels.hpp; the memory: surfaces, surf_* of DiagState (diagnostics_state.hpp).  Like the other
+// uses.  Kernel: surface_kernels.hpp; the memory: surfaces (a result buffer), surf_targets of DiagState (diagnostics_state.hpp).  Like the other
 // diagnostics nothing here writes model memory or a schedule flag: the only memory written is the results' own buffer.
 #pragma once
 
@@ -17,20 +17,12 @@ static_assert((int)SC_DEPTH == (int)GB25_SC_DEPTH && (int)SC_T == (int)GB25_SC_T
 static_assert((int)SURF_FOUND == (int)GB25_SURF_FOUND && (int)SURF_OUTCROP == (int)GB25_SURF_OUTCROP && (int)SURF_GROUNDED == (int)GB25_SURF_GROUNDED &&
                   (int)SURF_DRY == (int)GB25_SURF_DRY, "status bytes");
 
-// the padded targets, then the values [Nx Ny n] and the status bytes [Nx Ny n]; made by the first call, made anew when a call
-// asks for more values
+// the padded targets, then the values [Nx Ny n] and the status bytes [Nx Ny n]
 gb25_status surfaces_buffer(gb25_model* m, const char* what, int n) {
-  DiagState& D = m->diag;
-  if (D.surfaces && (size_t)n <= D.surf_values) return GB25_OK;
-  D.drop(D.surfaces);
-  D.surf_values = 0;
-  const size_t elems = (size_t)m->Nx * m->Ny * n, bytes = SURF_MAX * sizeof(double) + elems * (sizeof(real) + 1);
-  if (gb25_status s = diag_room_for(m, what, "the values and status bytes", (double)bytes)) return s;
-  HIPCHK(hipMalloc(&D.surfaces, bytes));
-  D.surf_values = (size_t)n;
-  return GB25_OK;
+  const size_t elems = (size_t)m->Nx * m->Ny * n;
+  return m->diag.surfaces.grow(m, what, "the values and status bytes", SURF_MAX * sizeof(double) + elems * (sizeof(real) + 1));
 }
-inline double* surfaces_targets(gb25_model* m) { return (double*)m->diag.surfaces; }
+inline double* surfaces_targets(gb25_model* m) { return (double*)m->diag.surfaces.p; }
 // (the status bytes lie behind the values of the CALL's n: the two arrays are packed, whatever the buffer has room for)
 inline real* surfaces_values(gb25_model* m) { return (real*)(surfaces_targets(m) + SURF_MAX); }
 

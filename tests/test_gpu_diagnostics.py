@@ -280,6 +280,46 @@ def test_repeatable_to_the_last_bit(float_type, grid_type):
     m2.backend.close()
 
 
+def blob(result):
+    """Every array and number of a result, as bytes."""
+    if isinstance(result, (tuple, list)):
+        return b"|".join(blob(r) for r in result)
+    if result is None or isinstance(result, (int, float)):
+        return repr(result).encode()
+    if isinstance(result, np.ndarray):
+        return np.ascontiguousarray(result).tobytes()
+    return blob([result.measure, result.first, result.second] + list(result.info.values()))      # (BlockSums, FilterSums)
+
+
+@pytest.mark.parametrize("float_type,grid_type", [("Float32", 0), ("Float64", 4)])
+def test_a_buffer_that_grows_and_is_reused(float_type, grid_type):
+    """The families whose results grow with the request keep ONE allocation each, made anew when a call needs more bytes: a small
+    request, one that needs more, the small one again.  The small results are the same bytes before and after the growth (a call
+    finds its parts at offsets of its own, whatever the buffer has room for), and the large one is what a fresh model gives,
+    whose buffer was made for exactly that request."""
+    m, fresh = stepped_model(float_type, grid_type), stepped_model(float_type, grid_type)
+    b, f = m.backend, fresh.backend
+    Nx, Ny, Nz = size_of(grid_type)
+    T = b.get_field("T", False)
+    targets = np.linspace(float(T.min()), float(T.max()), 10)[1:9]
+    edges = lambda n: np.linspace(float(T.min()), float(T.max()), n + 2)[1:-1]
+    families = {
+        "block sums": (lambda k: k.block_sums("T", (8, 8, Nz)), lambda k: k.block_sums("T", (1, 1, 1))),
+        "filter sums": (lambda k: k.filter_sums("T", (1, 1), (8, 8), (0, 1), planes=("first",)), lambda k: k.filter_sums("T", (2, 3))),
+        "zonal spectrum": (lambda k: k.zonal_spectrum("T", (0, 2), (0, 1)), lambda k: k.zonal_spectrum("T")),
+        "on surfaces": (lambda k: k.get_on_surfaces("T", "depth", targets[:1]), lambda k: k.get_on_surfaces("T", "depth", targets)),
+        "class sums": (lambda k: k.class_sums("cells", "T", edges(3), "cumulative"), lambda k: k.class_sums("cells", "T", edges(63), "cumulative")),
+    }
+    for name, (small, large) in families.items():
+        first, second, third = blob(small(b)), blob(large(b)), blob(small(b))
+        assert len(second) > len(first) > 0, name
+        assert first == third, name
+        assert second == blob(large(f)), name
+        assert any(first) and any(second), name
+    b.close()
+    f.close()
+
+
 @pytest.mark.parametrize("float_type,grid_type", [("Float32", 0), ("Float64", 0), ("Float32", 4), ("Float64", 4)])
 def test_advective_cfl(float_type, grid_type):
     """max over the interior cells of |u|/dx + |v|/dy + |w|/dz, restated from the fields and the metric getters."""

@@ -21,6 +21,7 @@
 #include "validity.hpp"
 #include "step_route.hpp"
 #include "subcycle_plan.hpp"
+#include "model_layout.hpp"
 
 #include <cmath>
 #include <cstdarg>
@@ -92,12 +93,13 @@ struct DeviceBlocks {
 
 struct gb25_model {
   gb25_config cfg;
-  int Nx = 0;  // local slab width
-  // 2-D (x, y) decomposition, Partition(Rx, Ry, 1) of the reference (sharding/sharded_baroclinic_instability_simulation_run.jl:
-  // 65-72): rank = ry Rx + rx owns the columns [rx Nx, (rx + 1) Nx) and the rows [j0, j0 + Ny) of the global grid.  Ry = 1: x slabs.
-  int Ny = 0;  // local rows (cfg.Ny / Ry)
+  // What plan_layout (model_layout.hpp) decided at creation, never changed afterwards: the argument of parent_dims and its kin.  The
+  // members below that carry a name of the layout (Nx .. yn_open, slab, Ns, dtau_frac, weights, W, Wy, Wys, tracer_rows_forced) are
+  // copies of it, made by adopt_layout and nowhere else; so are the starting values of the options it has a default for.
+  ModelLayout layout;
+  int Nx = 0, Ny = 0;  // local slab width and rows
   int Rx = 1, Ry = 1, rx = 0, ry = 0, j0 = 0;
-  bool ys_open = false, yn_open = false;   // a southern / northern neighbour rank exists (no wall on that side)
+  bool ys_open = false, yn_open = false;
   Grid g;
   Field f[GB25_FIELD_COUNT];
   Field pp[3];                   // ping-pong partners of eta, U, V
@@ -293,16 +295,9 @@ gb25_status fail(gb25_model* m, gb25_status s, const char* fmt, ...) {
   if (!(m)) return GB25_ERR_INVALID_ARGUMENT
 #define LAUNCHCHK() HIPCHK(hipGetLastError())
 
-bool is_v_shaped(int id) {
-  return id == GB25_V || id == GB25_GN_V || id == GB25_GM_V || id == GB25_BT_V || id == GB25_V_BAR ||
-         id == GB25_GN_BT_V || id == GB25_PREV_V;
-}
-bool is_2d(int id) { return (id >= GB25_ETA && id <= GB25_GN_BT_V) || id == GB25_JB; }
-bool is_catke_field(int id) { return id >= GB25_E && id <= GB25_PREV_V; }
-// The northern edge of this rank: the fold of a tripolar grid (the top row of ranks only), a wall (v has a row Ny), or -- neither
-// of the two -- a neighbour rank.
-inline bool is_folded(const gb25_model* m) { return m->cfg.grid_type >= GB25_GRID_TRIPOLAR && !m->yn_open; }
-inline bool has_north_wall(const gb25_model* m) { return m->cfg.grid_type < GB25_GRID_TRIPOLAR && !m->yn_open; }
+// (is_v_shaped, is_2d, is_catke_field: model_layout.hpp, over its table of field shapes)
+inline bool is_folded(const gb25_model* m) { return m->layout.north_fold; }
+inline bool has_north_wall(const gb25_model* m) { return m->layout.north_wall; }
 // First wet level (= number of immersed cells) of LOCAL column (i, j) on the host; 0 without a bottom table.  Rows beyond a global
 // wall read the wall's row, rows beyond the rank read a neighbour's as far as the table holds them (kb_Ey).  The clamp of i and
 // the cap at Nz are there for safety and change no result: build_bottom stores the columns [-E, Nx + E) with E = kb_E >=
@@ -808,29 +803,6 @@ gb25_status build_eos_tables(gb25_model* m) {
   return GB25_OK;
 }
 
-// Split-explicit averaging weights (Oceananigans FixedSubstepNumber, restated): shape function
-// (p=2, q=4, r=0.18927) sampled at tau = 2m/Ns, truncated like searchsortedlast(w, 0, rev=true).
-void build_substeps(gb25_model* m) {
-  const int N = m->cfg.substeps;
-  std::vector<double> w(N + 1, 0.0);
-  const double p = 2, q = 4, r = 0.18927, tau0 = (p + 2) * (p + q + 2) / (p + 1) / (p + q + 1);
-  for (int k = 1; k <= N; k++) {
-    double x = (2.0 * k / N) / tau0;
-    w[k] = std::pow(x, p) * (1 - std::pow(x, q)) - r * x;
-  }
-  int lo = 0, hi = N + 1;
-  while (lo < hi - 1) {
-    int mid = lo + ((hi - lo) >> 1);
-    if (w[mid] < 0.0) hi = mid; else lo = mid;
-  }
-  double s = 0;
-  for (int k = 1; k <= lo; k++) s += w[k];
-  m->Ns = lo;
-  m->dtau_frac = 2.0 / N;
-  m->weights.resize(lo);
-  for (int k = 1; k <= lo; k++) m->weights[k - 1] = w[k] / s;
-}
-
 // GridFittedBottom(bottom_height) -> first active level per column -> the folded tables (device_common.hpp, Immersed).
 // zb(i, j): bottom height at the centre of LOCAL column i (any i in [-E, Nx + E)), GLOBAL row j in [0, Ny_global).
 // Restated from Oceananigans.ImmersedBoundaries [UPSTREAM-UNVERIFIED]; oracle/gb25_oracle.c states the same rules cell
@@ -988,6 +960,23 @@ gb25_status alloc_field(gb25_model* m, Field& F, int nx, int ny, int nz) {
     return fail(m, GB25_ERR_OUT_OF_MEMORY, "hipMalloc of %zu bytes failed: %s", F.elems() * sizeof(real),
                 hipGetErrorString(e));
   HIPCHK(zeroed(F.d, F.elems() * sizeof(real)));
+  return GB25_OK;
+}
+inline gb25_status alloc_field(gb25_model* m, Field& F, Dims d) { return alloc_field(m, F, d.nx, d.ny, d.nz); }
+// an array with the parent extents of field id (model_layout.hpp)
+inline gb25_status alloc_like(gb25_model* m, Field& F, int id) { return alloc_field(m, F, parent_dims(m->layout, id)); }
+// three arrays in ONE zeroed block, F[q] with the extents dims(layout, id0 + q): the filtered state and its partners, the running
+// averages on the wide domain (one memset per step)
+gb25_status alloc_three(gb25_model* m, Field F[3], Dims (*dims)(const ModelLayout&, int), int id0, real** base) {
+  size_t tot = 0;
+  for (int q = 0; q < 3; q++) tot += dims(m->layout, id0 + q).elems();
+  HIPCHK(m->mem.alloc(base, tot * sizeof(real), true));
+  real* d = *base;
+  for (int q = 0; q < 3; q++) {
+    const Dims e = dims(m->layout, id0 + q);
+    F[q] = Field{d, e.nx, e.ny, e.nz};
+    d += e.elems();
+  }
   return GB25_OK;
 }
 
@@ -2551,6 +2540,21 @@ void gb25_default_config(gb25_config* c, int32_t Nx, int32_t Ny, int32_t Nz) {
   c->slab_mode = 0; c->grid_type = GB25_GRID_LAT_LON; c->ranks_y = 1;
 }
 
+// What plan_layout decided, into the members that carry its names and into the options it has a default for: the one place
+static void adopt_layout(gb25_model* m, const ModelLayout& L) {
+  m->layout = L;
+  m->Nx = L.Nx; m->Ny = L.Ny;
+  m->Rx = L.Rx; m->Ry = L.Ry; m->rx = L.rx; m->ry = L.ry; m->j0 = L.j0;
+  m->ys_open = L.ys_open; m->yn_open = L.yn_open; m->slab = L.slab;
+  m->Ns = L.sub.Ns; m->dtau_frac = L.sub.dtau_frac; m->weights = L.sub.weights;
+  m->W = L.W; m->Wy = L.Wy; m->Wys = L.Wys;
+  m->tracer_rows_forced = L.tracer_rows_forced;
+  // (gb25_set_option changes any of these defaults; nothing else is read from the environment)
+  m->mom_chunk_levels = m->trc_chunk_levels = L.chunk_levels;
+  m->baro_ahead = L.baro_ahead;
+  m->split_tendencies = L.split_tendencies;
+}
+
 gb25_status gb25_create(const gb25_config* cfg, gb25_model** out) {
   if (!cfg || !out) return GB25_ERR_INVALID_ARGUMENT;
   *out = nullptr;
@@ -2558,58 +2562,16 @@ gb25_status gb25_create(const gb25_config* cfg, gb25_model** out) {
   gb25_default_catke_parameters(&m->catke_par);
   *out = m;  // returned even on failure so the caller can read the error string, then destroy
   m->cfg = *cfg;
-  m->Ry = cfg->ranks_y > 1 ? cfg->ranks_y : 1;
-  if (cfg->Nx < 8 || cfg->Ny < 8 || cfg->Nz < 4 || cfg->halo < 4 || cfg->substeps < 1 || cfg->substeps > 4096 ||
-      cfg->nranks < 1 || cfg->rank < 0 || cfg->rank >= cfg->nranks || cfg->nranks % m->Ry != 0 ||
-      cfg->Nx % (cfg->nranks / m->Ry) != 0 || cfg->Ny % m->Ry != 0)
-    return fail(m, GB25_ERR_INVALID_ARGUMENT,
-                "invalid configuration: need Nx,Ny >= 8, Nz >= 4, halo >= 4, 1 <= substeps <= 4096, nranks = Rx ranks_y, "
-                "Nx %% Rx == 0, Ny %% ranks_y == 0");
-  if (cfg->slab_mode < 0 || cfg->slab_mode > 1)
-    return fail(m, GB25_ERR_INVALID_ARGUMENT, "slab_mode must be 0 (x halos by exchange iff nranks > 1) or 1 (always)");
-  m->Rx = cfg->nranks / m->Ry;
-  m->rx = cfg->rank % m->Rx;
-  m->ry = cfg->rank / m->Rx;
-  m->Nx = cfg->Nx / m->Rx;
-  m->Ny = cfg->Ny / m->Ry;
-  m->j0 = m->ry * m->Ny;
-  m->ys_open = m->ry > 0;
-  m->yn_open = m->ry < m->Ry - 1;
-  m->slab = cfg->nranks > 1 || cfg->slab_mode == 1;
+  m->last_dt = cfg->dt;
+
+  // ---- 1. plan, and refuse (model_layout.hpp): nothing of HIP, so a refused configuration allocates nothing
   {
-    // Levels per chunk of the two tendency kernels (options MOMENTUM_ / TRACER_CHUNK_LEVELS): 24 where that still leaves four
-    // rounds of blocks on the chip's 1024 block slots -- 1440 x 720 x 48: two chunks per column instead of four, +1.3 % steps/s
-    // (415.5 -> 420.9 on one box; 1440 x 720 x 60 with the islands 280 -> 285.5), the start-up of a chunk's march paid half as
-    // often --, 12 on narrower models: a 180-column rank of an 8-way decomposition would drop to one round and 0.47 -> 0.53 ms
-    // per step (tools/slab_selfring.py).  The chunking is the association of the column integrals of u, v: results differ in the
-    // last bits between the two, so a bit-for-bit comparison of a wide single domain with its narrow ranks pins the options.
-    const int nbx = (m->Nx + 63) / 64, nby = (m->Ny + 3) / 4;
-    if ((long)nbx * nby * std::max(1, cfg->Nz / 24) >= 4096) m->mom_chunk_levels = m->trc_chunk_levels = 24;
+    const LayoutPlan plan = plan_layout(*cfg, (int)sizeof(real), getenv("GB25_TRACER_ROWS"));
+    if (plan.status) return fail(m, plan.status, "%s", plan.refusal.c_str());
+    adopt_layout(m, plan.layout);
   }
-  if (const char* rows = getenv("GB25_TRACER_ROWS")) {
-    if (strcmp(rows, "1") != 0 && strcmp(rows, "2") != 0)
-      return fail(m, GB25_ERR_INVALID_ARGUMENT, "GB25_TRACER_ROWS must be 1 or 2 (unset: the library's rule)");
-    m->tracer_rows_forced = rows[0] - '0';
-  }
-  if (m->Nx < cfg->halo) return fail(m, GB25_ERR_INVALID_ARGUMENT, "slab narrower than the halo");
-  if (m->Ry > 1) {
-    // a rank of a 2-D decomposition steps on the staged sequence without the interior / edge split of the tendencies and
-    // without the early pressure of the own columns
-    m->split_tendencies = 0;
-    if (m->Ny < cfg->halo + 2) return fail(m, GB25_ERR_INVALID_ARGUMENT, "a rank's band of rows is narrower than the halo");
-  }
-  {
-    // The kernels address a parent array with 32-bit ELEMENT indices; the tendency kernels with 32-bit BYTE offsets from the
-    // first plane their block touches (tendency_kernels.hpp): a chunk of levels plus its stencil planes must stay below 2 GB.
-    const double plane = (double)(m->Nx + 2 * cfg->halo) * (m->Ny + 2 * cfg->halo + 1);
-    const double elems = plane * (cfg->Nz + 2 * cfg->halo + 1);
-    const int kchunks = std::max(1, cfg->Nz / 12), klen = (cfg->Nz + kchunks - 1) / kchunks;
-    if (elems >= 2147483648.0 || plane * (klen + 10) * sizeof(real) >= 2147483648.0)
-      return fail(m, GB25_ERR_INVALID_ARGUMENT,
-                  "a %dx%dx%d slab has %.2g elements per 3-D array (%.1f GB) and %.2g per plane; the kernels index at most 2^31 "
-                  "elements per array and %d planes of 2 GB together: decompose in x (nranks) so that the local slab is narrower",
-                  m->Nx, m->Ny, cfg->Nz, elems, elems * sizeof(real) / 1e9, plane, klen + 10);
-  }
+
+  // ---- 2. the device, the streams, the events
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
     return fail(m, GB25_ERR_NO_DEVICE, "no HIP device visible; libgb25hip has no CPU fallback");
@@ -2625,132 +2587,54 @@ gb25_status gb25_create(const gb25_config* cfg, gb25_model** out) {
   // run in order -- a rocprof trace of eight slabs in one process, 25 streams, shows the exchange stream and the main
   // stream taking turns.  A slab has three: own, side, and the exchange stream of its context; the stream of
   // SUBCYCLE_LOOKAHEAD = 2 is created on demand.)
-  for (hipStream_t* st : m->streams()) {
-    if (st == &m->baro_stream) continue;   // (on demand)
-#ifdef GB25_SIDE_PRIO
-    if (st == &m->side_stream) {   // (tools/build_variant.sh experiment: the side stream -- the pressure branch -- at the LOWEST / main at the highest priority)
-      int least = 0, greatest = 0;
-      HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-      HIPCHK(hipStreamCreateWithPriority(st, hipStreamNonBlocking, GB25_SIDE_PRIO > 0 ? least : greatest));
-      continue;
-    }
-#endif
-    HIPCHK(hipStreamCreateWithFlags(st, hipStreamNonBlocking));
-  }
+  for (hipStream_t* st : m->streams())
+    if (st != &m->baro_stream) HIPCHK(hipStreamCreateWithFlags(st, hipStreamNonBlocking));
   for (hipEvent_t* ev : m->events()) HIPCHK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
-
   m->stream = m->own_stream;
-  m->last_dt = cfg->dt;
-  // On launch-latency-bound grids the extra cross-stream hops of the sub-cycle look-ahead cost more than the
-  // sub-cycle they hide (0.252 vs 0.262 ms/step at 360x180x24, 0.173 vs 0.185 at 128x64x8; +3.5 % at 1440x720x48).
-  // A slab of a decomposition always uses it: there it also takes two exchanges off the critical path.
-  // (gb25_set_option changes any of these defaults; nothing is read from the environment.)
-  m->baro_ahead = (m->slab || (long)cfg->Nx * cfg->Ny * cfg->Nz >= 8000000L) ? 1 : 0;
+
+  // ---- 3. the grid's tables, then every array: each has the extents of a field (alloc_like: parent_dims) or of the sub-cycle's work
+  // array that stands for one (wide_dims: W columns either side, Wy + Wys more rows).  The order of allocation is kept as it was.
+  const ModelLayout& L = m->layout;
   gb25_status s;
   if ((s = build_grid(m))) return s;
   if ((s = build_eos_tables(m))) return s;
-  build_substeps(m);
-  if (cfg->grid_type < 0 || cfg->grid_type >= GB25_GRID_COUNT)
-    return fail(m, GB25_ERR_INVALID_ARGUMENT, "grid_type %d: 0 lat-lon, 1 lat-lon with the Gaussian islands, 2 lat-lon "
-                "through the curvilinear kernels, 3 tripolar, 4 tripolar with the Gaussian islands", cfg->grid_type);
-  if (cfg->grid_type >= GB25_GRID_LAT_LON_AS_CURVILINEAR) {
-    if (cfg->grid_type >= GB25_GRID_TRIPOLAR && (cfg->Nx % 2 || m->Ny < 2 * cfg->halo))
-      return fail(m, GB25_ERR_INVALID_ARGUMENT, "the tripolar grid needs an even Nx and Ny >= 2 halo (the fold maps columns onto columns)");
-    if ((s = build_curv_grid(m))) return s;
-  }
-  const int H = cfg->halo, sx = m->Nx + 2 * H;
+  if (cfg->grid_type >= GB25_GRID_LAT_LON_AS_CURVILINEAR && (s = build_curv_grid(m))) return s;
   for (int id = 0; id < GB25_FIELD_COUNT; id++) {
     if (id >= GB25_ETA_BAR && id <= GB25_V_BAR) continue;  // allocated contiguously below
     if (is_catke_field(id)) continue;   // (allocated when the closure is switched on)
-    int ny = m->Ny + 2 * H + (is_v_shaped(id) ? 1 : 0);
-    int nz = is_2d(id) ? 1 : cfg->Nz + 2 * H + (id == GB25_W ? 1 : 0);
-    if ((s = alloc_field(m, m->f[id], sx, ny, nz))) return s;
+    if ((s = alloc_like(m, m->f[id], id))) return s;
   }
-  {
-    size_t nc = (size_t)sx * (m->Ny + 2 * H), nv = (size_t)sx * (m->Ny + 2 * H + 1);
-    HIPCHK(m->mem.alloc(&m->bars, (2 * nc + nv) * sizeof(real), true));
-    Field& e = m->f[GB25_ETA_BAR]; e.d = m->bars; e.nx = sx; e.ny = m->Ny + 2 * H; e.nz = 1;
-    Field& u = m->f[GB25_U_BAR]; u.d = m->bars + nc; u.nx = sx; u.ny = m->Ny + 2 * H; u.nz = 1;
-    Field& v = m->f[GB25_V_BAR]; v.d = m->bars + 2 * nc; v.nx = sx; v.ny = m->Ny + 2 * H + 1; v.nz = 1;
-  }
+  if ((s = alloc_three(m, &m->f[GB25_ETA_BAR], parent_dims, GB25_ETA_BAR, &m->bars))) return s;   // contiguous etabar | Ubar | Vbar
   for (int q = 0; q < 3; q++) {
-    if ((s = alloc_field(m, m->pp[q], sx, m->f[GB25_ETA + q].ny, 1))) return s;
-    if ((s = alloc_field(m, m->pp2[q], sx, m->f[GB25_ETA + q].ny, 1))) return s;
-    if ((s = alloc_field(m, m->ahead_eta[q], sx, m->f[GB25_ETA + q].ny, 1))) return s;
+    if ((s = alloc_like(m, m->pp[q], GB25_ETA + q))) return s;
+    if ((s = alloc_like(m, m->pp2[q], GB25_ETA + q))) return s;
+    if ((s = alloc_like(m, m->ahead_eta[q], GB25_ETA + q))) return s;
   }
-  {   // partners of the filtered state, laid out like `bars`
-    size_t off = 0, tot = 0;
-    for (int q = 0; q < 3; q++) tot += m->f[GB25_ETA_BAR + q].elems();
-    HIPCHK(m->mem.alloc(&m->bars_ahead, tot * sizeof(real), true));
-    for (int q = 0; q < 3; q++) {
-      m->ahead_bar[q] = m->f[GB25_ETA_BAR + q];
-      m->ahead_bar[q].d = m->bars_ahead + off;
-      off += m->f[GB25_ETA_BAR + q].elems();
-    }
-  }
-  if ((s = alloc_field(m, m->dpx, m->f[GB25_PHY].nx, m->f[GB25_PHY].ny, m->f[GB25_PHY].nz))) return s;
-  if ((s = alloc_field(m, m->dpy, m->f[GB25_PHY].nx, m->f[GB25_PHY].ny, m->f[GB25_PHY].nz))) return s;
-
+  if ((s = alloc_three(m, m->ahead_bar, parent_dims, GB25_ETA_BAR, &m->bars_ahead))) return s;   // partners of the filtered state, laid out like `bars`
+  if ((s = alloc_like(m, m->dpx, GB25_PHY))) return s;
+  if ((s = alloc_like(m, m->dpy, GB25_PHY))) return s;
   for (int q = 0; q < 2; q++) {
-    if ((s = alloc_field(m, m->ahead[q], m->f[GB25_T].nx, m->f[GB25_T].ny, m->f[GB25_T].nz))) return s;
-    const Field &V3 = m->f[GB25_U + q], &V2 = m->f[GB25_GN_BT_U + q], &C2 = m->f[GB25_BT_U + q];
-    if ((s = alloc_field(m, m->ahead_uv[q], V3.nx, V3.ny, V3.nz))) return s;
-    if ((s = alloc_field(m, m->ahead_G[q], V2.nx, V2.ny, 1))) return s;
-    if ((s = alloc_field(m, m->ahead_colsum[q], C2.nx, C2.ny, 1))) return s;
+    if ((s = alloc_like(m, m->ahead[q], GB25_T + q))) return s;
+    if ((s = alloc_like(m, m->ahead_uv[q], GB25_U + q))) return s;
+    if ((s = alloc_like(m, m->ahead_G[q], GB25_GN_BT_U + q))) return s;
+    if ((s = alloc_like(m, m->ahead_colsum[q], GB25_BT_U + q))) return s;
   }
-  {
-    const size_t np = (size_t)4 * std::max(1, m->g.Nz / 6) * m->g.sx * m->g.sy_v;   // (room for chunks of 6 levels)
-    HIPCHK(m->mem.alloc(&m->uv_partials, np * sizeof(real), true));
-    HIPCHK(m->mem.alloc(&m->wbase, (np / 4) * sizeof(real), true));
-  }
-  if ((s = alloc_field(m, m->corr[0], sx, m->f[GB25_BT_V].ny, 1))) return s;
-  if ((s = alloc_field(m, m->corr[1], sx, m->f[GB25_BT_V].ny, 1))) return s;
-  if ((s = alloc_field(m, m->colsum[0], sx, m->f[GB25_BT_U].ny, 1))) return s;
-  if ((s = alloc_field(m, m->colsum[1], sx, m->f[GB25_BT_V].ny, 1))) return s;
-  if (m->slab || m->g.cv.north_fold) {
-    if (m->slab) {
-      // wide enough that after the Ns substeps the valid region still covers the slab's x HALO columns of eta, U, V: they are
-      // computed here like the neighbour computes them (same inputs, same arithmetic) and no exchange follows the sub-cycle
-      m->W = m->Ns + 1 + m->cfg.halo;
-      if (m->Nx < m->W)
-        return fail(m, GB25_ERR_INVALID_ARGUMENT, "slab width %d is narrower than the barotropic halo %d", m->Nx, m->W);
-    }
-    // folded grid: image rows beyond the pivot row, enough that what the last row's missing neighbour spoils (one row per
-    // substep) never reaches the pivot row
-    // (Oceananigans errors when the extended halo of its free surface exceeds the grid; so does this: with fewer rows the spoiled
-    // rows would reach the pivot row and eta, U, V next to the fold would be wrong without a word)
-    if (m->g.cv.north_fold) {
-      if (m->Ny - 2 < m->Ns + 1)
-        return fail(m, GB25_ERR_INVALID_ARGUMENT, "a folded grid needs Ny >= %d rows per rank for its %d effective substeps (the sub-cycle's "
-                    "image rows beyond the pivot row: Ns + 1 of them, made from the rows south of it); this rank has %d", m->Ns + 3, m->Ns, m->Ny);
-      m->Wy = m->Ns + 1;
-    }
-    // 2-D decomposition: wide halos in y as in x on the sides where a neighbour rank exists
-    if (m->yn_open) m->Wy = m->W;
-    if (m->ys_open) m->Wys = m->W;
-    if ((m->yn_open || m->ys_open) && m->Ny < m->W)
-      return fail(m, GB25_ERR_INVALID_ARGUMENT, "a rank's band of %d rows is narrower than the barotropic halo %d", m->Ny, m->W);
-    const int wsx = m->Nx + 2 * m->W, wy = m->Wy + m->Wys;
+  HIPCHK(m->mem.alloc(&m->uv_partials, 4 * chunk_columns(L) * sizeof(real), true));
+  HIPCHK(m->mem.alloc(&m->wbase, chunk_columns(L) * sizeof(real), true));
+  if ((s = alloc_like(m, m->corr[0], GB25_BT_V))) return s;   // (du and dv: both with the row of a y-face field)
+  if ((s = alloc_like(m, m->corr[1], GB25_BT_V))) return s;
+  if ((s = alloc_like(m, m->colsum[0], GB25_BT_U))) return s;
+  if ((s = alloc_like(m, m->colsum[1], GB25_BT_V))) return s;
+  if (L.wide()) {
     for (int a = 0; a < 2; a++)
       for (int q = 0; q < 3; q++)
-        if ((s = alloc_field(m, m->wide[a][q], wsx, m->f[GB25_ETA + q].ny + wy, 1))) return s;
-    {   // the three running averages are one allocation, zeroed by one memset per step
-      size_t tot = 0;
-      for (int q = 0; q < 3; q++) {
-        m->wideBar[q].nx = wsx; m->wideBar[q].ny = m->f[GB25_ETA + q].ny + wy; m->wideBar[q].nz = 1;
-        tot += m->wideBar[q].elems();
-      }
-      real* base = nullptr;
-      HIPCHK(m->mem.alloc(&base, tot * sizeof(real), true));
-      for (int q = 0; q < 3; q++) {
-        m->wideBar[q].d = base;
-        base += m->wideBar[q].elems();
-      }
-    }
-    if ((s = alloc_field(m, m->wideG[0], wsx, m->f[GB25_GN_BT_U].ny + wy, 1))) return s;
-    if ((s = alloc_field(m, m->wideG[1], wsx, m->f[GB25_GN_BT_V].ny + wy, 1))) return s;
+        if ((s = alloc_field(m, m->wide[a][q], wide_dims(L, GB25_ETA + q)))) return s;
+    real* wide_bars = nullptr;   // the three running averages are one allocation, zeroed by one memset per step
+    if ((s = alloc_three(m, m->wideBar, wide_dims, GB25_ETA, &wide_bars))) return s;
+    if ((s = alloc_field(m, m->wideG[0], wide_dims(L, GB25_GN_BT_U)))) return s;
+    if ((s = alloc_field(m, m->wideG[1], wide_dims(L, GB25_GN_BT_V)))) return s;
     if (m->g.cv.on && (s = build_curv_wide(m))) return s;
-    if (m->Wy && !m->slab) HIPCHK(m->mem.alloc(&m->tall_buf, (size_t)5 * (m->Wy + 1) * wsx * sizeof(real)));
+    if (L.Wy && !L.slab) HIPCHK(m->mem.alloc(&m->tall_buf, tall_buf_elems(L) * sizeof(real)));
   }
   if ((s = rebuild_bottom(m))) return s;
   HIPCHK(hipDeviceSynchronize());
@@ -2800,17 +2684,12 @@ gb25_status gb25_synchronize(gb25_model* m) {
 
 gb25_status gb25_field_dims(const gb25_model* m, gb25_field id, int include_halos, int32_t d[3]) {
   if (!m || id < 0 || id >= GB25_FIELD_COUNT || !d) return GB25_ERR_INVALID_ARGUMENT;
-  const Field& F = m->f[id];
-  if (!F.d) return GB25_ERR_INVALID_ARGUMENT;   // (a field of CATKE on a model whose closure is not CATKE)
-  const int H = m->cfg.halo;
+  if (!m->f[id].d) return GB25_ERR_INVALID_ARGUMENT;   // (a field of CATKE on a model whose closure is not CATKE)
   // A y-face field of a folded grid has Ny rows ((Periodic, RightConnected, Bounded): the faces beyond the last row of cells are
-  // halo cells), so its parent has Ny + 2H rows like a cell-centred one; the device arrays keep the row a Bounded grid needs.
-  const int ny = F.ny - (((m->g.cv.north_fold || m->yn_open) && is_v_shaped(id)) ? 1 : 0);   // (likewise below a northern neighbour rank)
-  if (include_halos) {
-    d[0] = F.nx; d[1] = ny; d[2] = F.nz;
-  } else {
-    d[0] = F.nx - 2 * H; d[1] = ny - 2 * H; d[2] = is_2d(id) ? 1 : F.nz - 2 * H;
-  }
+  // halo cells), so its parent has Ny + 2H rows like a cell-centred one, likewise below a northern neighbour rank; the device
+  // arrays keep the row a Bounded grid needs (host_dims and parent_dims, model_layout.hpp).
+  const Dims h = host_dims(m->layout, id, include_halos != 0);
+  d[0] = h.nx; d[1] = h.ny; d[2] = h.nz;
   return GB25_OK;
 }
 
@@ -2831,11 +2710,11 @@ static gb25_status copy_field(gb25_model* m, gb25_field id, real* host, int incl
     else HIPCHK(hipMemcpy(host, F.d, F.elems() * sizeof(real), hipMemcpyDeviceToHost));
     return GB25_OK;
   }
-  const int H = include_halos ? 0 : m->cfg.halo;
+  const Dims skip = include_halos ? Dims{0, 0, 0} : halo_depth(m->layout, id);
   hipMemcpy3DParms p = {};
   hipPitchedPtr dev = make_hipPitchedPtr(F.d, (size_t)F.nx * sizeof(real), F.nx, F.ny);
   hipPitchedPtr hst = make_hipPitchedPtr(host, (size_t)d[0] * sizeof(real), d[0], d[1]);
-  hipPos dpos = make_hipPos((size_t)H * sizeof(real), H, is_2d(id) ? 0 : H), zero = make_hipPos(0, 0, 0);
+  hipPos dpos = make_hipPos((size_t)skip.nx * sizeof(real), skip.ny, skip.nz), zero = make_hipPos(0, 0, 0);
   p.extent = make_hipExtent((size_t)d[0] * sizeof(real), d[1], d[2]);
   if (to_device) {
     p.srcPtr = hst; p.srcPos = zero; p.dstPtr = dev; p.dstPos = dpos; p.kind = hipMemcpyHostToDevice;
@@ -2996,15 +2875,12 @@ gb25_status gb25_set_closure_catke(gb25_model* m, int32_t on) {
   if (on && m->cfg.Nz < 2) return fail(m, GB25_ERR_INVALID_ARGUMENT, "CATKE needs at least two levels (it lives on the faces between them)");
   if (gb25_status s = wait_for_model(m)) return s;
   if (on && !m->f[GB25_E].d) {
-    const int H = m->cfg.halo, sx = m->Nx + 2 * H, sy = m->Ny + 2 * H, nz = m->cfg.Nz + 2 * H;
     gb25_status s;
-    for (int id = GB25_E; id <= GB25_PREV_V; id++) {
-      const bool faces = id >= GB25_KAPPA_U && id <= GB25_KAPPA_E;
-      if ((s = alloc_field(m, m->f[id], sx, sy + (is_v_shaped(id) ? 1 : 0), id == GB25_JB ? 1 : nz + (faces ? 1 : 0)))) return s;
-    }
-    if ((s = alloc_field(m, m->catke_b, sx, sy, nz))) return s;
-    if ((s = alloc_field(m, m->catke_src, sx, sy, 1))) return s;
-    if ((s = alloc_field(m, m->catke_scratch, sx, sy, nz))) return s;
+    for (int id = 0; id < GB25_FIELD_COUNT; id++)
+      if (is_catke_field(id) && (s = alloc_like(m, m->f[id], id))) return s;
+    if ((s = alloc_like(m, m->catke_b, GB25_E))) return s;
+    if ((s = alloc_like(m, m->catke_src, GB25_JB))) return s;
+    if ((s = alloc_like(m, m->catke_scratch, GB25_E))) return s;
   }
   if (gb25_status s_ = materialize_prev_uv(m)) return s_;   // (while the closure still says where they are)
   m->catke = on != 0;
@@ -3310,13 +3186,12 @@ static gb25_status opt_catke_stale_e_halos(gb25_model* m, int32_t* v) {
   return GB25_OK;
 }
 static gb25_status opt_chunk_levels(gb25_model* m, int32_t* v) {
-  // the tendency kernels reach one chunk of levels plus its stencil planes with 32-bit byte offsets (gb25_create checks the
-  // default chunking): the chosen one must stay within that reach too
-  const double plane = (double)(m->Nx + 2 * m->cfg.halo) * (m->Ny + 2 * m->cfg.halo + 1);
-  const int kchunks = std::max(1, m->cfg.Nz / *v), klen = (m->cfg.Nz + kchunks - 1) / kchunks;
-  if (plane * (klen + 10) * sizeof(real) >= 2147483648.0)
+  // the tendency kernels reach one chunk of levels plus its stencil planes with 32-bit byte offsets (plan_layout checks the
+  // default chunking by the same rule): the chosen one must stay within that reach too
+  const TendencyReach r = tendency_reach_ok(m->layout, *v, (int)sizeof(real));
+  if (!r.ok)
     return fail(m, GB25_ERR_INVALID_ARGUMENT, "chunks of %d levels (+ 10 stencil planes of %.3g elements) exceed the 2 GB the tendency "
-                "kernels address from one base: choose fewer levels per chunk", klen, plane);
+                "kernels address from one base: choose fewer levels per chunk", r.klen, r.plane);
   m->valid.void_colsums();
   return GB25_OK;
 }
@@ -3668,9 +3543,8 @@ gb25_status gb25_save_state(gb25_model* m, const char* directory, const char* la
       return s;
     }
     const int64_t i0 = (int64_t)m->rx * m->Nx, j0 = m->j0;
-    // (global rows: Ny, + 1 for a y-face field of a grid with a northern wall)
-    const int64_t gny = (int64_t)m->cfg.Ny + ((is_v_shaped(fld.id) && m->cfg.grid_type < GB25_GRID_TRIPOLAR) ? 1 : 0);
-    const int64_t slice[6] = {i0, i0 + d[0], j0, j0 + d[1], 0, d[2]}, gshape[3] = {m->cfg.Nx, m->Ry > 1 ? gny : d[1], d[2]};
+    const int64_t slice[6] = {i0, i0 + d[0], j0, j0 + d[1], 0, d[2]};
+    const int64_t gshape[3] = {m->cfg.Nx, m->Ry > 1 ? global_rows(m->layout, fld.id) : d[1], d[2]};
     z.add_array(std::string(fld.name) + ".data", sizeof(real) == 8 ? "<f8" : "<f4", {d[0], d[1], d[2]}, host.data());
     z.add_array(std::string(fld.name) + ".slice", "<i8", {6}, slice);
     z.add_array(std::string(fld.name) + ".global_shape", "<i8", {3}, gshape);

@@ -134,7 +134,8 @@ typedef enum {
   GB25_OPT_LAZY_CORRECTOR,       /* [1] single flat lat-lon domain, between the steps of one gb25_loop call: the barotropic
                                     correction of u, v is added by the kernels that read them instead of by a sweep over
                                     u and v (same bits; memory holds the corrected velocities when the call returns) */
-  GB25_OPT_MOMENTUM_CHUNK_LEVELS, /* [24 on models wide enough for four rounds of blocks with it -- 1440 x 720 x 48 --, else 12] levels a
+  GB25_OPT_MOMENTUM_CHUNK_LEVELS, /* [24 on models wide enough for four rounds of blocks with it -- 1440 x 720 x 48 -- and small enough that such chunks stay
+                                    within the 2 GB the kernel addresses from one base, else 12] levels a
                                     block of the momentum tendency kernel marches through (>= 6); also the association of the
                                     column integrals of u, v: results change in the last bits (a bit-for-bit comparison of a wide
                                     single domain with its narrow ranks pins it on both sides) */

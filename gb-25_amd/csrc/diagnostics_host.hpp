@@ -107,7 +107,7 @@ gb25_status diag_source(gb25_model* m, gb25_field id, const real** src) {
     if (gb25_status s = materialize_uv(m)) return s;
   if (id == GB25_PHY && m->phy_stale) {
     m->prof_redirect = GB25_K_DIAGNOSTICS;
-    const gb25_status s = compute_p_impl(m);
+    const gb25_status s = compute_p_impl(m, PressureBox::whole(launch_facts(m)));
     m->prof_redirect = -1;
     if (s) return s;
   }

@@ -22,6 +22,7 @@
 #include "step_route.hpp"
 #include "subcycle_plan.hpp"
 #include "model_layout.hpp"
+#include "launch_plan.hpp"
 
 #include <cmath>
 #include <cstdarg>
@@ -183,7 +184,7 @@ struct gb25_model {
   int baro_block = 5;                // substeps per barotropic launch (option SUBCYCLE_BLOCK = 1: one launch per substep; 5: 64 x 17 tiles,
                                      // four blocks per CU, every block of a 1440 x 720 launch resident at once: 0.16 ms for 21 substeps against 0.21 with 7)
   int kernel_gen = 2;                // 2: LDS / flux-sharing tendency kernels (tendency_kernels.hpp); 1: direct-stencil kernels
-  int pressure_form = 0;             // option PRESSURE_FORM: 0 = the rule of compute_p_impl; 1 tiles, 2 one row, 3 four rows per thread
+  int pressure_form = 0;             // option PRESSURE_FORM: 0 = the rule of plan_pressure; 1 tiles, 2 one row, 3 four rows per thread
   int spectrum_table_where = 0;      // option SPECTRUM_TABLE: 0 = the rule of spectrum_run (LDS where it fits); 1 global memory
   int pressure_bits = 64;            // option PRESSURE_PRECISION: 64 = fp64 EOS + integral (default); 32 = the float type's own
   // single periodic domain: the last writers of u, v (corrector), T, S (tracer look-ahead) and eta, U, V (last barotropic
@@ -986,19 +987,18 @@ inline int trc_kchunks(const gb25_model* m) { return std::max(1, m->g.Nz / m->tr
 inline bool chunkings_match(const gb25_model* m) { return trc_kchunks(m) == mom_kchunks(m); }
 inline dim3 grid2(int nx, int ny, dim3 b) { return dim3((nx + b.x - 1) / b.x, (ny + b.y - 1) / b.y); }
 
-// sel: 3 = u, v, T, S;  1 = u, v;  2 = T, S
-Halo3 halo3(gb25_model* m, int sel = 3) {
+Halo3 halo3(gb25_model* m, Fields3 sel) {
   Halo3 h{};
   int n = 0;
-  if (sel & 1) {   // (xf, neg: how the field crosses the zipper fold -- on x faces, changing sign)
+  if (has(sel, Fields3::UV)) {   // (xf, neg: how the field crosses the zipper fold -- on x faces, changing sign)
     h.p[n] = m->f[GB25_U].d; h.xf[n] = 1; h.neg[n] = 1; h.is_v[n++] = 0;
     h.p[n] = m->f[GB25_V].d; h.neg[n] = 1; h.is_v[n++] = 1;
   }
-  if (sel & 2) {
+  if (has(sel, Fields3::TS)) {
     h.p[n] = m->f[GB25_T].d; h.is_v[n++] = 0;
     h.p[n] = m->f[GB25_S].d; h.is_v[n++] = 0;
   }
-  if (sel & 4) h.p[n] = m->f[GB25_E].d, h.is_v[n++] = 0;   // (the TKE tracer of CATKE: a launch of its own, sel = 4)
+  if (has(sel, Fields3::E)) h.p[n] = m->f[GB25_E].d, h.is_v[n++] = 0;   // (the TKE tracer of CATKE: a launch of its own)
   h.n = n;
   return h;
 }
@@ -1027,113 +1027,74 @@ inline bool producers_fold(const gb25_model* m) {
 // folded grid, halo cells)
 inline int v_rows(const Grid& g) { return g.Ny; }
 
-// y/z boundary layers (always local) and, for a single slab, the periodic x copy.
-// extended: also treat the x-halo columns (slab mode, after the neighbours' columns were unpacked).
-// which: 3 = 3-D and 2-D fields, 1 = the 3-D bundle only, 2 = the 2-D fields only (slab pipeline).
-// sel3: which 3-D fields (halo3); st: stream (nullptr = the model's stream).
-gb25_status fill_halos_2d(gb25_model* m, Halo2 h2);
-gb25_status fill_halos_impl(gb25_model* m, bool with_x, bool extended = false, int which = 3, int sel3 = 3,
-                            hipStream_t st = nullptr, bool use_default_stream = true, const Halo2* h2_other = nullptr) {
+// what the plans of launch_plan.hpp need to know of the model: the one place that reads it
+inline LaunchFacts launch_facts(const gb25_model* m) {
   const Grid& g = m->g;
-  if (use_default_stream) st = m->stream;
+  return {g.Nx, g.Ny, g.Nz, g.H, g.sy_c, g.sy_v, g.x_periodic != 0, g.cv.north_fold != 0, g.cv.pivot_slaved, m->slab, m->ys_open, m->yn_open,
+          m->fill_fused != 0, g.cv.on != 0};
+}
+
+// Binds the model's arrays to a fill request, plans it (plan_fill) and issues the planned launches in order on the model's stream.
+// given: the 2-D fields of a Fields2::Given request.  The timer is the caller's.
+gb25_status issue_fill(gb25_model* m, FillRequest rq, const Halo2& given) {
+  const Grid& g = m->g;
+  const Halo3 h3 = halo3(m, rq.f3);
+  const Halo2 h2 = rq.f2 == Fields2::Given ? given : rq.f2 == Fields2::Prognostic ? halo2_prognostic(m) : Halo2{};
+  rq.n_given = given.n;
+  const FillPlan p = plan_fill(rq, launch_facts(m));
+  const dim3 b(256);
+  auto launch = [&](const Grid& gl, const FillLaunch& L) {
+    const dim3 gr(L.gx, L.gy, L.gz);
+    switch (L.kernel) {
+      case FillKernel::Y: hipLaunchKernelGGL(k_fill_y, gr, b, 0, m->stream, gl, h3, h2, L.i0, L.ni); break;
+      case FillKernel::YZ: hipLaunchKernelGGL(k_fill_yz, gr, b, 0, m->stream, gl, h3, h2, L.i0, L.ni, L.jlo); break;
+      case FillKernel::Fold: hipLaunchKernelGGL(k_fill_fold, gr, b, 0, m->stream, gl, h3, h2); break;
+      case FillKernel::X: hipLaunchKernelGGL(k_fill_x, gr, b, 0, m->stream, gl, h3, h2, L.rows_c, L.rows_v); break;
+      case FillKernel::Fused:
+        hipLaunchKernelGGL(k_fill_fused, gr, b, 0, m->stream, gl, h3, h2, L.nbx, L.nb_yz, L.nbr, L.rows_c, L.rows_v);
+        break;
+    }
+  };
+  for (int q = 0; q < p.n; q++) {
+    if (p.l[q].flat) {
+      Grid g2 = g;
+      g2.Nz = 0;
+      launch(g2, p.l[q]);
+    } else {
+      launch(g, p.l[q]);
+    }
+  }
+  LAUNCHCHK();
+  return GB25_OK;
+}
+// y / z boundary layers (always local), the rows beyond a single domain's zipper fold and the periodic x copy of the fields and
+// columns the request names (launch_plan.hpp)
+gb25_status fill_halos_impl(gb25_model* m, FillRequest rq, const Halo2& given = Halo2{}) {
   Timed t(m, GB25_K_FILL_HALOS);
-  Halo3 h3 = halo3(m, sel3);
-  Halo2 h2 = h2_other ? *h2_other : halo2_prognostic(m);
-  dim3 b(256);
-  const int i0 = extended ? -g.H : 0, ni = extended ? g.Nx + 2 * g.H : g.Nx;
-  if (which == 2 && with_x && g.x_periodic && !extended && !h2_other) return fill_halos_2d(m, halo2_prognostic(m));
-  if (g.cv.north_fold && !m->slab) {   // y / z layers, the rows beyond the fold, then the periodic x copy over all of them
-    if (which == 2) return fill_halos_2d(m, h2);
-    if (which == 1) h2.n = 0;
-    hipLaunchKernelGGL(k_fill_yz, dim3((g.Nx + 255) / 256, g.Nz + 1 + g.Ny), b, 0, st, g, h3, h2, 0, g.Nx, 0);
-    hipLaunchKernelGGL(k_fill_fold, dim3((g.Nx + 255) / 256, g.H + g.cv.pivot_slaved, g.Nz + 2 + (h2.n ? 1 : 0)), b, 0, st, g, h3, h2);
-    const int rows_c = g.sy_c * (g.Nz + 2 * g.H), rows_v = g.sy_v * (g.Nz + 2 * g.H);
-    hipLaunchKernelGGL(k_fill_x, dim3((unsigned)(((long)rows_v * 2 * g.H + 255) / 256), 4 + h2.n), b, 0, st, g, h3, h2,
-                       rows_c, rows_v);
-    LAUNCHCHK();
-    return GB25_OK;
-  }
-  if (which == 2) {
-    Grid g2 = g;
-    g2.Nz = 0;   // k_fill_y then runs its 2-D branch only
-    hipLaunchKernelGGL(k_fill_y, dim3((ni + 255) / 256, 1), b, 0, st, g2, h3, h2, i0, ni);
-    LAUNCHCHK();
-    return GB25_OK;
-  }
-  if (which == 1) h2.n = 0;
-  if (m->fill_fused && with_x && g.x_periodic && !extended) {   // single slab: y, z and periodic x in one launch
-    const int nbx = (g.Nx + 255) / 256, nb_yz = nbx * (g.Nz + 1 + g.Ny);
-    const int rows_c = g.sy_c * (g.Nz + 2 * g.H), rows_v = g.sy_v * (g.Nz + 2 * g.H);
-    const int nbr = (int)(((long)rows_v * 2 * g.H + 255) / 256);
-    hipLaunchKernelGGL(k_fill_fused, dim3(nb_yz + nbr * (4 + h2.n)), b, 0, st, g, h3, h2, nbx, nb_yz, nbr, rows_c,
-                       rows_v);
-    LAUNCHCHK();
-    return GB25_OK;
-  }
-  // (z layers: the own rows; `extended` on a rank of a 2-D decomposition: the halo rows of its open sides too -- they arrived
-  // with the neighbours' rows, interior levels only)
-  const int jlo = (extended && m->ys_open) ? -g.H : 0, jhi = (extended && m->yn_open) ? g.Ny + g.H : g.Ny;
-  hipLaunchKernelGGL(k_fill_yz, dim3((ni + 255) / 256, g.Nz + 1 + (jhi - jlo)), b, 0, st, g, h3, h2, i0, ni, jlo);
-  if (with_x && g.x_periodic) {
-    int rows_c = g.sy_c * (g.Nz + 2 * g.H), rows_v = g.sy_v * (g.Nz + 2 * g.H);
-    long threads = (long)rows_v * 2 * g.H;
-    hipLaunchKernelGGL(k_fill_x, dim3((unsigned)((threads + 255) / 256), 4 + h2.n), b, 0, st, g, h3, h2, rows_c,
-                       rows_v);
-  }
-  LAUNCHCHK();
-  return GB25_OK;
+  return issue_fill(m, rq, given);
 }
+// the caller's 2-D fields alone, with the periodic x copy; no timer of its own
+gb25_status fill_halos_2d(gb25_model* m, Halo2 h2) { return issue_fill(m, FillRequest::flat(Fields2::Given, Columns::OwnWithPeriodicX), h2); }
 
-gb25_status fill_halos_2d(gb25_model* m, Halo2 h2) {
-  const Grid& g = m->g;
-  Halo3 none{};
-  dim3 b(256);
-  // Nz = 0 makes k_fill_y take its 2-D branch for blockIdx.y == 0; k_fill_x's 3-D slices
-  // (blockIdx.y < 4) see zero rows and fall through.
-  Grid g2 = g;
-  g2.Nz = 0;
-  hipLaunchKernelGGL(k_fill_y, dim3((g.Nx + 255) / 256, 1), b, 0, m->stream, g2, none, h2, 0, g.Nx);
-  if (g.cv.north_fold && !m->slab)   // (a slab's rows beyond the fold come from its partner rank: slab_step.hpp)
-    hipLaunchKernelGGL(k_fill_fold, dim3((g.Nx + 255) / 256, g.H + g.cv.pivot_slaved, 1), b, 0, m->stream, g, none, h2);
-  if (g.x_periodic) {
-    long threads = (long)g.sy_v * 2 * g.H;
-    hipLaunchKernelGGL(k_fill_x, dim3((unsigned)((threads + 255) / 256), 4 + h2.n), b, 0, m->stream, g2, none, h2, 0,
-                       0);
-  }
-  LAUNCHCHK();
-  return GB25_OK;
-}
-
-// part: 0 = the whole extended range -H+1 .. Nx+H-2; 1 = the slab's own columns 0 .. Nx-2 (they read own columns
-// only: runs while the x-halo bundle travels); 2 = the two edge strips that part 1 left out.
-gb25_status compute_w_impl(gb25_model* m, int part = 0) {
+gb25_status compute_w_impl(gb25_model* m, Pass pass = Pass::Whole) {
   const Grid& g = m->g;
   Timed t(m, GB25_K_COMPUTE_W);
-  int ia = -g.H + 1, na = g.Nx + 2 * g.H - 2, ib = 0, nbcols = 0;
-  if (part == 1) {
-    ia = 0; na = g.Nx - 1;
-  } else if (part == 2) {
-    ia = -g.H + 1; na = g.H - 1; ib = g.Nx - 1; nbcols = g.H;
-  }
-  const int ey = g.Ny + 2 * g.H - 2;
-  // narrow strips: 16 columns x 16 rows per block instead of 64 x 4 (a 64-wide block would be three-quarters empty)
-  dim3 b = (na + nbcols) >= 64 ? dim3(64, 4) : dim3(16, 16);
+  const WColumns w = w_columns(pass, launch_facts(m));
+  const dim3 b(w.bx, w.by);
   const LazyCorr lz{m->corr[0].d, m->corr[1].d, m->wbase, m->g.sx * m->g.sy_v};
   auto kw = k_compute_w<false, false>;
   if (m->route.kernels_add_correction()) kw = k_compute_w<false, true>;
   else if (g.cv.on) kw = k_compute_w<true, false>;
-  hipLaunchKernelGGL(kw, grid2(na + nbcols, ey, b), b, 0, m->stream, g, m->f[GB25_U].d, m->f[GB25_V].d, m->f[GB25_W].d, ia,
-                     na, ib, nbcols, lz);
+  hipLaunchKernelGGL(kw, grid2(w.cols.ni, w.rows, b), b, 0, m->stream, g, m->f[GB25_U].d, m->f[GB25_V].d, m->f[GB25_W].d, w.cols.i0,
+                     w.cols.na(), w.cols.b0(), w.cols.nb(), lz);
   LAUNCHCHK();
   return GB25_OK;
 }
-// Hydrostatic pressure on columns [i_first, i_last] (default: the whole extended range -H+1 .. Nx+H-2; column
-// i_first - 1 is read as the west neighbour of the first x difference), optionally on a second range as well.
-gb25_status compute_p_impl(gb25_model* m, int i_first = INT_MIN, int i_last = INT_MIN, int i_first_b = 0,
-                           int i_last_b = -1, bool may_skip_p = false, int j_first = INT_MIN, int j_last = INT_MIN) {
+// Hydrostatic pressure and its differences on the columns and rows of `box`, in the form plan_pressure chooses (launch_plan.hpp).
+// may_skip_p: pHY' itself need not be stored (nobody reads it inside a composite step unless it is pinned).
+static_assert(PR == PRESSURE_ROWS, "the plan counts the rows per thread of k_compute_p<PR>");
+gb25_status compute_p_impl(gb25_model* m, PressureBox box, bool may_skip_p = false) {
   const Grid& g = m->g;
-  const real *Tsrc = m->f[GB25_T].d, *Ssrc = m->f[GB25_S].d;
-  real *dpx_out = m->dpx.d, *dpy_out = m->dpy.d;
   if (m->pressure_bits == 32) {
     // the model float type's own arithmetic, whole extended range, pHY' stored, differences from the stored values
     Timed t(m, GB25_K_COMPUTE_P);
@@ -1148,50 +1109,17 @@ gb25_status compute_p_impl(gb25_model* m, int i_first = INT_MIN, int i_last = IN
     LAUNCHCHK();
     return GB25_OK;
   }
-  real* n2 = nullptr;   // (CATKE's N^2 is SeawaterBuoyancy's dz_b -- alpha dzT - beta dzS -- not a difference of buoyancies: k_catke_n2)
   const bool write_p = !may_skip_p || m->phy_pinned;
   m->phy_stale = !write_p;
-  if (i_first == INT_MIN) {
-    i_first = -g.H + 1;
-    i_last = g.Nx + g.H - 2;
-  }
   Timed t(m, GB25_K_COMPUTE_P);
-  dim3 b(64, 4);
-  const int ncol = i_last - i_first + 2;   // written columns + the helper column
-  const int ncol_b = i_last_b >= i_first_b ? i_last_b - i_first_b + 2 : 0;
-  if (j_first == INT_MIN) {                // rows -H+1 .. Ny+H-2
-    j_first = -g.H + 1;
-    j_last = g.Ny + g.H - 2;
-  }
-  const int nrow = j_last - j_first + 1;
-  const int tiles_a = (ncol + 62) / 63, tiles_b = (ncol_b + 62) / 63;
-  // strips and narrow slabs: with four rows per thread a 180-column slab is 138 blocks on 256 CUs and the fp64 chains run at
-  // their latency (0.14 ms, against 0.31 ms for 1440 columns): one row per thread (4x the waves, 2.03 evaluations per cell).
-  // The narrowest of them on the lat-lon grid take the tile form: a wave = 16 columns x 4 rows, one evaluation per thread and
-  // level, 15 x 3 written cells (a block of four waves: 12 rows) -- 5.6x the waves of the four-row form, 1.42 evaluations per
-  // cell, rows of 64 B.  Same box, one rank alone: 180 columns 0.497 -> 0.484 ms per step, 360: 0.808 -> 0.794, the 4 x 2 mesh
-  // rank 0.518 -> 0.510; but 720 columns 1.358 -> 1.401 and the folded grid's slabs 0.614 -> 0.617 (180) and 0.978 -> 1.018 (360)
-  // beside their heavier curvilinear neighbours: those keep the one-row form.
-  const bool narrow = (tiles_a + tiles_b) * ((nrow + PR * 4 - 1) / (PR * 4)) < 1024;
-  // (option PRESSURE_FORM forces one form, on any grid: the kernels read no horizontal metric)
-  const int form = m->pressure_form ? m->pressure_form : (narrow && !g.cv.on && ncol + ncol_b <= 400) ? 1 : narrow ? 2 : 3;
-  if (form == 1) {
-    const int ta = (i_last - i_first + 1 + 14) / 15, tb = ncol_b ? (i_last_b - i_first_b + 1 + 14) / 15 : 0;
-    dim3 gr(ta + tb, (nrow + 11) / 12);
-    auto kern = write_p ? k_compute_p_tile<true> : k_compute_p_tile<false>;
-    hipLaunchKernelGGL(kern, gr, b, 0, m->stream, g, Tsrc, Ssrc, m->f[GB25_PHY].d, dpx_out, dpy_out, i_first, i_last,
-                       i_first_b, i_last_b, ta, n2, j_first, j_last);
-  } else if (form == 2) {
-    dim3 gr(tiles_a + tiles_b, (nrow + 3) / 4);
-    auto kern = write_p ? k_compute_p<1, true> : k_compute_p<1, false>;
-    hipLaunchKernelGGL(kern, gr, b, 0, m->stream, g, Tsrc, Ssrc, m->f[GB25_PHY].d, dpx_out, dpy_out, i_first, i_last,
-                       i_first_b, i_last_b, tiles_a, n2, j_first, j_last);
-  } else {
-    dim3 gr(tiles_a + tiles_b, (nrow + PR * 4 - 1) / (PR * 4));
-    auto kern = write_p ? k_compute_p<PR, true> : k_compute_p<PR, false>;
-    hipLaunchKernelGGL(kern, gr, b, 0, m->stream, g, Tsrc, Ssrc, m->f[GB25_PHY].d, dpx_out, dpy_out, i_first, i_last,
-                       i_first_b, i_last_b, tiles_a, n2, j_first, j_last);
-  }
+  const PressurePlan p = plan_pressure(box, launch_facts(m), m->pressure_form);
+  auto kern = write_p ? k_compute_p_tile<true> : k_compute_p_tile<false>;
+  if (p.form == 2) kern = write_p ? k_compute_p<1, true> : k_compute_p<1, false>;
+  if (p.form == 3) kern = write_p ? k_compute_p<PR, true> : k_compute_p<PR, false>;
+  const Cols& c = box.cols;
+  // (the kernels' N^2 output is unused: CATKE's N^2 is SeawaterBuoyancy's dz_b -- alpha dzT - beta dzS -- not a difference of buoyancies: k_catke_n2)
+  hipLaunchKernelGGL(kern, dim3(p.gx, p.gy), dim3(64, 4), 0, m->stream, g, m->f[GB25_T].d, m->f[GB25_S].d, m->f[GB25_PHY].d, m->dpx.d,
+                     m->dpy.d, c.i0, c.i0 + c.na() - 1, c.b0(), c.b0() + c.nb() - 1, p.tiles_a, (real*)nullptr, box.j_first, box.j_last);
   LAUNCHCHK();
   return GB25_OK;
 }
@@ -1243,13 +1171,13 @@ struct MomentumKernels {   // k_momentum_tendencies_v5
   static constexpr bool admits(bool a, bool i, bool c, bool l, bool d, bool w) { return momentum_variant(a, i, c, l, d, w); }
   template <bool... B> static kernel_t instance() { return k_momentum_tendencies_v5<MW, TYm, B...>; }
 };
-// part: see momentum_impl.  WFLY: w on the fly in a lazy step, or beside the corrector's sweep (memory holds the corrected
+// pass: see Pass (launch_plan.hpp).  WFLY: w on the fly in a lazy step, or beside the corrector's sweep (memory holds the corrected
 // velocities, only w is not read) -- in the passes over the whole domain
-std::array<bool, MomentumKernels::n> momentum_flags(const gb25_model* m, int part) {
+std::array<bool, MomentumKernels::n> momentum_flags(const gb25_model* m, Pass pass) {
   const bool ahead = m->ab2_ahead == 1 && !m->valid.ptr_exposed, curv = m->g.cv.on;
   const StepRoute& r = m->route;
   return {ahead, m->immersed || curv, curv, r.kernels_add_correction(), m->bottom_drag != 0,
-          ahead && r.kernels_carry_w() && (r.kernels_add_correction() || part == 0)};
+          ahead && r.kernels_carry_w() && (r.kernels_add_correction() || pass == Pass::Whole)};
 }
 
 struct TracerKernels {   // k_tracer_tendencies_v5; the flags O7: ORD = 7 (WENO(order = 7)), else 5; R2: ROWS = 2 (two rows per lane), else 1
@@ -1302,13 +1230,13 @@ std::array<bool, SingleKernels::n> single_flags(const gb25_model* m) {
   return {m->immersed || curv, curv, m->tracer_order == 7, m->route.kernels_carry_w()};
 }
 
-// part: 0 = every tile column; 1 = the interior tile columns (a12: launched before the x-halo bundle has arrived);
-//       2 = the edge tile columns, then whatever follows the complete evaluation (the look-ahead's finish kernel).
+// pass (launch_plan.hpp): every tile column; the interior tile columns (a12: launched before the x-halo bundle has arrived); the edge
+// tile columns, then whatever follows the complete evaluation (the look-ahead's finish kernel).
 gb25_status materialize_prev_uv(gb25_model* m);
-gb25_status momentum_impl(gb25_model* m, int part = 0) {
+gb25_status momentum_impl(gb25_model* m, Pass pass = Pass::Whole) {
   const Grid& g = m->g;
   int nbx, nb;
-  m->valid.tendency_kernel_runs(part != 2);   // look-aheads made from the previous tendencies are void
+  m->valid.tendency_kernel_runs(pass != Pass::Edges);   // look-aheads made from the previous tendencies are void
   if (m->kernel_gen >= 2) {
     Timed t(m, GB25_K_GU);   // the fused G_u + G_v kernel is accounted under the "gu" timer
     nbx = (g.Nx + V2_TX - 1) / V2_TX;
@@ -1316,14 +1244,14 @@ gb25_status momentum_impl(gb25_model* m, int part = 0) {
     const int nby = (v_rows(g) + TYm - 1) / TYm;   // (zipper fold: the y faces on the fold line have a tendency too)
     const int kchunks = mom_kchunks(m);
     TileCols tc{nbx, nbx, 0, 0};
-    if (part) {
+    if (pass != Pass::Whole) {
       const int hi = interior_tile_columns_end(g);
-      if (part == 1) tc = TileCols{hi - 1, hi - 1, 1, 0};
+      if (pass == Pass::Interior) tc = TileCols{hi - 1, hi - 1, 1, 0};
       else tc = TileCols{1 + nbx - hi, 1, 0, hi};
     }
     tc.cr = ChunkRange{0, kchunks, 0};
     nb = tc.n * nby * kchunks;
-    const std::array<bool, MomentumKernels::n> flags = momentum_flags(m, part);
+    const std::array<bool, MomentumKernels::n> flags = momentum_flags(m, pass);
     const bool ahead = flags[0];
     UvAhead nx{};
     const real dt = (real)m->last_dt, chi = (real)m->cfg.chi;
@@ -1339,8 +1267,8 @@ gb25_status momentum_impl(gb25_model* m, int part = 0) {
     }
     if (m->bottom_drag != 0) {
       // the bottom flux boundary condition of u, v from the (corrected) velocities this evaluation sees.  A slab's
-      // interior pass runs before the x halos arrive: face 0, the one that reads v of the west halo column, waits for part 2
-      const int i_first = part == 1 ? 1 : 0, n = part == 2 ? 1 : g.Nx - i_first;
+      // interior pass runs before the x halos arrive: face 0, the one that reads v of the west halo column, waits for the edge pass
+      const int i_first = pass == Pass::Interior ? 1 : 0, n = pass == Pass::Edges ? 1 : g.Nx - i_first;
       dim3 b(64, 4);
       hipLaunchKernelGGL(m->immersed ? k_bottom_drag_flux<true> : k_bottom_drag_flux<false>, grid2(n, v_rows(g), b), b, 0,
                          m->stream, g, m->f[GB25_U].d, m->f[GB25_V].d, m->d_bottom_flux[0], m->d_bottom_flux[1],
@@ -1348,7 +1276,7 @@ gb25_status momentum_impl(gb25_model* m, int part = 0) {
     }
     const LazyCorr lz{m->corr[0].d, m->corr[1].d, m->wbase, m->g.sx * m->g.sy_v};
     // (single domain: the kernel also writes the halo images of the next u, v; a slab's come with the next bundle)
-    if (m->route.memory_lacks_correction() && !(m->slab || (nx.fold && part == 0)))
+    if (m->route.memory_lacks_correction() && !(m->slab || (nx.fold && pass == Pass::Whole)))
       return fail(m, GB25_ERR_STATE, "internal: uncorrected velocities in a step whose momentum kernel cannot correct them");
     MomentumKernels::kernel_t k5;
     if (gb25_status s_ = tendency_instance<MomentumKernels>(m, flags, &k5)) return s_;
@@ -1376,7 +1304,7 @@ gb25_status momentum_impl(gb25_model* m, int part = 0) {
       }
     }
     t.stop();   // the timer covers the tendency kernel alone
-    if (ahead && part != 1) {
+    if (ahead && pass != Pass::Interior) {
       dim3 b(64, 4);
       hipLaunchKernelGGL(k_ab2_velocities_finish, grid2(g.Nx, v_rows(g), b), b, 0, m->stream, g, m->uv_partials, kchunks,
                          nx.plane2, m->ahead_G[0].d, m->ahead_G[1].d, m->ahead_colsum[0].d, m->ahead_colsum[1].d);
@@ -1385,7 +1313,7 @@ gb25_status momentum_impl(gb25_model* m, int part = 0) {
     LAUNCHCHK();
     return GB25_OK;
   }
-  if (part == 1) return GB25_OK;   // the direct-stencil kernels are not split: everything after the halos arrived
+  if (pass == Pass::Interior) return GB25_OK;   // the direct-stencil kernels are not split: everything after the halos arrived
   if (m->immersed || g.cv.on) return fail(m, GB25_ERR_STATE, "the direct-stencil kernels (GB25_OPT_KERNELS = 1) know neither immersed boundaries nor curvilinear grids");
   if (g.top_flux[0] || g.top_flux[1] || g.bottom_flux[0]) return fail(m, GB25_ERR_STATE, "the direct-stencil kernels (GB25_OPT_KERNELS = 1) know no flux boundary conditions");
   tile_grid(g, &nbx, &nb);
@@ -1445,7 +1373,7 @@ gb25_status tracers_impl(gb25_model* m) {
       // their halo cells come from the ordinary fill -- y / z layers, the rows beyond a zipper fold, the periodic x copy
       m->route.tracer_kernel_wrote_corrected();
       for (int q = 0; q < 2; q++) std::swap(m->f[GB25_U + q].d, m->uvc[q].d);
-      if (gb25_status s = fill_halos_impl(m, true, false, 1, 1)) return s;
+      if (gb25_status s = fill_halos_impl(m, FillRequest::uv(Columns::OwnWithPeriodicX))) return s;
     }
     return GB25_OK;
   }
@@ -2058,7 +1986,7 @@ gb25_status catke_diffusivities_impl(gb25_model* m) {
   if (!m->catke) return GB25_OK;
   gb25_status s;
   if ((s = catke_tke_step_impl(m))) return s;
-  if (!m->catke_stale_e_halos && (s = fill_halos_impl(m, true, false, 1, 4))) return s;
+  if (!m->catke_stale_e_halos && (s = fill_halos_impl(m, FillRequest::e(Columns::OwnWithPeriodicX)))) return s;
   return catke_diffusivities_finish_impl(m);
 }
 // what compute_tendencies! leaves in G^n.e: the SLOW tendency of e -- -div(u e) (one tracer, the two halves of the packed
@@ -2168,10 +2096,10 @@ gb25_status atmosphere_ocean_fluxes_impl(gb25_model* m) {
 gb25_status update_state_impl(gb25_model* m) {
   gb25_status s;
   if ((s = mask_impl(m))) return s;
-  if ((s = fill_halos_impl(m, true))) return s;
-  if (m->catke && (s = fill_halos_impl(m, true, false, 1, 4))) return s;   // the TKE tracer
+  if ((s = fill_halos_impl(m, FillRequest::everything_periodic_x()))) return s;
+  if (m->catke && (s = fill_halos_impl(m, FillRequest::e(Columns::OwnWithPeriodicX)))) return s;   // the TKE tracer
   if ((s = compute_w_impl(m))) return s;
-  if ((s = compute_p_impl(m))) return s;
+  if ((s = compute_p_impl(m, PressureBox::whole(launch_facts(m))))) return s;
   // (compute_diffusivities! ahead of the tendencies, as update_state! has them: neither reads what the other writes, and the
   // e step must have read CATKE's previous velocities before the momentum kernel's look-ahead reuses their buffers)
   if ((s = catke_update_impl(m))) return s;
@@ -2249,8 +2177,6 @@ inline bool route_carries_w(const gb25_model* m, Corrector c) {
 // The head of a step whose corrector is not the sweep: du, dv (k_corrector_2d) on the columns `c`, rows jr0 + [0, nj), in blocks of
 // shape b; the chunk bases of w (k_w_bases) on the columns `bases`; G^- <- G^n where `cache` says so.  An empty range (ni = 0) launches
 // nothing; the column integrals are used up once du, dv of the OWN columns are made (a slab's halo columns skip them).  The timer is the caller's.
-struct Cols { int i0, ni, skip_from, skip; };   // columns i0 + [0, ni) (from skip_from on: + skip)
-constexpr Cols NO_COLS{0, 0, INT_MAX, 0};
 gb25_status unswept_head(gb25_model* m, dim3 b, Cols c, int jr0, int nj, Cols bases, bool cache) {
   gb25_status s;
   if (c.ni > 0) {
@@ -2285,7 +2211,7 @@ gb25_status time_step_impl(gb25_model* m, int euler, bool more = false) {
     if ((s = ab2_step_impl(m, dt, euler))) return s;
     m->time += dt;
     m->iteration += 1;
-    if ((s = fill_halos_impl(m, true))) return s;
+    if ((s = fill_halos_impl(m, FillRequest::everything_periodic_x()))) return s;
     if ((s = corrector_impl(m, true))) return s;
     if ((s = update_state_impl(m))) return s;
     return atmosphere_ocean_fluxes_impl(m);
@@ -2324,12 +2250,12 @@ gb25_status time_step_impl(gb25_model* m, int euler, bool more = false) {
     OnStream on(m, side);
     if ((s = ab2_tracers_impl(m, (real)dt, chi))) return s;
     // y/z/x halos of T, S -- unless the look-ahead that was just adopted wrote them itself
-    if ((complete || !(ts_adopted && m->ahead_ts_folded)) && (s = fill_halos_impl(m, true, false, 1, 2))) return s;
+    if ((complete || !(ts_adopted && m->ahead_ts_folded)) && (s = fill_halos_impl(m, FillRequest::ts(Columns::OwnWithPeriodicX)))) return s;
     // (closure = CATKE: e is not stepped by ab2_step!; its halos were refilled after its step inside compute_diffusivities! --
     // unless the option keeps them stale there, as Oceananigans does as recalled: then they are filled here, with the others)
-    if (m->catke && m->catke_stale_e_halos && (s = fill_halos_impl(m, true, false, 1, 4))) return s;
+    if (m->catke && m->catke_stale_e_halos && (s = fill_halos_impl(m, FillRequest::e(Columns::OwnWithPeriodicX)))) return s;
     HIPCHK(hipEventRecord(m->ev_ts, side));
-    if ((s = compute_p_impl(m, INT_MIN, INT_MIN, 0, -1, true))) return s;
+    if ((s = compute_p_impl(m, PressureBox::whole(launch_facts(m)), true))) return s;
     if (adopted && (s = fill_halos_2d(m, hG))) return s;
   }
   HIPCHK(hipEventRecord(m->ev_join, side));
@@ -2396,8 +2322,9 @@ gb25_status time_step_impl(gb25_model* m, int euler, bool more = false) {
     // (through the tracer kernel: u, v get their halo cells behind that kernel, which writes their corrected interior: tracers_impl)
     const bool unswept = corrector == Corrector::InConsumers || corrector == Corrector::ThroughTracers;
     const bool uv_fresh = unswept || (producers_fold(m) && m->composite && !complete);
-    const int which = (uv_fresh ? 0 : 1) | ((eta_halos_fresh && !complete) ? 0 : 2);
-    if (which && (s = fill_halos_impl(m, true, false, which, 1))) return s;
+    const FillRequest stale{uv_fresh ? Fields3::None : Fields3::UV, (eta_halos_fresh && !complete) ? Fields2::None : Fields2::Prognostic,
+                            Columns::OwnWithPeriodicX};
+    if (!stale.empty() && (s = fill_halos_impl(m, stale))) return s;
   }
   if (!m->route.kernels_carry_w() && (s = compute_w_impl(m))) return s;
   if (corrector == Corrector::ThroughTracers && !m->tracers_first) return fail(m, GB25_ERR_STATE, "internal: the corrector through the tracer kernel needs the tracer kernel first");
@@ -2775,7 +2702,7 @@ gb25_status gb25_set_field(gb25_model* m, gb25_field f, const void* host, int in
 gb25_status gb25_get_field(gb25_model* m, gb25_field f, void* host_, int include_halos) {
   real* host = static_cast<real*>(host_);
   if (m && f == GB25_PHY && m->phy_stale) {   // the step stored only the differences: T, S are those it was made from
-    gb25_status s = compute_p_impl(m);
+    gb25_status s = compute_p_impl(m, PressureBox::whole(launch_facts(m)));
     if (s) return s;
   }
   return copy_field(m, f, host, include_halos, false);
@@ -2796,7 +2723,7 @@ gb25_status gb25_field_device_ptr(gb25_model* m, gb25_field id, void** dev) {
   if (id == GB25_PHY) {
     m->phy_pinned = true;
     if (m->phy_stale) {
-      gb25_status s = compute_p_impl(m);
+      gb25_status s = compute_p_impl(m, PressureBox::whole(launch_facts(m)));
       if (s) return s;
     }
   }
@@ -3010,12 +2937,12 @@ gb25_status gb25_get_bottom_info(const gb25_model* m, int32_t which, int32_t i, 
 gb25_status gb25_fill_halo_regions(gb25_model* m) {
   CHECK_MODEL(m);
   if (m->slab) return fail(m, GB25_ERR_STATE, "phase-by-phase driving is for single-domain models: a slab's x halos come from the exchange inside gb25_first_time_step / gb25_time_step / gb25_loop");
-  return fill_halos_impl(m, true);
+  return fill_halos_impl(m, FillRequest::everything_periodic_x());
 }
 gb25_status gb25_compute_auxiliaries(gb25_model* m) {
   CHECK_MODEL(m);
   gb25_status s = compute_w_impl(m);
-  if (!s) s = compute_p_impl(m);
+  if (!s) s = compute_p_impl(m, PressureBox::whole(launch_facts(m)));
   // (closure = CATKE: compute_diffusivities! is the third auxiliary -- it steps e and makes kappa_u, kappa_c, kappa_e, L^e, J^b)
   if (!s && m->catke && m->slab) return fail(m, GB25_ERR_STATE, "gb25_compute_auxiliaries with CATKE: phase-by-phase driving is for single-domain models");
   return s ? s : catke_diffusivities_impl(m);

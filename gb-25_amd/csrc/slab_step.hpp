@@ -302,11 +302,11 @@ inline bool strips_on_comm(const gb25_model* m) {
 gb25_status catke_step_local(gb25_model* m) {
   gb25_status s;
   if ((s = catke_tke_step_impl(m))) return s;
-  return fill_halos_impl(m, false, false, 1, 4);   // y/z layers of the new e on the own columns: the packed columns travel complete
+  return fill_halos_impl(m, FillRequest::e(Columns::Own));   // y/z layers of the new e on the own columns: the packed columns travel complete
 }
 gb25_status catke_finish_local(gb25_model* m) {
   gb25_status s;
-  if ((s = fill_halos_impl(m, false, true, 1, 4))) return s;   // y/z layers of e over the extended range (the halo rows' bottom / top layers)
+  if ((s = fill_halos_impl(m, FillRequest::e(Columns::Extended)))) return s;   // y/z layers of e over the extended range (the halo rows' bottom / top layers)
   if ((s = catke_diffusivities_finish_impl(m))) return s;
   return catke_tendency_impl(m);
 }
@@ -318,14 +318,13 @@ gb25_status catke_finish_local(gb25_model* m) {
 // (a rank of a 2-D decomposition computes its pressure in one pass once all halos are in: the early pass plus a one-row strip
 // for the y difference of row 0 measured slower on the one-rank proxy, 0.566 against 0.537 ms -- profiles/r03_tuning_log.md)
 inline bool pressure_early(const gb25_model* m) { return m->two_streams && m->pressure_bits == 64 && m->Ry == 1; }
-// Forks to the slab's side stream: the pressure of the columns [i0, i1] and [i0b, i1b] there, beside what the calling stream goes on
-// with; ev_join marks its end.
-gb25_status pressure_on_side_stream(gb25_model* m, int i0, int i1, int i0b, int i1b) {
+// Forks to the slab's side stream: the pressure of `box` there, beside what the calling stream goes on with; ev_join marks its end.
+gb25_status pressure_on_side_stream(gb25_model* m, PressureBox box) {
   HIPCHK(hipEventRecord(m->ev_fork, m->stream));
   HIPCHK(hipStreamWaitEvent(m->side_stream, m->ev_fork, 0));
   {
     OnStream on(m, m->side_stream);
-    if (gb25_status s = compute_p_impl(m, i0, i1, i0b, i1b, true)) return s;
+    if (gb25_status s = compute_p_impl(m, box, true)) return s;
   }
   HIPCHK(hipEventRecord(m->ev_join, m->side_stream));
   return GB25_OK;
@@ -334,7 +333,6 @@ gb25_status pressure_on_side_stream(gb25_model* m, int i0, int i1, int i0b, int 
 // Update: AB2 update of u,v,T,S + barotropic forcing, then the y/z boundary layers of the 3-D bundle so that its packed x columns
 // (Bundle) can travel WHILE the own columns are corrected
 gb25_status stage_update(gb25_model* m, int euler) {
-  const Grid& g = m->g;
   gb25_status s;
   const double dt = m->last_dt;
   const real chi = euler ? -real(0.5) : (real)m->cfg.chi;
@@ -357,11 +355,11 @@ gb25_status stage_update(gb25_model* m, int euler) {
     m->time += dt;
     m->iteration += 1;
   }
-  if ((s = fill_halos_impl(m, false, false, 1))) return s;
+  if ((s = fill_halos_impl(m, FillRequest::uvts(Columns::Own)))) return s;
   // T, S of the slab's own columns are final from here on: their pressure (fp64-bound) runs on the side stream beside the
   // exchanges and the sub-cycle; the strips next to the x halos follow in HaloColumns.  The first x difference of this pass reads
   // a stale halo column and is redone by the west strip.
-  return pressure_early(m) ? pressure_on_side_stream(m, 0, g.Nx - 1, 0, -1) : GB25_OK;
+  return pressure_early(m) ? pressure_on_side_stream(m, PressureBox::own_columns(launch_facts(m))) : GB25_OK;
 }
 
 // Subcycle: BaroWide has been unpacked into the wide halos: copy the interiors, sub-cycle, publish.
@@ -394,14 +392,14 @@ gb25_status stage_subcycle(gb25_model* m, bool ahead, bool substeps_only) {
     for (int q = 0; q < 3; q++) { h2.p[q] = m->ahead_eta[q].d; h2.is_v[q] = q == 2; }
     h2.n = 3;
     // y layer, x halo columns included: the widened sub-cycle computed those like the neighbour did (no BaroHaloAhead)
-    if (!done.layers_written && (s = fill_halos_impl(m, false, true, 2, 3, nullptr, true, &h2))) return s;
+    if (!done.layers_written && (s = fill_halos_impl(m, FillRequest::flat_extended(Fields2::Given), h2))) return s;
     m->valid.record_subcycle_lookahead();
     return GB25_OK;
   }
   m->time += dt;
   m->iteration += 1;
   // y layer of the new eta, U, V, x halo columns included (computed by the widened sub-cycle: no BaroHalo)
-  return done.layers_written ? GB25_OK : fill_halos_impl(m, false, true, 2);
+  return done.layers_written ? GB25_OK : fill_halos_impl(m, FillRequest::flat_extended());
 }
 
 // OwnColumns: everything that needs nothing from the neighbours runs while the exchanges are in flight: the barotropic corrector
@@ -431,18 +429,17 @@ gb25_status stage_own_columns(gb25_model* m, bool head_only) {
   }
   if (head_only || !tendencies_split(m)) return GB25_OK;
   // y/z layers of the corrected u, v, own columns (lazy: the layers of the uncorrected ones are in place since Update)
-  if (!lazy && (s = fill_halos_impl(m, false, false, 1, 1))) return s;
-  if (!wfly && (s = compute_w_impl(m, 1))) return s;
+  if (!lazy && (s = fill_halos_impl(m, FillRequest::uv(Columns::Own)))) return s;
+  if (!wfly && (s = compute_w_impl(m, Pass::Interior))) return s;
   HIPCHK(hipStreamWaitEvent(m->stream, m->ev_join, 0));       // the own columns' pressure differences (side stream)
-  return momentum_impl(m, 1);
+  return momentum_impl(m, Pass::Interior);
 }
 
 // StripsOnComm (issued on the exchange stream behind the unpack of Bundle): the two pressure strips: T, S of the halo columns are
 // in; the interior pass of Update (side stream: event ev_join) must be over -- the west strip redoes its column 0
 gb25_status stage_strips(gb25_model* m) {
-  const Grid& g = m->g;
   HIPCHK(hipStreamWaitEvent(m->stream, m->ev_join, 0));
-  if (gb25_status s = compute_p_impl(m, -g.H + 1, 0, g.Nx, g.Nx + g.H - 2, true)) return s;
+  if (gb25_status s = compute_p_impl(m, PressureBox::strips(launch_facts(m)), true)) return s;
   HIPCHK(hipEventRecord(m->ev_strips, m->stream));
   m->strips_issued = true;
   return GB25_OK;
@@ -468,7 +465,7 @@ gb25_status stage_halo_columns(gb25_model* m, bool first_part, bool second_part)
   const bool strips_done = m->strips_issued;   // (StripsOnComm ran them on the exchange stream)
   if (second_part) m->strips_issued = false;
   // west strip (redoes column 0) + east strip
-  auto pressure_strips = [&] { return pressure_on_side_stream(m, -g.H + 1, 0, g.Nx, g.Nx + g.H - 2); };
+  auto pressure_strips = [&] { return pressure_on_side_stream(m, PressureBox::strips(launch_facts(m))); };
   if (first_part) {
     // the two pressure strips next to the x halos start as soon as the bundle is unpacked: T, S of the halo columns arrived
     // complete (their y/z layers were filled by their owner before it packed them), and the side stream runs them behind the
@@ -497,19 +494,20 @@ gb25_status stage_halo_columns(gb25_model* m, bool first_part, bool second_part)
     }
     // (with the early strips T and S are left alone here: their layers are in place, own columns since Update)
     if (p_early && !strips_first) HIPCHK(hipStreamWaitEvent(m->stream, m->ev_join, 0));   // (the interior pass reads T, S)
-    if (!(lazy && strips_first) && (s = fill_halos_impl(m, false, true, 3, strips_first ? 1 : 3))) return s;
+    const FillRequest arrived{strips_first ? Fields3::UV : Fields3::UV | Fields3::TS, Fields2::Prognostic, Columns::Extended};
+    if (!(lazy && strips_first) && (s = fill_halos_impl(m, arrived))) return s;
     if (!second_part) return GB25_OK;
   }
   if (p_early && !strips_first && (s = pressure_strips())) return s;   // (beside w)
-  if (!wfly && (s = compute_w_impl(m, split ? 2 : 0))) return s;
+  if (!wfly && (s = compute_w_impl(m, split ? Pass::Edges : Pass::Whole))) return s;
   if (strips_done) {
     HIPCHK(hipStreamWaitEvent(m->stream, m->ev_strips, 0));
   } else if (p_early) {
     HIPCHK(hipStreamWaitEvent(m->stream, m->ev_join, 0));
   } else {
-    if ((s = compute_p_impl(m))) return s;
+    if ((s = compute_p_impl(m, PressureBox::whole(launch_facts(m))))) return s;
   }
-  return momentum_impl(m, split ? 2 : 0);
+  return momentum_impl(m, split ? Pass::Edges : Pass::Whole);
 }
 
 // Tracers: the tracer tendencies; the look-ahead of the next sub-cycle (BaroWideAhead, SubcycleAhead) runs beside them
@@ -547,9 +545,9 @@ gb25_status slab_stage(gb25_model* m, Stage stage, int euler) {
 gb25_status update_state_local_impl(gb25_model* m) {   // update_state! without the x-halo fill
   gb25_status s;
   if ((s = mask_impl(m))) return s;   // (own columns; the halo columns arrived masked by their owners)
-  if ((s = fill_halos_impl(m, false, m->slab))) return s;
+  if ((s = fill_halos_impl(m, FillRequest::everything(m->slab ? Columns::Extended : Columns::Own)))) return s;
   if ((s = compute_w_impl(m))) return s;
-  if ((s = compute_p_impl(m))) return s;
+  if ((s = compute_p_impl(m, PressureBox::whole(launch_facts(m))))) return s;
   if ((s = momentum_impl(m))) return s;
   if ((s = tracers_impl(m))) return s;
   return m->catke ? catke_step_local(m) : GB25_OK;   // (the sequencer goes on with the Catke groups and catke_finish_local)
@@ -1150,14 +1148,14 @@ struct GroupOps : StepOps {
     gb25_status s_;
     switch (what) {
       case Initialize: return initialize_impl(m);
-      case FillLocal: return fill_halos_impl(m, false);
+      case FillLocal: return fill_halos_impl(m, FillRequest::everything(Columns::Own));
       case UpdateStateLocal: return update_state_local_impl(m);
       case MaskFillLocal:
         if ((s_ = mask_impl(m))) return s_;
-        return fill_halos_impl(m, false, true);
+        return fill_halos_impl(m, FillRequest::everything(Columns::Extended));
       case AuxiliariesTendenciesLocal:
         if ((s_ = compute_w_impl(m))) return s_;
-        if ((s_ = compute_p_impl(m))) return s_;
+        if ((s_ = compute_p_impl(m, PressureBox::whole(launch_facts(m))))) return s_;
         [[fallthrough]];
       case TendenciesLocal:
         if ((s_ = momentum_impl(m))) return s_;

@@ -23,6 +23,7 @@
 #include "subcycle_plan.hpp"
 #include "model_layout.hpp"
 #include "launch_plan.hpp"
+#include "tendency_plan.hpp"
 
 #include <cmath>
 #include <cstdarg>
@@ -1031,7 +1032,8 @@ inline int v_rows(const Grid& g) { return g.Ny; }
 inline LaunchFacts launch_facts(const gb25_model* m) {
   const Grid& g = m->g;
   return {g.Nx, g.Ny, g.Nz, g.H, g.sy_c, g.sy_v, g.x_periodic != 0, g.cv.north_fold != 0, g.cv.pivot_slaved, m->slab, m->ys_open, m->yn_open,
-          m->fill_fused != 0, g.cv.on != 0};
+          m->fill_fused != 0, g.cv.on != 0, g.pl_c, g.pl_v, (long)m->f[GB25_W].elems(), (int)sizeof(real), m->mom_chunk_levels,
+          m->trc_chunk_levels, v_rows(g), m->Ry, m->immersed != 0, m->tracer_order, m->tracer_rows_forced};
 }
 
 // Binds the model's arrays to a fill request, plans it (plan_fill) and issues the planned launches in order on the model's stream.
@@ -1130,15 +1132,10 @@ void tile_grid(const Grid& g, int* nbx, int* nb) {
   *nb = *nbx * nby * g.Nz;
 }
 
-// Tile columns of the momentum kernel that read the slab's own columns only (u, v up to 3 columns, w up to 2 columns
-// away): [1, bx_hi).  Empty when the slab is too narrow.
-inline int interior_tile_columns_end(const Grid& g) {
-  const int nbx = (g.Nx + V2_TX - 1) / V2_TX;
-  return std::max(1, std::min(nbx - 1, (g.Nx - 3) / V2_TX));
-}
+// the options' half of the split of a slab's tendencies into the Interior and Edges passes; the geometry's: momentum_splittable
 inline bool tendencies_split(const gb25_model* m) {
   return m->slab && m->split_tendencies && m->two_streams && m->pressure_bits == 64 && m->kernel_gen >= 2 &&
-         interior_tile_columns_end(m->g) > 1 && !m->g.cv.north_fold && m->Ry == 1;   // (the rows beyond a fold / of a neighbour in y arrive last)
+         momentum_splittable(launch_facts(m));
 }
 
 // ---- which template instance of a tendency kernel runs.  A family's flags are in the order of the kernel's template
@@ -1163,9 +1160,8 @@ gb25_status tendency_instance(gb25_model* m, const std::array<bool, Fam::n>& f, 
 
 struct MomentumKernels {   // k_momentum_tendencies_v5
   // waves/SIMD the register allocator is held to: 4 (128 VGPRs) in fp32; fp64 operands are register pairs,
-  // so the Float64 build asks for 2 (256 VGPRs) instead of spilling.  TYm: rows (= waves) per block: 4 blocks per CU cover
-  // each other's barriers
-  static constexpr int MW = sizeof(real) == 8 ? 2 : 4, TYm = 4, n = 6;
+  // so the Float64 build asks for 2 (256 VGPRs) instead of spilling.  TYm: rows (= waves) per block (tile_sizes.hpp)
+  static constexpr int MW = sizeof(real) == 8 ? 2 : 4, TYm = MOMENTUM_TY, n = 6;
   static constexpr const char* name = "momentum (AHEAD IMM CURV LAZY DRAG WFLY)";
   using kernel_t = decltype(&k_momentum_tendencies_v5<MW, TYm, false, false>);
   static constexpr bool admits(bool a, bool i, bool c, bool l, bool d, bool w) { return momentum_variant(a, i, c, l, d, w); }
@@ -1196,19 +1192,7 @@ struct TracerKernels {   // k_tracer_tendencies_v5; the flags O7: ORD = 7 (WENO(
   template <bool A, bool I, bool F, bool C, bool L, bool O7, bool W, bool WC, bool R2>
   static kernel_t instance() { return k_tracer_tendencies_v5<R2 ? TW2 : O7 ? TW7 : TW, A, I, F, C, L, O7 ? 7 : 5, W, WC, R2 ? 2 : 1>; }
 };
-// Rows per lane of the tracer kernel (tracer_tile_rows2, tendency_kernels.hpp).  Two where the instance exists (flat grid, order 5),
-// the launch covers a whole single domain -- a slab or a rank of a mesh keeps one, so that the bitwise comparisons of a decomposition
-// with the single domain compare the two forms --, the model is Float32 (Float64: 252 VGPRs, two waves, the launch 5 % slower) and the
-// blocks of 8 rows still number TRACER_ROWS2_MIN_BLOCKS: measured 1440 x 720 x 48 (4140 blocks) +1 % steps/s, 720 x 720 x 48 (2160)
-// +-0, 720 x 360 x 48 (2160 of 12 levels) -1.7 %, 360 x 360 x 48 -4 %.  GB25_TRACER_ROWS = 1 | 2 in the
-// environment of gb25_create forces the value wherever the instance exists.
-constexpr long TRACER_ROWS2_MIN_BLOCKS = 4096;
-int tracer_rows(const gb25_model* m, int nbx, int kchunks) {
-  const bool exists = !m->immersed && !m->g.cv.on && m->tracer_order == 5;
-  if (!exists || m->tracer_rows_forced == 1) return 1;
-  if (m->tracer_rows_forced == 2) return 2;
-  return (!m->slab && sizeof(real) == 4 && (long)nbx * ((m->g.Ny + 7) / 8) * kchunks >= TRACER_ROWS2_MIN_BLOCKS) ? 2 : 1;
-}
+// rows: the rows per lane plan_tracers chose.
 // WCORR: the corrector through the tracer kernel -- it adds du, dv as it loads (LAZY) and writes the corrected u, v; the halo
 // cells of the next T, S are then left to the fill (no FOLD)
 std::array<bool, TracerKernels::n> tracer_flags(const gb25_model* m, int rows) {
@@ -1239,18 +1223,8 @@ gb25_status momentum_impl(gb25_model* m, Pass pass = Pass::Whole) {
   m->valid.tendency_kernel_runs(pass != Pass::Edges);   // look-aheads made from the previous tendencies are void
   if (m->kernel_gen >= 2) {
     Timed t(m, GB25_K_GU);   // the fused G_u + G_v kernel is accounted under the "gu" timer
-    nbx = (g.Nx + V2_TX - 1) / V2_TX;
-    constexpr int TYm = MomentumKernels::TYm;
-    const int nby = (v_rows(g) + TYm - 1) / TYm;   // (zipper fold: the y faces on the fold line have a tendency too)
-    const int kchunks = mom_kchunks(m);
-    TileCols tc{nbx, nbx, 0, 0};
-    if (pass != Pass::Whole) {
-      const int hi = interior_tile_columns_end(g);
-      if (pass == Pass::Interior) tc = TileCols{hi - 1, hi - 1, 1, 0};
-      else tc = TileCols{1 + nbx - hi, 1, 0, hi};
-    }
-    tc.cr = ChunkRange{0, kchunks, 0};
-    nb = tc.n * nby * kchunks;
+    const MomentumPlan p = plan_momentum(pass, launch_facts(m));
+    TileCols tc{p.n, p.nlead, p.bx0, p.bx1};
     const std::array<bool, MomentumKernels::n> flags = momentum_flags(m, pass);
     const bool ahead = flags[0];
     UvAhead nx{};
@@ -1266,13 +1240,11 @@ gb25_status momentum_impl(gb25_model* m, Pass pass = Pass::Whole) {
       nx.fold = (producers_fold(m) && !m->immersed) ? 1 : 0;   // (with a bottom the corrector's own halo writes do it)
     }
     if (m->bottom_drag != 0) {
-      // the bottom flux boundary condition of u, v from the (corrected) velocities this evaluation sees.  A slab's
-      // interior pass runs before the x halos arrive: face 0, the one that reads v of the west halo column, waits for the edge pass
-      const int i_first = pass == Pass::Interior ? 1 : 0, n = pass == Pass::Edges ? 1 : g.Nx - i_first;
+      // the bottom flux boundary condition of u, v from the (corrected) velocities this evaluation sees
       dim3 b(64, 4);
-      hipLaunchKernelGGL(m->immersed ? k_bottom_drag_flux<true> : k_bottom_drag_flux<false>, grid2(n, v_rows(g), b), b, 0,
+      hipLaunchKernelGGL(m->immersed ? k_bottom_drag_flux<true> : k_bottom_drag_flux<false>, grid2(p.drag_n, v_rows(g), b), b, 0,
                          m->stream, g, m->f[GB25_U].d, m->f[GB25_V].d, m->d_bottom_flux[0], m->d_bottom_flux[1],
-                         (real)m->bottom_drag, i_first, n);
+                         (real)m->bottom_drag, p.drag_i_first, p.drag_n);
     }
     const LazyCorr lz{m->corr[0].d, m->corr[1].d, m->wbase, m->g.sx * m->g.sy_v};
     // (single domain: the kernel also writes the halo images of the next u, v; a slab's come with the next bundle)
@@ -1280,33 +1252,23 @@ gb25_status momentum_impl(gb25_model* m, Pass pass = Pass::Whole) {
       return fail(m, GB25_ERR_STATE, "internal: uncorrected velocities in a step whose momentum kernel cannot correct them");
     MomentumKernels::kernel_t k5;
     if (gb25_status s_ = tendency_instance<MomentumKernels>(m, flags, &k5)) return s_;
-    if (nb > 0) {
-      // The kernel's per-lane offsets are 32-bit BYTE offsets from the array pointers.  An array beyond that reach (4.4 GB per
-      // field for config 5 as one domain) takes several launches, each a run of chunks of levels whose planes -- stencil and
-      // halo layers included -- lie within 2 GB of pointers rebased by `kofs` planes.  Normally: one launch, kofs = 0.
-      const int klen = (g.Nz + kchunks - 1) / kchunks;
-      const double plane_bytes = (double)g.pl_v * sizeof(real), reach = 2147483648.0;
-      const bool small = (double)m->f[GB25_W].elems() * sizeof(real) < reach;
-      for (int c0 = 0; c0 < kchunks;) {
-        // the lowest plane a run starting with chunk c0 touches: three levels below its first one, or a bottom halo layer
-        const int kofs = small ? 0 : std::max(0, c0 * klen + g.H - 4);
-        int c1 = c0 + 1;   // (a run takes every following chunk whose highest plane -- window, w, top halo layer -- is within reach)
-        while (c1 < kchunks && (std::min(g.Nz, (c1 + 1) * klen) + g.H + 5 - kofs) * plane_bytes < reach) c1++;
-        tc.cr = ChunkRange{c0, c1 - c0, kofs};
-        const long oc_ = (long)g.pl_c * kofs, ov_ = (long)g.pl_v * kofs;
-        UvAhead nr = nx;
-        if (ahead) { nr.GmU += oc_; nr.GmV += ov_; nr.un += oc_; nr.vn += ov_; }
-        const int nbr = tc.n * nby * (c1 - c0);
-        hipLaunchKernelGGL(k5, dim3(nbr), dim3(V2_TX, TYm), 0, m->stream, g, m->f[GB25_U].d + oc_, m->f[GB25_V].d + ov_,
-                           m->f[GB25_W].d + oc_, m->dpx.d + oc_, m->dpy.d + oc_, m->f[GB25_GN_U].d + oc_, m->f[GB25_GN_V].d + ov_,
-                           tc, kchunks, nbr, nr, lz);
-        c0 = c1;
-      }
+    // one launch per run of chunks of levels within the kernel's reach (tendency_plan.hpp).  Normally: one launch, kofs = 0
+    for (int c0 = 0; p.nb() > 0 && c0 < p.kchunks;) {
+      const ChunkRun run = chunk_run(p.chunks, c0);
+      tc.cr = ChunkRange{run.first, run.count, run.kofs};
+      const long oc_ = (long)g.pl_c * run.kofs, ov_ = (long)g.pl_v * run.kofs;
+      UvAhead nr = nx;
+      if (ahead) { nr.GmU += oc_; nr.GmV += ov_; nr.un += oc_; nr.vn += ov_; }
+      const int nbr = p.n * p.nby * run.count;
+      hipLaunchKernelGGL(k5, dim3(nbr), dim3(V2_TX, MomentumKernels::TYm), 0, m->stream, g, m->f[GB25_U].d + oc_, m->f[GB25_V].d + ov_,
+                         m->f[GB25_W].d + oc_, m->dpx.d + oc_, m->dpy.d + oc_, m->f[GB25_GN_U].d + oc_, m->f[GB25_GN_V].d + ov_,
+                         tc, p.kchunks, nbr, nr, lz);
+      c0 = run.first + run.count;
     }
     t.stop();   // the timer covers the tendency kernel alone
-    if (ahead && pass != Pass::Interior) {
+    if (ahead && p.finish) {
       dim3 b(64, 4);
-      hipLaunchKernelGGL(k_ab2_velocities_finish, grid2(g.Nx, v_rows(g), b), b, 0, m->stream, g, m->uv_partials, kchunks,
+      hipLaunchKernelGGL(k_ab2_velocities_finish, grid2(g.Nx, v_rows(g), b), b, 0, m->stream, g, m->uv_partials, p.kchunks,
                          nx.plane2, m->ahead_G[0].d, m->ahead_G[1].d, m->ahead_colsum[0].d, m->ahead_colsum[1].d);
       m->valid.record_velocity_lookahead(dt, chi);
     }
@@ -1337,12 +1299,8 @@ gb25_status tracers_impl(gb25_model* m) {
   m->valid.tendency_kernel_runs(false);
   if (m->kernel_gen >= 2) {
     Timed t(m, GB25_K_TRACERS);
-    nbx = (g.Nx + V3_OUT - 1) / V3_OUT;
-    const int kchunks = trc_kchunks(m);
-    const int rows = tracer_rows(m, nbx, kchunks);
-    const int nby = (g.Ny + 4 * rows - 1) / (4 * rows);   // (a block: four waves of `rows` rows each)
-    nb = nbx * nby * kchunks;
-    const std::array<bool, TracerKernels::n> flags = tracer_flags(m, rows);
+    const TracerPlan p = plan_tracers(launch_facts(m));
+    const std::array<bool, TracerKernels::n> flags = tracer_flags(m, p.rows);
     const bool ahead = flags[0], fold = flags[2];
     Ab2Ahead nx{};
     if (ahead) {   // predicted parameters of the next ab2_step!: the clock's dt and the model's chi
@@ -1363,9 +1321,9 @@ gb25_status tracers_impl(gb25_model* m) {
       nx.vc = m->uvc[1].d;
     }
     m->ahead_ts_folded = fold;
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(64, 4), 0, m->stream, g, m->f[GB25_U].d,
+    hipLaunchKernelGGL(kern, dim3(p.nb), dim3(64, 4), 0, m->stream, g, m->f[GB25_U].d,
                        m->f[GB25_V].d, m->f[GB25_W].d, m->f[GB25_T].d, m->f[GB25_S].d, m->f[GB25_GN_T].d,
-                       m->f[GB25_GN_S].d, nbx, kchunks, nb, nx, lz);
+                       m->f[GB25_GN_S].d, p.nbx, p.kchunks, p.nb, nx, lz);
     LAUNCHCHK();
     m->valid.record_tracer_lookahead(ahead, nx.dt, (real)m->cfg.chi);
     if (wcorr) {
@@ -1794,71 +1752,50 @@ void cache_previous_tendencies(gb25_model* m) {
   for (int q = 0; q < 4; q++) std::swap(m->f[GB25_GN_U + q].d, m->f[GB25_GM_U + q].d);
   m->valid.void_lookaheads();   // the look-aheads used the tendency pairs as they were before
 }
-// the corrector inside its consumers: du, dv (k_corrector_2d) on columns i0 + [0, ni) (from skip_from on: + skip), rows jr0 + [0, nj)
-gb25_status corrector_2d_impl(gb25_model* m, dim3 b, int i0, int ni, int skip_from, int skip, int jr0, int nj) {
-  hipLaunchKernelGGL(m->immersed ? k_corrector_2d<true> : k_corrector_2d<false>, grid2(ni, nj, b), b, 0, m->stream, m->g,
+// the corrector inside its consumers: du, dv (k_corrector_2d) on the columns c, rows jr0 + [0, nj)
+gb25_status corrector_2d_impl(gb25_model* m, dim3 b, Cols c, int jr0, int nj) {
+  hipLaunchKernelGGL(m->immersed ? k_corrector_2d<true> : k_corrector_2d<false>, grid2(c.ni, nj, b), b, 0, m->stream, m->g,
                      m->f[GB25_BT_U].d, m->f[GB25_BT_V].d, m->colsum[0].d, m->colsum[1].d, m->f[GB25_U_BAR].d, m->f[GB25_V_BAR].d,
-                     m->corr[0].d, m->corr[1].d, i0, ni, skip_from, skip, jr0, nj);
+                     m->corr[0].d, m->corr[1].d, c.i0, c.ni, c.skip_from, c.skip, jr0, nj);
   LAUNCHCHK();
   return GB25_OK;
 }
-// w on the fly: w at the chunk boundaries (k_w_bases) on columns i0 + [0, ni) (from skip_from on: + skip), rows -2 .. Ny + 1
-gb25_status w_bases_impl(gb25_model* m, dim3 b, int i0, int ni, int skip_from, int skip) {
+// w on the fly: w at the chunk boundaries (k_w_bases) on the columns c, rows -2 .. Ny + 1
+gb25_status w_bases_impl(gb25_model* m, dim3 b, Cols c) {
   const Grid& g = m->g;
   auto kb = g.cv.on ? k_w_bases<true, true> : (m->immersed ? k_w_bases<true, false> : k_w_bases<false, false>);
-  hipLaunchKernelGGL(kb, grid2(ni, g.Ny + 4, b), b, 0, m->stream, g, m->uv_partials, mom_kchunks(m), g.sx * g.sy_v,
-                     LazyCorr{m->corr[0].d, m->corr[1].d, nullptr, 0}, m->wbase, i0, ni, skip_from, skip);
+  hipLaunchKernelGGL(kb, grid2(c.ni, g.Ny + 4, b), b, 0, m->stream, g, m->uv_partials, mom_kchunks(m), g.sx * g.sy_v,
+                     LazyCorr{m->corr[0].d, m->corr[1].d, nullptr, 0}, m->wbase, c.i0, c.ni, c.skip_from, c.skip);
   LAUNCHCHK();
   return GB25_OK;
 }
 
-// use_colsum: only inside a composite time step, where nothing can have touched u, v since the AB2 kernel.
-// part: 0 = every column this model corrects (a slab of a decomposition includes its x-halo columns);
-//       1 = the slab's own columns only (needs no halo data: runs while the last exchanges are in flight);
-//       2 = the x-halo columns only.  The G^n/G^- exchange happens once, with part 0 or 1.
-gb25_status corrector_impl(gb25_model* m, bool use_colsum = false, int part = 0) {
+// The barotropic corrector on the columns the request names, in the form plan_corrector chooses (tendency_plan.hpp)
+gb25_status corrector_impl(gb25_model* m, CorrectorRequest rq) {
   const Grid& g = m->g;
   {
     Timed t(m, GB25_K_CORRECTOR);
-    dim3 b(64, 4);
-    const bool ext = m->slab;
-    int i0 = ext ? -g.H : 0, ni = ext ? g.Nx + 2 * g.H : g.Nx, skip_from = INT_MAX, skip = 0;
-    if (part == 1) {
-      i0 = 0;
-      ni = g.Nx;
-    } else if (part == 2) {
-      if (!ext) return GB25_OK;
-      i0 = -g.H; ni = 2 * g.H; skip_from = 0; skip = g.Nx;
+    const CorrectorPlan p = plan_corrector(rq, launch_facts(m), m->valid.colsum_valid, m->valid.halo_colsum_valid);
+    if (p.form == CorrectorForm::Nothing) return GB25_OK;
+    const dim3 b(64, 4);
+    const Cols& c = p.cols;
+    if (p.form == CorrectorForm::Cells) {
+      hipLaunchKernelGGL(m->immersed ? k_corrector_cells<true> : k_corrector_cells<false>,
+                         dim3((c.ni + 63) / 64, (p.nj + 3) / 4, g.Nz), b, 0, m->stream, g, m->f[GB25_U].d, m->f[GB25_V].d,
+                         m->f[GB25_BT_U].d, m->f[GB25_BT_V].d, m->f[GB25_U_BAR].d, m->f[GB25_V_BAR].d, m->colsum[0].d,
+                         m->colsum[1].d, c.i0, c.ni, c.skip_from, c.skip, p.j0, p.nj, INT_MAX, 0);
+    } else {
+      const bool fold = producers_fold(m) && m->composite, leaves = m->route.sweep_leaves_increments();
+      auto kern = m->immersed ? (fold ? k_corrector<true, true> : k_corrector<true, false>)
+                              : (fold ? k_corrector<false, true> : k_corrector<false, false>);
+      hipLaunchKernelGGL(kern, grid2(c.ni, p.nj, b), b, 0, m->stream, g, m->f[GB25_U].d, m->f[GB25_V].d,
+                         m->f[GB25_BT_U].d, m->f[GB25_BT_V].d, m->f[GB25_U_BAR].d, m->f[GB25_V_BAR].d,
+                         p.reads_colsum ? m->colsum[0].d : nullptr, p.reads_colsum ? m->colsum[1].d : nullptr, c.i0, c.ni, mom_kchunks(m),
+                         c.skip_from, c.skip, p.j0, p.nj, INT_MAX, 0, leaves ? m->corr[0].d : nullptr, leaves ? m->corr[1].d : nullptr);
     }
-    const bool cs = use_colsum && m->valid.colsum_valid && part != 2;
-    const bool fold = producers_fold(m) && m->composite;
-    // one thread per cell where the column integrals are at hand: the own columns of a slab, and its x-halo columns when
-    // the integrals came with the 3-D bundle (group 0 carries the owner's; marching 16 columns x Ny threads up 48 levels
-    // for them was 36 us of latency on the critical path of a 180-column rank)
-    const bool cells_halo = m->slab && part == 2 && use_colsum && m->valid.halo_colsum_valid;
-    const bool cells = (m->slab && part == 1 && cs) || cells_halo;
-    real* const du = m->route.sweep_leaves_increments() ? m->corr[0].d : nullptr;
-    real* const dv = m->route.sweep_leaves_increments() ? m->corr[1].d : nullptr;
-    auto launch = [&](int i0_, int ni_, int skf, int sk, int jr0, int nj, int jskf, int jsk) {
-      if (cells) {
-        hipLaunchKernelGGL(m->immersed ? k_corrector_cells<true> : k_corrector_cells<false>,
-                           dim3((ni_ + 63) / 64, (nj + 3) / 4, g.Nz), b, 0, m->stream, g, m->f[GB25_U].d, m->f[GB25_V].d,
-                           m->f[GB25_BT_U].d, m->f[GB25_BT_V].d, m->f[GB25_U_BAR].d, m->f[GB25_V_BAR].d, m->colsum[0].d,
-                           m->colsum[1].d, i0_, ni_, skf, sk, jr0, nj, jskf, jsk);
-      } else {
-        auto kern = m->immersed ? (fold ? k_corrector<true, true> : k_corrector<true, false>)
-                                : (fold ? k_corrector<false, true> : k_corrector<false, false>);
-        hipLaunchKernelGGL(kern, grid2(ni_, nj, b), b, 0, m->stream, g, m->f[GB25_U].d, m->f[GB25_V].d,
-                           m->f[GB25_BT_U].d, m->f[GB25_BT_V].d, m->f[GB25_U_BAR].d, m->f[GB25_V_BAR].d,
-                           cs ? m->colsum[0].d : nullptr, cs ? m->colsum[1].d : nullptr, i0_, ni_, mom_kchunks(m),
-                           skf, sk, jr0, nj, jskf, jsk, du, dv);
-      }
-    };
-    // rows: the own ones (the halo rows of a rank of a 2-D decomposition arrive corrected: group 10 travels after this)
-    launch(i0, ni, skip_from, skip, 0, g.Ny, INT_MAX, 0);
     LAUNCHCHK();
+    if (!p.caches) return GB25_OK;
   }
-  if (part == 2) return GB25_OK;
   m->valid.void_colsums();
   cache_previous_tendencies(m);
   return GB25_OK;
@@ -1996,13 +1933,12 @@ gb25_status catke_tendency_impl(gb25_model* m) {
   Timed t_closure(m, GB25_K_CLOSURE);
   const Grid& g = m->g;
   {
-    const int nbx = (g.Nx + V3_PAIR - 1) / V3_PAIR, nby = (g.Ny + 3) / 4, kchunks = trc_kchunks(m);
-    const int nb = nbx * nby * kchunks;
+    const TracerPlan p = plan_single(launch_facts(m));
     SingleKernels::kernel_t kt;
     if (gb25_status s_ = tendency_instance<SingleKernels>(m, single_flags(m), &kt)) return s_;
     const LazyCorr lz{m->corr[0].d, m->corr[1].d, m->wbase, g.sx * g.sy_v};
-    hipLaunchKernelGGL(kt, dim3(nb), dim3(64, 4), 0, m->stream, g, m->f[GB25_U].d, m->f[GB25_V].d, m->f[GB25_W].d, m->f[GB25_E].d,
-                       m->f[GB25_GN_E].d, nbx, kchunks, nb, lz);
+    hipLaunchKernelGGL(kt, dim3(p.nb), dim3(64, 4), 0, m->stream, g, m->f[GB25_U].d, m->f[GB25_V].d, m->f[GB25_W].d, m->f[GB25_E].d,
+                       m->f[GB25_GN_E].d, p.nbx, p.kchunks, p.nb, lz);
   }
   dim3 b(64, 4);
   hipLaunchKernelGGL(k_catke_add_top_source, grid2(g.Nx, g.Ny, b), b, 0, m->stream, g, m->catke_src.d, m->f[GB25_GN_E].d);
@@ -2174,22 +2110,23 @@ inline bool route_carries_w(const gb25_model* m, Corrector c) {
   return c != Corrector::Sweep;
 }
 
-// The head of a step whose corrector is not the sweep: du, dv (k_corrector_2d) on the columns `c`, rows jr0 + [0, nj), in blocks of
-// shape b; the chunk bases of w (k_w_bases) on the columns `bases`; G^- <- G^n where `cache` says so.  An empty range (ni = 0) launches
-// nothing; the column integrals are used up once du, dv of the OWN columns are made (a slab's halo columns skip them).  The timer is the caller's.
-gb25_status unswept_head(gb25_model* m, dim3 b, Cols c, int jr0, int nj, Cols bases, bool cache) {
+// The head of a step whose corrector is not the sweep, as the request names it (HeadRequest, tendency_plan.hpp): du, dv, the chunk
+// bases of w, G^- <- G^n.  An empty range (ni = 0) launches nothing; the column integrals are used up once du, dv of the OWN columns
+// are made (a slab's halo columns skip them).  The timer is the caller's.
+gb25_status unswept_head(gb25_model* m, const HeadRequest& rq) {
   gb25_status s;
-  if (c.ni > 0) {
-    if ((s = corrector_2d_impl(m, b, c.i0, c.ni, c.skip_from, c.skip, jr0, nj))) return s;
-    if (c.skip == 0) m->valid.void_colsums();
+  const dim3 b(rq.bx, rq.by);
+  if (rq.cols.ni > 0) {
+    if ((s = corrector_2d_impl(m, b, rq.cols, rq.j0, rq.nj))) return s;
+    if (rq.cols.skip == 0) m->valid.void_colsums();
   }
   // (through the tracer kernel: memory lacks du, dv only until that kernel has run, and no other kernel reads u, v before it)
   if (!m->route.tracer_kernel_corrects()) m->route.correction_left_in_2d();
-  if (bases.ni > 0) {
-    if ((s = w_bases_impl(m, b, bases.i0, bases.ni, bases.skip_from, bases.skip))) return s;
+  if (rq.bases.ni > 0) {
+    if ((s = w_bases_impl(m, b, rq.bases))) return s;
     m->route.w_carried_in_kernels();
   }
-  if (cache) cache_previous_tendencies(m);
+  if (rq.cache) cache_previous_tendencies(m);
   return GB25_OK;
 }
 
@@ -2212,7 +2149,7 @@ gb25_status time_step_impl(gb25_model* m, int euler, bool more = false) {
     m->time += dt;
     m->iteration += 1;
     if ((s = fill_halos_impl(m, FillRequest::everything_periodic_x()))) return s;
-    if ((s = corrector_impl(m, true))) return s;
+    if ((s = corrector_impl(m, CorrectorRequest::all(true)))) return s;
     if ((s = update_state_impl(m))) return s;
     return atmosphere_ocean_fluxes_impl(m);
   }
@@ -2278,12 +2215,11 @@ gb25_status time_step_impl(gb25_model* m, int euler, bool more = false) {
   // corrector reads and writes its own columns only, and the fill after it rewrites exactly the same halo cells from
   // the corrected interior, so the first fill has no effect on any later value: it is left out (3 launches).
   const Grid& g = m->g;
-  const dim3 b(64, 4);
-  const Cols own{0, g.Nx, INT_MAX, 0}, wide{-2, g.Nx + 4, INT_MAX, 0};
+  const LaunchFacts facts = launch_facts(m);
   switch (corrector) {
     case Corrector::InConsumers: {
       Timed t(m, GB25_K_CORRECTOR);
-      if ((s = unswept_head(m, b, own, 0, g.Ny + 1, m->route.kernels_carry_w() ? wide : NO_COLS, true))) return s;
+      if ((s = unswept_head(m, HeadRequest::in_consumers(facts, m->route.kernels_carry_w())))) return s;
       break;
     }
     case Corrector::ThroughTracers: {
@@ -2291,7 +2227,7 @@ gb25_status time_step_impl(gb25_model* m, int euler, bool more = false) {
       for (int q = 0; q < 2; q++)
         if (!m->uvc[q].d && (s = alloc_field(m, m->uvc[q], m->f[GB25_U + q].nx, m->f[GB25_U + q].ny, m->f[GB25_U + q].nz))) return s;
       // du, dv on the own faces (rows of y faces: [0, Ny) on a folded grid, [0, Ny] below a wall) ...
-      if ((s = unswept_head(m, b, own, 0, g.Ny + (g.cv.north_fold ? 0 : 1), NO_COLS, false))) return s;
+      if ((s = unswept_head(m, HeadRequest::through_tracers_faces(facts)))) return s;
       // ... and their halo cells as the fills derive them (the rows beyond a zipper fold: images with the sign of a vector component)
       if (g.cv.north_fold) {
         Halo2 hc{};
@@ -2300,7 +2236,7 @@ gb25_status time_step_impl(gb25_model* m, int euler, bool more = false) {
         hc.n = 2;
         if ((s = fill_halos_2d(m, hc))) return s;
       }
-      if ((s = unswept_head(m, b, NO_COLS, 0, 0, wide, false))) return s;
+      if ((s = unswept_head(m, HeadRequest::through_tracers_bases(facts)))) return s;
       // (the two strips of halo cells of the uncorrected u, v the tracer kernel reads: k_uncorrected_edges)
       hipLaunchKernelGGL(k_uncorrected_edges, dim3((std::max(g.Nx, g.Ny) + 255) / 256, g.Nz, g.cv.north_fold ? 3 : 2), dim3(256), 0, main, g,
                          m->f[GB25_U].d, m->f[GB25_V].d);
@@ -2310,10 +2246,10 @@ gb25_status time_step_impl(gb25_model* m, int euler, bool more = false) {
     }
     case Corrector::SweepWFly:   // (the sweep leaves du, dv of the own columns behind for k_w_bases)
     case Corrector::Sweep:
-      s = corrector_impl(m, true);
+      s = corrector_impl(m, CorrectorRequest::all(true));
       m->route.sweep_done();
       if (s) return s;
-      if (corrector == Corrector::SweepWFly && (s = w_bases_impl(m, b, wide.i0, wide.ni, wide.skip_from, wide.skip))) return s;
+      if (corrector == Corrector::SweepWFly && (s = w_bases_impl(m, dim3(64, 4), wide_bases(facts)))) return s;
       if (corrector == Corrector::SweepWFly) m->route.w_carried_in_kernels();
       break;
   }
@@ -3069,7 +3005,7 @@ gb25_status gb25_ab2_step(gb25_model* m, double dt, int euler) {
 }
 gb25_status gb25_correct_velocities_and_cache_previous_tendencies(gb25_model* m, double) {
   CHECK_MODEL(m);
-  return corrector_impl(m);
+  return corrector_impl(m, CorrectorRequest::all(false));   // (a caller of the single phases may have touched u, v: no column integrals)
 }
 gb25_status gb25_update_state(gb25_model* m) {
   CHECK_MODEL(m);
@@ -3117,8 +3053,8 @@ static gb25_status opt_chunk_levels(gb25_model* m, int32_t* v) {
   // default chunking by the same rule): the chosen one must stay within that reach too
   const TendencyReach r = tendency_reach_ok(m->layout, *v, (int)sizeof(real));
   if (!r.ok)
-    return fail(m, GB25_ERR_INVALID_ARGUMENT, "chunks of %d levels (+ 10 stencil planes of %.3g elements) exceed the 2 GB the tendency "
-                "kernels address from one base: choose fewer levels per chunk", r.klen, r.plane);
+    return fail(m, GB25_ERR_INVALID_ARGUMENT, "chunks of %d levels (+ %d stencil planes of %.3g elements) exceed the 2 GB the tendency "
+                "kernels address from one base: choose fewer levels per chunk", r.klen, r.planes - r.klen, r.plane);
   m->valid.void_colsums();
   return GB25_OK;
 }

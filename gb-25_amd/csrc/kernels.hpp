@@ -10,6 +10,7 @@
 #pragma once
 #include "device_common.hpp"
 #include "subcycle_plan.hpp"   // the tile constants of the sub-cycle kernels: BT_TX, BT_NT, BT_SMAX, BW_NT
+#include "tile_sizes.hpp"      // ... and of the direct-stencil kernels: TX, TY
 
 namespace gb25 {
 
@@ -19,8 +20,6 @@ __device__ __forceinline__ void store_x_images(const Grid& g, real* a, int o, re
   if (xw) a[o + g.Nx] = x;   // column i < H is the periodic image of column i + Nx (east halo)
   if (xe) a[o - g.Nx] = x;   // column i >= Nx - H of column i - Nx (west halo)
 }
-
-constexpr int TX = 64, TY = 4;
 
 struct TileIdx {
   int i, j, k;

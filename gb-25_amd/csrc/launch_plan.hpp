@@ -3,6 +3,7 @@
 // are the ONLY place any of this is decided; fill_halos_impl, compute_w_impl and compute_p_impl (gb25_api.hip) bind the model's arrays
 // to the plan and issue it.  Plain C++, no HIP, no gb25_model: a host compiler can include this file alone (tests/test_launch_plan.py).
 // The vocabulary, the table of forms and the quirks in prose: DESIGN.md, "The launches of a fill, of w and of the pressure".
+// (The tendency kernels, the corrector and the head of an unswept step: tendency_plan.hpp, on the same LaunchFacts, Cols and Pass.)
 #pragma once
 #include <climits>
 namespace {
@@ -18,6 +19,16 @@ struct LaunchFacts {
   bool ys_open, yn_open;   // a southern / northern neighbour rank exists
   bool fill_fused;     // option FILL_FUSED
   bool curvilinear;
+  // ... and what the plans of the tendency kernels and the corrector read besides (tendency_plan.hpp)
+  int pl_c, pl_v;      // elements of one plane of a cell-shaped and of a y-face array
+  long w_elems;        // elements of w, the tallest 3-D array
+  int real_bytes;      // sizeof(real)
+  int mom_chunk_levels, trc_chunk_levels;   // options MOMENTUM_ / TRACER_CHUNK_LEVELS
+  int v_rows;          // rows of y faces a launch covers
+  int Ry;              // ranks in y of the decomposition
+  bool immersed;
+  int tracer_order;         // 5 | 7
+  int tracer_rows_forced;   // 1, 2: GB25_TRACER_ROWS forced it; 0: the rule of plan_tracers
 };
 
 // columns i0 + [0, ni); from column skip_from on: + skip.  Two ranges in one launch: the first ends before skip_from, the second begins

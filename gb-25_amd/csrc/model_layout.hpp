@@ -5,6 +5,7 @@
 // this file alone (tests/test_model_layout.py).  The rules in prose: DESIGN.md, "The layout of a model".
 #pragma once
 #include "../../include/gb25.h"
+#include "tendency_plan.hpp"   // the reach of the tendency kernels
 
 #include <algorithm>
 #include <cmath>
@@ -126,7 +127,8 @@ inline size_t chunk_columns(const ModelLayout& L) { return (size_t)std::max(1, L
 inline size_t tall_buf_elems(const ModelLayout& L) { return (size_t)5 * (L.Wy + 1) * wide_dims(L, GB25_ETA).nx; }
 
 // The kernels address a parent array with 32-bit ELEMENT indices; the tendency kernels with 32-bit BYTE offsets from the
-// first plane their block touches (tendency_kernels.hpp): a chunk of levels plus its stencil planes must stay below 2 GB.
+// first plane their block touches (tendency_kernels.hpp): a chunk of levels plus its stencil planes must stay below 2 GB.  The planes
+// are counted by the rule the launches follow (tendency_plan.hpp, "the reach of the tendency kernels").
 struct TendencyReach {
   bool ok;
   int klen, planes;     // levels of the longest chunk; with its stencil planes
@@ -135,9 +137,9 @@ struct TendencyReach {
 inline TendencyReach tendency_reach_ok(const ModelLayout& L, int chunk_levels, int real_bytes) {
   const Dims v = parent_dims(L, GB25_V);
   const double plane = (double)v.nx * v.ny;
-  const int kchunks = std::max(1, L.Nz / chunk_levels), klen = (L.Nz + kchunks - 1) / kchunks;
-  const double bytes = plane * (klen + 10) * real_bytes;
-  return {bytes < 2147483648.0, klen, klen + 10, plane, bytes};
+  const LevelChunks c = level_chunks(L.Nz, L.H, chunk_levels, plane * real_bytes, true);
+  const int planes = chunk_planes_at_creation(c);
+  return {within_reach(c, planes), c.klen, planes, plane, planes * c.plane_bytes};
 }
 
 struct LayoutPlan {

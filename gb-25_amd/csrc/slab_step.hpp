@@ -416,15 +416,8 @@ gb25_status stage_own_columns(gb25_model* m, bool head_only) {
     if (head_only) m->route.head_done();
     if (!m->valid.colsum_valid) return fail(m, GB25_ERR_STATE, "internal: a lazy step without the column integrals of u, v");
     Timed t(m, GB25_K_CORRECTOR);
-    // (a rank of a 2-D decomposition has no interior pass: du, dv and the chunk bases of w over its whole extended range at
-    // once, in HaloColumns, when every halo is in)
-    // chunk bases of w on the columns [0, Nx - 2] (their u faces are own columns), before the interior momentum pass
-    // overwrites the chunk sums they are made from
-    const bool own = m->Ry == 1;
-    if ((s = unswept_head(m, dim3(64, 4), own ? Cols{0, g.Nx, INT_MAX, 0} : NO_COLS, 0, g.Ny + 1,
-                          own && wfly ? Cols{0, g.Nx - 1, INT_MAX, 0} : NO_COLS, true)))
-      return s;
-  } else if ((s = corrector_impl(m, true, 1))) {
+    if ((s = unswept_head(m, HeadRequest::slab_own_columns(launch_facts(m), wfly)))) return s;
+  } else if ((s = corrector_impl(m, CorrectorRequest::own_columns()))) {
     return s;
   }
   if (head_only || !tendencies_split(m)) return GB25_OK;
@@ -449,7 +442,7 @@ gb25_status stage_strips(gb25_model* m) {
 // rows that leave for the southern / northern neighbour next (BundleRows) are corrected over their whole width
 // (a lazy step: the rows leave uncorrected, like the columns; the receiver makes du, dv of its halo rows itself)
 gb25_status stage_halo_rows_corrector(gb25_model* m) {
-  return m->route.corrector_in_consumers() ? GB25_OK : corrector_impl(m, true, 2);
+  return m->route.corrector_in_consumers() ? GB25_OK : corrector_impl(m, CorrectorRequest::halo_columns());
 }
 
 // HaloColumns: Bundle has been unpacked: corrector on the x-halo columns, then update_state without any further exchange (y/z
@@ -475,21 +468,11 @@ gb25_status stage_halo_columns(gb25_model* m, bool first_part, bool second_part)
       // du, dv of the x halo columns: the neighbours' column integrals came with the bundle, the new U, V of those columns
       // from the widened sub-cycle; their y/z layers of u, v arrived filled -- nothing else to do
       if (!m->valid.halo_colsum_valid) return fail(m, GB25_ERR_STATE, "internal: a lazy step without the neighbours' column integrals");
-      if (m->Ry > 1) {
-        // 2-D decomposition: everything at once -- own cells, halo columns, halo rows of the open sides (corners included)
-        // rows: from the southern halo rows (or row 0) to the last northern halo row of the cell-shaped arrays (or the wall face)
-        const int hs = m->ys_open ? g.H : 0, nj = hs + g.Ny + (m->yn_open ? g.H : 1);
-        if ((s = unswept_head(m, dim3(64, 4), Cols{-g.H, g.Nx + 2 * g.H, INT_MAX, 0}, -hs, nj,
-                              wfly ? Cols{-2, g.Nx + 4, INT_MAX, 0} : NO_COLS, false)))
-          return s;
-        // (the bottom / top layers of the halo rows, which arrived with their interior levels: the fill below)
-      } else {
-        // ... in blocks of 16 x 16, and the chunk bases of w on the columns -2, -1 and Nx - 1, Nx, Nx + 1 (the w tiles reach two columns out)
-        if ((s = unswept_head(m, dim3(16, 16), Cols{-g.H, 2 * g.H, 0, g.Nx}, 0, g.Ny + 1,
-                              wfly ? Cols{-2, 5, 0, g.Nx - 1} : NO_COLS, false)))
-          return s;
-      }
-    } else if (m->Ry == 1 && (s = corrector_impl(m, true, 2))) {   // (2-D decomposition: done in HaloRowsCorrector)
+      // 2-D decomposition: everything at once (the bottom / top layers of the halo rows, which arrived with their interior levels: the
+      // fill below); a slab: the two halo strips
+      const LaunchFacts f = launch_facts(m);
+      if ((s = unswept_head(m, m->Ry > 1 ? HeadRequest::mesh_rank(f, wfly) : HeadRequest::slab_halo_strips(f, wfly)))) return s;
+    } else if (m->Ry == 1 && (s = corrector_impl(m, CorrectorRequest::halo_columns()))) {   // (2-D decomposition: done in HaloRowsCorrector)
       return s;
     }
     // (with the early strips T and S are left alone here: their layers are in place, own columns since Update)

@@ -11,10 +11,9 @@
 #include <type_traits>
 
 #include "device_common.hpp"
+#include "tile_sizes.hpp"   // V2_TX, V3_OUT, V3_PAIR: shared with the plans of the launches (tendency_plan.hpp)
 
 namespace gb25 {
-
-constexpr int V2_TX = 64;   // tile width = one wavefront; tile height TY (rows = waves per block) is a template parameter
 
 // =============================================================================================
 // Momentum tendencies G_u and G_v fused: block = (64 x 8) columns marching in k.  Per level the block stages
@@ -671,8 +670,6 @@ __global__ __launch_bounds__(V2_TX* V2_TY, MINW) void k_momentum_tendencies_v5(
   }
 }
 
-constexpr int V3_OUT = 63;   // outputs per wavefront
-
 // AHEAD: the kernel also writes the tracers of the next time level, Tn = T + dt (C1 G^n - C2 G^-), into a second
 // pair of arrays: at this point T and the fresh G^n are in registers, so the next step's ab2_step_field! for T and S
 // costs one read (G^-) and one write per tracer here instead of a separate 3R + 1W sweep.  The host adopts Tn/Sn
@@ -1157,7 +1154,6 @@ __global__ __launch_bounds__(256, MINW) void k_tracer_tendencies_v5(Grid g, cons
 // =============================================================================================
 // WFLY: w is not read (the field is stale in a step that carries w inside its tendency kernels): Az w of both columns from the
 // divergence of their transports, the east faces' from the next lane, starting from lz.wbase -- as tracer_tile does.
-constexpr int V3_PAIR = 2 * V3_OUT;   // outputs per wavefront
 // The variants that exist: tracer_tile_single's static_assert and the host's choice of instance (catke_tendency_impl) both use this rule.
 constexpr bool single_variant(bool IMM, bool CURV, int ORD, bool WFLY) { return (!CURV || IMM) && (ORD == 5 || ORD == 7); }
 template <bool IMM, bool CURV, int ORD, bool WFLY = false>

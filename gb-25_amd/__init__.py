@@ -47,6 +47,7 @@ from .sharding import factors
 from .arg_parsing import (float_type_from_args, float_type_from_string, interior_size, multifloat_from_args,
                           parse_baroclinic_instability_args)
 from .sharded_io import load_all_fields, load_global_field, save_model_state
+from .restart import checkpoint, read_checkpoint, restore, run_checkpointed
 
 
 class GPU:

@@ -71,6 +71,8 @@ ABI_SYMBOLS = [
     "gb25_get_average", "gb25_average_device_ptr", "gb25_averages_end",
     "gb25_particles_info_bytes", "gb25_particles_begin", "gb25_particles_set", "gb25_particles_get", "gb25_particles_advance",
     "gb25_particles_sample", "gb25_particles_get_info", "gb25_particles_end",
+    "gb25_checkpoint_info_bytes", "gb25_restore_info_bytes", "gb25_checkpoint_snapshot", "gb25_checkpoint_write",
+    "gb25_checkpoint_get_info", "gb25_checkpoint_release", "gb25_restore", "gb25_set_clock",
 ]
 # gb25_derived (include/gb25.h)
 DERIVED_IDS = {"vorticity": 0, "kinetic_energy": 1, "density_anomaly": 2, "potential_density": 3, "mixed_layer_depth": 4}
@@ -284,6 +286,28 @@ class ParticlesInfo(_Record):
         return dict(zip(PARTICLE_COUNTERS, getattr(self, which)))
 
 
+class CheckpointInfo(_Record):
+    """gb25_checkpoint_info (include/gb25.h): whether a snapshot waits to be written and whether its drain has finished; members,
+    pieces and bytes of the restart set, the arena it passes through; whether averages or particles were open (they are not saved)."""
+    _fields_ = [("taken", C.c_int32), ("drained", C.c_int32), ("members", C.c_int32), ("pieces", C.c_int32),
+                ("bytes", C.c_int64), ("arena_bytes", C.c_int64),
+                ("averages_open_not_saved", C.c_int32), ("particles_open_not_saved", C.c_int32)]
+
+
+# the recorded result-changing options, in the order of the bits of gb25_restore_info.options_changed
+RESTORED_OPTIONS = ("kernels", "pressure_precision", "momentum_chunk_levels", "tracer_chunk_levels", "w_on_the_fly", "substep_order",
+                    "fold_pivot_slaved", "catke_stale_e_halos")
+
+
+class RestoreInfo(_Record):
+    """gb25_restore_info (include/gb25.h)."""
+    _fields_ = [("members", C.c_int32), ("pieces", C.c_int32), ("bytes", C.c_int64), ("options_changed", C.c_uint32),
+                ("tracer_rows_differ", C.c_int32), ("phy_stale", C.c_int32), ("reserved", C.c_int32)]
+
+    def changed_options(self):
+        return [n for q, n in enumerate(RESTORED_OPTIONS) if self.options_changed >> q & 1]
+
+
 def average_group_of(name):
     """"means" | "squares" | "fluxes": the group a quantity of AVERAGE_IDS belongs to."""
     q = AVERAGE_IDS[name]
@@ -457,6 +481,12 @@ def load_library(float_type="Float32"):
     lib.gb25_get_average.argtypes = [P, C.c_int, C.c_int32, P, C.c_int64]
     lib.gb25_average_device_ptr.argtypes = [P, C.c_int, C.POINTER(P), C.POINTER(C.c_int32)]
     lib.gb25_averages_end.argtypes = [P]
+    lib.gb25_checkpoint_snapshot.argtypes = [P, C.c_int64]
+    lib.gb25_checkpoint_write.argtypes = [P, C.c_char_p, C.c_char_p]
+    lib.gb25_checkpoint_get_info.argtypes = [P, C.POINTER(CheckpointInfo)]
+    lib.gb25_checkpoint_release.argtypes = [P]
+    lib.gb25_restore.argtypes = [P, C.c_char_p, C.c_char_p, C.POINTER(RestoreInfo)]
+    lib.gb25_set_clock.argtypes = [P, C.c_double, C.c_int64, C.c_double]
     lib.gb25_particles_begin.argtypes = [P, C.c_int64]
     lib.gb25_particles_set.argtypes = [P, C.c_int64, C.c_int64, P, P, P, P, P, P]
     lib.gb25_particles_get.argtypes = [P, C.c_int64, C.c_int64, P, P, P, P, P, P, P]
@@ -486,7 +516,8 @@ def load_library(float_type="Float32"):
                        ("gb25_budget_bytes", Budget), ("gb25_transport_bytes", Transport),
                        ("gb25_class_sum_bytes", ClassSum), ("gb25_spectral_coefficient_bytes", SpectralCoefficient),
                        ("gb25_averages_info_bytes", AveragesInfo), ("gb25_particles_info_bytes", ParticlesInfo),
-                       ("gb25_block_info_bytes", BlockInfo), ("gb25_filter_info_bytes", FilterInfo)):
+                       ("gb25_block_info_bytes", BlockInfo), ("gb25_filter_info_bytes", FilterInfo),
+                       ("gb25_checkpoint_info_bytes", CheckpointInfo), ("gb25_restore_info_bytes", RestoreInfo)):
         getattr(lib, fn).restype = C.c_int32
         if getattr(lib, fn)() != C.sizeof(struct):
             raise GB25Error(f"{path}: {fn}() = {getattr(lib, fn)()} there, {C.sizeof(struct)} bytes in this binding: "
@@ -1137,6 +1168,37 @@ class HipBackend:
         """save_model_state: this rank's slab -> <directory>/<label>/fields_rank<R>.npz; returns the path."""
         self._call("gb25_save_state", str(directory).encode(), str(label).encode())
         return os.path.join(str(directory), label, f"fields_rank{self.cfg.rank}.npz")
+
+    # ---- checkpoint and restart (include/gb25.h: "checkpoint and bit-for-bit restart")
+    def checkpoint_path(self, directory, label="checkpoint"):
+        return os.path.join(str(directory), label, f"restart_rank{self.cfg.rank}.gb25")
+
+    def checkpoint_snapshot(self, max_arena_bytes=0):
+        """gb25_checkpoint_snapshot: the restart set into the device arena in one launch; the drain to the host runs beside whatever
+        the model does next."""
+        self._call("gb25_checkpoint_snapshot", int(max_arena_bytes))
+
+    def checkpoint_write(self, directory, label="checkpoint"):
+        """gb25_checkpoint_write: waits for the drain, writes the file; returns its path."""
+        self._call("gb25_checkpoint_write", str(directory).encode(), str(label).encode())
+        return self.checkpoint_path(directory, label)
+
+    def checkpoint_info(self):
+        out = CheckpointInfo()
+        self._call("gb25_checkpoint_get_info", C.byref(out))
+        return out
+
+    def checkpoint_release(self): self._call("gb25_checkpoint_release")
+
+    def restore(self, directory, label="checkpoint"):
+        """gb25_restore: fields, clock, scalar state and recorded options of <directory>/<label>/restart_rank<R>.gb25; a refusal
+        (GB25Error naming what differs) leaves the model untouched."""
+        out = RestoreInfo()
+        self._call("gb25_restore", str(directory).encode(), str(label).encode(), C.byref(out))
+        return out
+
+    def set_clock(self, time, iteration, last_dt):
+        self._call("gb25_set_clock", float(time), int(iteration), float(last_dt))
 
     def set_top_flux(self, name, J):
         """FluxBoundaryCondition at the top of u | v | T | S: interior-shaped array (None: back to no-flux)."""

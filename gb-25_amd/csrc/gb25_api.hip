@@ -17,6 +17,7 @@
 #include "stability_kernels.hpp"
 #include "block_kernels.hpp"
 #include "filter_kernels.hpp"
+#include "restart_kernels.hpp"
 #include "diagnostics_state.hpp"
 #include "validity.hpp"
 #include "step_route.hpp"
@@ -273,6 +274,12 @@ struct gb25_model {
   // a stale pHY' is a diagnostic)
   DiagState diag;
   int prof_redirect = -1;
+  // checkpoint and restart: the arena, the pinned host buffer, the copy stream (restart_host.hpp; made by the first snapshot or
+  // restore, freed by gb25_checkpoint_release and gb25_destroy)
+  struct RestartState* restart = nullptr;
+  size_t top_flux_elems[4] = {0, 0, 0, 0};   // (what each d_top_flux was allocated with)
+  uint64_t grid_print[2] = {0, 0};           // the grid fingerprint of a checkpoint, made once per grid (restart_host.hpp)
+  bool grid_print_valid = false;
 };
 
 namespace {
@@ -2007,6 +2014,7 @@ gb25_status atmosphere_ocean_fluxes_impl(gb25_model* m) {
   for (int q = 0; q < 4; q++) {
     if (!m->d_top_flux[q]) {
       HIPCHK(m->mem.alloc(&m->d_top_flux[q], n2 * sizeof(real)));
+      m->top_flux_elems[q] = n2;
       HIPCHK(hipMemsetAsync(m->d_top_flux[q], 0, n2 * sizeof(real), m->stream));
     }
     m->g.top_flux[q] = m->d_top_flux[q];
@@ -2366,6 +2374,7 @@ gb25_status quiesce_for_grid_change(gb25_model* m) {
   HIPCHK(hipStreamSynchronize(m->side_stream));
   if (m->baro_stream) HIPCHK(hipStreamSynchronize(m->baro_stream));
   m->valid.grid_changes();
+  m->grid_print_valid = false;
   m->implicit_key[0][0] = m->implicit_key[1][0] = -1.0;   // (the elimination tables of a closure hold the old spacings)
   return GB25_OK;
 }
@@ -2383,6 +2392,8 @@ static gb25_status wait_for_model(gb25_model* m) {
   if (m->group) HIPCHK(m->group->sync_side());
   return GB25_OK;
 }
+
+namespace { void restart_release(gb25_model* m); }   // (restart_host.hpp)
 
 // =============================================================================================
 extern "C" {
@@ -2506,6 +2517,7 @@ gb25_status gb25_create(const gb25_config* cfg, gb25_model** out) {
 
 void gb25_destroy(gb25_model* m) {
   if (!m) return;
+  restart_release(m);
   if (m->group) group_destroy(m->group);   // (the exchange context of every slab it holds)
   if (m->own_stream) hipStreamSynchronize(m->own_stream);
   m->diag.release();
@@ -2907,7 +2919,10 @@ gb25_status gb25_set_top_flux(gb25_model* m, gb25_field f, const void* host) {
     m->g.top_flux[q] = nullptr;   // (the array stays allocated for the next use)
     return GB25_OK;
   }
-  if (!m->d_top_flux[q]) HIPCHK(m->mem.alloc(&m->d_top_flux[q], n2 * sizeof(real), true));
+  if (!m->d_top_flux[q]) {
+    HIPCHK(m->mem.alloc(&m->d_top_flux[q], n2 * sizeof(real), true));
+    m->top_flux_elems[q] = n2;
+  }
   int32_t di[3];
   gb25_field_dims(m, f, 0, di);   // (the interior of the field's horizontal location: Ny rows of y faces on a folded grid)
   const int H = m->cfg.halo, nxi = di[0], nyi = di[1];
@@ -3445,6 +3460,7 @@ gb25_status gb25_profile_get(gb25_model* m, gb25_kernel k, int64_t* launches, do
 
 }  // extern "C"
 
+#include "restart_host.hpp"
 #include "diagnostics_host.hpp"
 #include "averages_host.hpp"
 #include "classes_host.hpp"

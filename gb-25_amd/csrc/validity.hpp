@@ -24,6 +24,19 @@ template <class Real> struct Validity {
   void option_changes() { void_lookaheads(); tend_forkable = false; }
   void pointer_handed_out() { ptr_exposed = true; void_lookaheads(); }
   void grid_changes() { option_changes(); colsum_valid = halo_colsum_valid = false; complete_fills_owed(); }
+  // gb25_restore wrote every array of the restart set behind every cache: nothing made ahead of time or summed earlier belongs to this state
+  // -- except what the snapshot held as members and recorded as valid (`made`), which is this state's own; a model whose pointers
+  // are out keeps no look-ahead, and the early fork of the tracer branch rests on an event of the old run (tend_forkable stays false)
+  void state_restored(const Validity& made) {
+    grid_changes();   // (everything void, complete fills owed) -- then, by name, what the snapshot recorded
+    if (ptr_exposed) return;
+    ahead_valid = made.ahead_valid; ahead_dt = made.ahead_dt; ahead_chi = made.ahead_chi;
+    ahead_uv_valid = made.ahead_uv_valid; ahead_uv_dt = made.ahead_uv_dt; ahead_uv_chi = made.ahead_uv_chi;
+    ahead_baro_valid = made.ahead_baro_valid;
+    colsum_valid = made.colsum_valid;
+    halo_colsum_valid = made.halo_colsum_valid;
+    complete_fills_needed = made.complete_fills_needed;
+  }
   // a tendency kernel is about to run; from_new_state: the momentum kernel STARTS an evaluation (the edge pass of a split one does not)
   void tendency_kernel_runs(bool from_new_state) { tend_forkable = false; if (from_new_state) void_velocity_lookaheads(); }
   // ---- causes that validate; what a step consumes; predicates

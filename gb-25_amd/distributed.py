@@ -383,6 +383,21 @@ class LocalSlabEnsemble:
             b.synchronize()
 
     # the composites of any member step every slab of the exchange context
+    # checkpoint and restart: one file per rank, restart_rank<R>.gb25; a restore needs the same decomposition
+    def checkpoint(self, directory, label="checkpoint", wait=True, max_arena_bytes=0):
+        """Snapshot every rank (one launch each), then write the files -- or, with wait=False, return the handles whose write()
+        does, while the ensemble steps on.  Returns the paths / the handles in rank order."""
+        from .restart import Snapshot
+        for b in self.backends:
+            b.checkpoint_snapshot(max_arena_bytes)
+        handles = [Snapshot(b, directory, label) for b in self.backends]
+        return [h.write() for h in handles] if wait else handles
+
+    def restore(self, directory, label="checkpoint"):
+        """Every rank reads its own file (the exchange context exists from the ensemble's construction on); a refusal of one
+        rank raises before the ranks behind it are touched.  Returns the RestoreInfo of every rank."""
+        return [b.restore(directory, label) for b in self.backends]
+
     def first_time_step(self):
         self.backends[0].first_time_step()
 

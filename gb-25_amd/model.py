@@ -219,6 +219,12 @@ class HydrostaticFreeSurfaceModel:
     def synchronize(self):
         self.backend.synchronize()
 
+    def checkpoint(self, directory, label="checkpoint", wait=True):
+        """Snapshot the restart set on the device and (wait=True) write <directory>/<label>/restart_rank<R>.gb25; wait=False
+        returns a handle whose .write() finishes the checkpoint while the model steps on (gb25_amd/restart.py)."""
+        from .restart import checkpoint
+        return checkpoint(self, directory, label, wait)
+
     def __repr__(self):
         Nx, Ny, Nz = self.grid.size
         return (f"HydrostaticFreeSurfaceModel({Nx}x{Ny}x{Nz} LatitudeLongitudeGrid, halo {self.grid.halo}, "

@@ -1153,6 +1153,50 @@ gb25_status gb25_particles_sample(gb25_model *m, gb25_field f, double *out, int6
 gb25_status gb25_particles_get_info(const gb25_model *m, gb25_particles_info *info);
 gb25_status gb25_particles_end(gb25_model *m);
 
+/* ---- checkpoint and bit-for-bit restart ("Checkpoint and restart").  Single domains and ranks of a decomposition: each
+ *      rank writes and reads its own file, the exchange context exists before the restore, another decomposition is refused.
+ *      gb25_checkpoint_snapshot copies the restart set -- every parent array a step reads and a step wrote, halos included, bits as
+ *      they are in memory (gb-25_amd/csrc/restart_plan.hpp) -- into a device arena in ONE launch on the model's stream (filed under
+ *      GB25_K_DIAGNOSTICS), forming two integer checksums per member (s1 = sum x_n, s2 = sum (n + 1) x_n mod 2^64 over the bit
+ *      patterns) in the same pass; a copy stream then drains the arena into pinned host memory behind an event, and the model's
+ *      stream does not wait: gb25_loop may be called at once.  It voids no look-ahead and moves no buffer.  max_arena_bytes > 0
+ *      bounds the arena: the set then passes through it in pieces, synchronously, and the file is the same byte for byte.
+ *      gb25_checkpoint_write waits for the drain only and writes <directory>/<label>/restart_rank<R>.gb25 (to *.tmp, renamed when
+ *      complete; label NULL or "": "checkpoint").  Without a snapshot it is GB25_ERR_STATE; so is a second snapshot before the
+ *      first was written or released.  gb25_checkpoint_release frees the arena and the pinned buffers (gb25_destroy does too).
+ *      Open averages and particle sessions are NOT saved: gb25_checkpoint_get_info says whether one was open.
+ *      gb25_restore synchronises the model, and refuses with GB25_ERR_STATE and a message that names what differs: another float
+ *      type, another configuration (shape, halo, rank / nranks / ranks_y, grid type, substeps, constants), a closure or the coupling
+ *      on in one and off in the other, another grid (fingerprint of z faces, bottom and metrics: the host sets grid, bottom and
+ *      atmosphere again BEFORE the restore), a checksum mismatch (naming the member).  A refused model is untouched.  Otherwise the
+ *      fields, the clock and the scalar state are those of the snapshot, the recorded result-changing options are applied
+ *      (options_changed: bit q = entry q of KERNELS, PRESSURE_PRECISION, MOMENTUM_CHUNK_LEVELS, TRACER_CHUNK_LEVELS, W_ON_THE_FLY,
+ *      SUBSTEP_ORDER, FOLD_PIVOT_SLAVED, CATKE_STALE_E_HALOS), the look-aheads and column sums that were valid at the snapshot are
+ *      members and valid again (everything else made ahead of time is void), and the steps that follow give the bits of the run
+ *      that went on. */
+typedef struct {
+  int32_t taken, drained;       /* a snapshot waits to be written; its drain to the host has finished */
+  int32_t members, pieces;      /* of the last snapshot (or restore) */
+  int64_t bytes, arena_bytes;   /* the restart set; the device arena it passes through */
+  int32_t averages_open_not_saved, particles_open_not_saved;
+} gb25_checkpoint_info;
+typedef struct {
+  int32_t members, pieces;
+  int64_t bytes;
+  uint32_t options_changed;     /* which recorded options differed from the model's and were applied */
+  int32_t tracer_rows_differ;   /* GB25_TRACER_ROWS was forced otherwise in the run that wrote the file (same bits either way) */
+  int32_t phy_stale;            /* pHY' was not a member: it is recomputed from T, S when asked for */
+  int32_t reserved;
+} gb25_restore_info;
+int32_t     gb25_checkpoint_info_bytes(void);   /* sizeof the structs as THIS library was built */
+int32_t     gb25_restore_info_bytes(void);
+gb25_status gb25_checkpoint_snapshot(gb25_model *m, int64_t max_arena_bytes /* 0: no cap */);
+gb25_status gb25_checkpoint_write(gb25_model *m, const char *directory, const char *label);
+gb25_status gb25_checkpoint_get_info(const gb25_model *m, gb25_checkpoint_info *info);
+gb25_status gb25_checkpoint_release(gb25_model *m);
+gb25_status gb25_restore(gb25_model *m, const char *directory, const char *label, gb25_restore_info *info);
+gb25_status gb25_set_clock(gb25_model *m, double time, int64_t iteration, double last_dt);
+
 /* ---- built-in per-kernel HIP-event timing (bench.py's roofline numbers) */
 gb25_status gb25_profile_enable(gb25_model *m, int on); /* 0: off, 1: every kernel, 2 + k: kernel k alone */
 gb25_status gb25_profile_reset(gb25_model *m);

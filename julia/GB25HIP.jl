@@ -618,4 +618,37 @@ function get_average(m::Model, a::Integer; normalized::Bool = true)
 end
 averages_end(m::Model) = check(m, ccall((:gb25_averages_end, m.lib), Cint, (Ptr{Cvoid},), m.ptr), "gb25_averages_end")
 
+# ---- checkpoint and bit-for-bit restart (include/gb25.h)
+checkpoint_snapshot(m::Model; max_arena_bytes::Integer = 0) =
+    check(m, ccall((:gb25_checkpoint_snapshot, m.lib), Cint, (Ptr{Cvoid}, Int64), m.ptr, max_arena_bytes), "gb25_checkpoint_snapshot")
+checkpoint_write(m::Model, directory::AbstractString, label::AbstractString = "checkpoint") =
+    check(m, ccall((:gb25_checkpoint_write, m.lib), Cint, (Ptr{Cvoid}, Cstring, Cstring), m.ptr, directory, label), "gb25_checkpoint_write")
+checkpoint_release(m::Model) = check(m, ccall((:gb25_checkpoint_release, m.lib), Cint, (Ptr{Cvoid},), m.ptr), "gb25_checkpoint_release")
+function checkpoint(m::Model, directory::AbstractString, label::AbstractString = "checkpoint")
+    checkpoint_snapshot(m)
+    checkpoint_write(m, directory, label)
+end
+# gb25_checkpoint_info / gb25_restore_info (include/gb25.h), field for field
+struct CheckpointInfo
+    taken::Int32; drained::Int32; members::Int32; pieces::Int32
+    bytes::Int64; arena_bytes::Int64
+    averages_open_not_saved::Int32; particles_open_not_saved::Int32
+end
+struct RestoreInfo
+    members::Int32; pieces::Int32; bytes::Int64; options_changed::UInt32
+    tracer_rows_differ::Int32; phy_stale::Int32; reserved::Int32
+end
+function checkpoint_info(m::Model)
+    info = Ref(CheckpointInfo(0, 0, 0, 0, 0, 0, 0, 0))
+    check(m, ccall((:gb25_checkpoint_get_info, m.lib), Cint, (Ptr{Cvoid}, Ref{CheckpointInfo}), m.ptr, info), "gb25_checkpoint_get_info")
+    info[]
+end
+function restore!(m::Model, directory::AbstractString, label::AbstractString = "checkpoint")
+    info = Ref(RestoreInfo(0, 0, 0, 0, 0, 0, 0))
+    check(m, ccall((:gb25_restore, m.lib), Cint, (Ptr{Cvoid}, Cstring, Cstring, Ref{RestoreInfo}), m.ptr, directory, label, info), "gb25_restore")
+    info[]
+end
+set_clock!(m::Model, time::Real, iteration::Integer, last_Δt::Real) =
+    check(m, ccall((:gb25_set_clock, m.lib), Cint, (Ptr{Cvoid}, Float64, Int64, Float64), m.ptr, time, iteration, last_Δt), "gb25_set_clock")
+
 end # module

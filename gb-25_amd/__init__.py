@@ -41,6 +41,7 @@ from .filters import FilterSums, filter_of_planes, filter_sums_host, kernel_weig
 # (the submodule first, as for the averages: the name `particles` of the package is the function)
 from .particles import (Particles, ParticlesHost, advance_host, exchange_particles, particle_rates, particles, run_with_particles,
                         sample_host, seed_particles, seed_positions)
+from .passive import PassiveTracers, passive_tracers, passive_update_host, run_with_tracers
 from .data_free import (PrescribedAtmosphere, analytic_atmosphere, data_free_ocean_climate_model_init,
                         set_prescribed_atmosphere, set_data_free_state, zonal_wind, sunlight, Tatm)
 from .sharding import factors

@@ -71,6 +71,8 @@ ABI_SYMBOLS = [
     "gb25_get_average", "gb25_average_device_ptr", "gb25_averages_end",
     "gb25_particles_info_bytes", "gb25_particles_begin", "gb25_particles_set", "gb25_particles_get", "gb25_particles_advance",
     "gb25_particles_sample", "gb25_particles_get_info", "gb25_particles_end",
+    "gb25_tracer_spec_bytes", "gb25_tracers_begin", "gb25_tracers_set", "gb25_tracers_get", "gb25_tracers_advance", "gb25_tracers_stats",
+    "gb25_tracers_clock", "gb25_tracers_end",
     "gb25_checkpoint_info_bytes", "gb25_restore_info_bytes", "gb25_checkpoint_snapshot", "gb25_checkpoint_write",
     "gb25_checkpoint_get_info", "gb25_checkpoint_release", "gb25_restore", "gb25_set_clock",
 ]
@@ -104,6 +106,8 @@ OPTION_IDS = {"kernels": 0, "ab2_lookahead": 1, "subcycle_lookahead": 2, "subcyc
               "lazy_corrector": 11, "momentum_chunk_levels": 12, "tracer_chunk_levels": 13, "tracers_first": 14, "w_on_the_fly": 15, "sub_stream_priority": 16, "subcycle_whole": 17, "early_strips": 18,
               "catke_stale_e_halos": 19, "comm_timeout_seconds": 20, "roctx_ranges": 21, "substep_order": 22, "fold_pivot_slaved": 23, "pressure_form": 24,
               "spectrum_table": 25}
+TRACERS_MAX = 8                                                           # GB25_TRACERS_MAX
+TRACER_ARRAYS = {"c": 0, "Gn": 1, "Gm": 2}                                # `which` of gb25_tracers_get
 UNIQUE_ID_BYTES = 128
 # int32 fn(void *user, int32 buffer_set, const void *send_w, const void *send_e, void *recv_w, void *recv_e, int64 nbytes)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
@@ -165,6 +169,12 @@ class FieldStats(_Record):
                 ("count", C.c_int64), ("nonfinite", C.c_int64),
                 ("at_max_abs", C.c_int32 * 3), ("first_nonfinite", C.c_int32 * 3), ("global_offset", C.c_int32 * 3),
                 ("reserved", C.c_int32)]
+
+
+class TracerSpec(_Record):
+    """gb25_tracer_spec (include/gb25.h): the constant source per second, the value the top level is reset to (when surface_reset
+    is not 0), and whether negative values are clipped after every update (such a tracer is not conserved)."""
+    _fields_ = [("source", C.c_double), ("surface_value", C.c_double), ("surface_reset", C.c_int32), ("clip_negative", C.c_int32)]
 
 
 class FieldDiff(_Record):
@@ -494,6 +504,13 @@ def load_library(float_type="Float32"):
     lib.gb25_particles_sample.argtypes = [P, C.c_int, P, C.c_int64]
     lib.gb25_particles_get_info.argtypes = [P, C.POINTER(ParticlesInfo)]
     lib.gb25_particles_end.argtypes = [P]
+    lib.gb25_tracers_begin.argtypes = [P, C.c_int32, C.POINTER(TracerSpec), C.POINTER(P)]
+    lib.gb25_tracers_set.argtypes = [P, P, C.c_int32, P, C.c_int]
+    lib.gb25_tracers_get.argtypes = [P, P, C.c_int32, C.c_int32, P, C.c_int]
+    lib.gb25_tracers_advance.argtypes = [P, P]
+    lib.gb25_tracers_stats.argtypes = [P, P, C.c_int32, C.POINTER(FieldStats)]
+    lib.gb25_tracers_clock.argtypes = [P, P, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+    lib.gb25_tracers_end.argtypes = [P, P]
     lib.gb25_profile_enable.argtypes = [P, C.c_int]
     lib.gb25_profile_get.argtypes = [P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     for name in ["gb25_use_own_stream", "gb25_synchronize", "gb25_set_baroclinic_instability", "gb25_initialize",
@@ -516,6 +533,7 @@ def load_library(float_type="Float32"):
                        ("gb25_budget_bytes", Budget), ("gb25_transport_bytes", Transport),
                        ("gb25_class_sum_bytes", ClassSum), ("gb25_spectral_coefficient_bytes", SpectralCoefficient),
                        ("gb25_averages_info_bytes", AveragesInfo), ("gb25_particles_info_bytes", ParticlesInfo),
+                       ("gb25_tracer_spec_bytes", TracerSpec),
                        ("gb25_block_info_bytes", BlockInfo), ("gb25_filter_info_bytes", FilterInfo),
                        ("gb25_checkpoint_info_bytes", CheckpointInfo), ("gb25_restore_info_bytes", RestoreInfo)):
         getattr(lib, fn).restype = C.c_int32
@@ -1041,6 +1059,49 @@ class HipBackend:
 
     def particles_end(self):
         self._call("gb25_particles_end")
+
+    # ---- passive tracers carried beside the run (include/gb25.h: "passive tracers carried beside a run"; gb-25_amd/passive.py)
+    def tracers_begin(self, specs):
+        """gb25_tracers_begin: a set of len(specs) tracers (TracerSpec, or dicts of its fields); returns the set's handle."""
+        specs = [s if isinstance(s, TracerSpec) else TracerSpec(**s) for s in specs]
+        arr = (TracerSpec * max(len(specs), 1))(*specs)
+        out = C.c_void_p()
+        self._call("gb25_tracers_begin", len(specs), arr, C.byref(out))
+        return out
+
+    def tracers_set(self, handle, n, array, include_halos=False):
+        """gb25_tracers_set: tracer n from an array shaped like T's interior (or parent); the next advance is an Euler step."""
+        d = self.field_dims("T", include_halos)
+        a = np.asarray(array, dtype=self.dtype)
+        if a.shape != d:
+            raise ValueError(f"tracer {n}: expected shape {d}, got {a.shape}")
+        buf = np.ascontiguousarray(a.transpose(2, 1, 0))
+        self._call("gb25_tracers_set", handle, int(n), buf.ctypes.data_as(C.c_void_p), int(include_halos))
+
+    def tracers_get(self, handle, n, which="c", include_halos=False):
+        """gb25_tracers_get: "c", "Gn" (the tendency of the last advance) or "Gm" (the one before) of tracer n, index order [i, j, k]."""
+        d = self.field_dims("T", include_halos)
+        out = np.empty(d[::-1], dtype=self.dtype)
+        self._call("gb25_tracers_get", handle, int(n), TRACER_ARRAYS[which], out.ctypes.data_as(C.c_void_p), int(include_halos))
+        return out.transpose(2, 1, 0)
+
+    def tracers_advance(self, handle):
+        """gb25_tracers_advance: the set over one dt with u, v, w as they stand; before the model's step."""
+        self._call("gb25_tracers_advance", handle)
+
+    def tracers_stats(self, handle, n):
+        out = FieldStats()
+        self._call("gb25_tracers_stats", handle, int(n), C.byref(out))
+        return out
+
+    def tracers_clock(self, handle):
+        """(time, iteration) of the set."""
+        t, it = C.c_double(), C.c_int64()
+        self._call("gb25_tracers_clock", handle, C.byref(t), C.byref(it))
+        return t.value, it.value
+
+    def tracers_end(self, handle):
+        self._call("gb25_tracers_end", handle)
 
     def metric(self, name, index=1):
         v = C.c_double()

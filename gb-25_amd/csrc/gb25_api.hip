@@ -12,6 +12,7 @@
 #include "averages_kernels.hpp"
 #include "class_kernels.hpp"
 #include "particle_kernels.hpp"
+#include "passive_kernels.hpp"
 #include "spectrum_kernels.hpp"
 #include "surface_kernels.hpp"
 #include "stability_kernels.hpp"
@@ -280,6 +281,9 @@ struct gb25_model {
   size_t top_flux_elems[4] = {0, 0, 0, 0};   // (what each d_top_flux was allocated with)
   uint64_t grid_print[2] = {0, 0};           // the grid fingerprint of a checkpoint, made once per grid (restart_host.hpp)
   bool grid_print_valid = false;
+  // passive tracers carried beside the run (passive_host.hpp): the sets begun on this model and not ended yet.  Each set owns its
+  // memory; gb25_destroy frees the ones still here
+  std::vector<struct gb25_tracers*> tracer_sets;
 };
 
 namespace {
@@ -2394,6 +2398,7 @@ static gb25_status wait_for_model(gb25_model* m) {
 }
 
 namespace { void restart_release(gb25_model* m); }   // (restart_host.hpp)
+namespace { void passive_release_all(gb25_model* m); }   // (passive_host.hpp)
 
 // =============================================================================================
 extern "C" {
@@ -2518,6 +2523,7 @@ gb25_status gb25_create(const gb25_config* cfg, gb25_model** out) {
 void gb25_destroy(gb25_model* m) {
   if (!m) return;
   restart_release(m);
+  passive_release_all(m);
   if (m->group) group_destroy(m->group);   // (the exchange context of every slab it holds)
   if (m->own_stream) hipStreamSynchronize(m->own_stream);
   m->diag.release();
@@ -2735,6 +2741,9 @@ gb25_status gb25_set_dt(gb25_model* m, double dt) {
 gb25_status gb25_set_vertical_diffusivity(gb25_model* m, double nu, double kappa) {
   CHECK_MODEL(m);
   if (!(nu >= 0) || !(kappa >= 0)) return fail(m, GB25_ERR_INVALID_ARGUMENT, "viscosity and diffusivity must be >= 0");
+  if ((nu != 0 || kappa != 0) && !m->tracer_sets.empty())
+    return fail(m, GB25_ERR_STATE, "gb25_set_vertical_diffusivity: %zu set(s) of passive tracers are open, and they are built for closure = nothing "
+                "(gb25_tracers_end first)", m->tracer_sets.size());
   if (gb25_status s = collective_guard(m, 7, 0, nu)) return s;
   if (gb25_status s = collective_guard(m, 7, 1, kappa)) return s;
   m->nu = nu;
@@ -2747,6 +2756,9 @@ gb25_status gb25_set_closure_catke(gb25_model* m, int32_t on) {
   CHECK_MODEL(m);
   if (gb25_status s = collective_guard(m, 8, (unsigned)(on != 0), 0.0)) return s;
   if (on && (m->nu != 0 || m->kappa != 0)) return fail(m, GB25_ERR_STATE, "one closure at a time: the vertical diffusivity is set");
+  if (on && !m->tracer_sets.empty())
+    return fail(m, GB25_ERR_STATE, "gb25_set_closure_catke: %zu set(s) of passive tracers are open, and they are built for closure = nothing "
+                "(gb25_tracers_end first)", m->tracer_sets.size());
   if (on && m->cfg.Nz < 2) return fail(m, GB25_ERR_INVALID_ARGUMENT, "CATKE needs at least two levels (it lives on the faces between them)");
   if (gb25_status s = wait_for_model(m)) return s;
   if (on && !m->f[GB25_E].d) {
@@ -3465,6 +3477,7 @@ gb25_status gb25_profile_get(gb25_model* m, gb25_kernel k, int64_t* launches, do
 #include "averages_host.hpp"
 #include "classes_host.hpp"
 #include "particles_host.hpp"
+#include "passive_host.hpp"
 #include "spectrum_host.hpp"
 #include "surfaces_host.hpp"
 #include "stability_host.hpp"

@@ -1153,6 +1153,55 @@ gb25_status gb25_particles_sample(gb25_model *m, gb25_field f, double *out, int6
 gb25_status gb25_particles_get_info(const gb25_model *m, gb25_particles_info *info);
 gb25_status gb25_particles_end(gb25_model *m);
 
+/* ---- passive tracers carried beside a run (csrc/passive_host.hpp, csrc/passive_kernels.hpp: k_passive_update; gb-25_amd/passive.py
+ *      restates the update).  A SET of 1 .. GB25_TRACERS_MAX tracers at the cell centres, advected by the model's u, v, w with the
+ *      model's tracer advection scheme (WENO order 5 or 7), advanced by calls of its own BETWEEN the model's steps -- nothing inside
+ *      a model step changes, and a model stepped with sets beside it gives the bits of one stepped alone: the calls are READ-ONLY for
+ *      the schedule (nothing pinned, every look-ahead alive; the only memory written is the set's own allocation).  Single domains
+ *      with closure = nothing.
+ *      gb25_tracer_spec: `source` is added per second of model time (0: a dye; 1: an ideal age in seconds); with surface_reset != 0
+ *      the top level is set to surface_value after every update (the boundary condition of ideal age); with clip_negative != 0 the
+ *      update ends with c = max(c, 0) -- such a tracer is NO LONGER CONSERVED.
+ *      A set has a clock of its own, started from the model's by gb25_tracers_begin.  gb25_tracers_advance moves the set over ONE
+ *      step of the model's dt with u, v, w as they stand, and is valid only while the set's iteration equals the model's: call it
+ *      BEFORE the model step that leaves the same state (advance, gb25_time_step, advance, ...).  Anything else is GB25_ERR_STATE with
+ *      a message that names both iterations.  The first advance of a set, and the first after gb25_tracers_set, is an Euler step (as
+ *      gb25_first_time_step is for the model); later ones are quasi-AB2 with the model's chi.  Per tracer: G^n = -div(U c) by the
+ *      one-tracer tendency kernel of the model's grid; then ONE launch for the whole set,
+ *          c <- (c + dt ((1.5 + chi) G^n - (0.5 + chi) G^-)) + dt source          (in the library's float type, NO fused multiply-add)
+ *      then the surface reset, the clip, zero in immersed cells, and the halo cells the next tendency reads: the periodic x images,
+ *      one layer beyond the y walls and the bottom / top, and on a folded grid the rows beyond the zipper by the rule of a centre
+ *      field (cell (i, Ny-1+q) <- cell (Nx-1-i, Ny-1-q), no sign; GB25_OPT_FOLD_PIVOT_SLAVED is refused).  G^n and G^- then exchange
+ *      by pointer.  The call returns when the launches are complete.  At model iteration 0 the fields hold what the host has set: w and
+ *      the halo cells of u, v exist only once gb25_initialize and gb25_update_state have run (gb25_first_time_step runs them again, to
+ *      the same bits), so a set that is to take the model's first step too is advanced between gb25_update_state and
+ *      gb25_first_time_step (gb-25_amd/passive.py, run_with_tracers, does that).
+ *      gb25_tracers_set / _get move tracer n (0-based) like gb25_set_field / gb25_get_field of GB25_T (same shapes, include_halos
+ *      alike); set masks immersed cells, makes the halo cells above and makes the next advance an Euler step; get: which = 0: c,
+ *      1: G^n of the last advance, 2: G^- (the one before).  gb25_tracers_stats: gb25_get_field_stats of c (interior).
+ *      MEMORY: three parent arrays per tracer, one allocation per set, checked against the free device memory BEFORE it is made
+ *      (GB25_ERR_OUT_OF_MEMORY leaves nothing allocated); gb25_tracers_end frees it, gb25_destroy frees the sets still open.
+ *      Checkpoints do not contain tracer sets.
+ *      REFUSED by name, before anything is allocated (begin) or launched (advance): a rank of a decomposition; a vertical
+ *      diffusivity or CATKE (and gb25_set_vertical_diffusivity / gb25_set_closure_catke refuse to turn a closure on while a set is
+ *      open); count outside 1 .. GB25_TRACERS_MAX; a set of another model (GB25_ERR_INVALID_ARGUMENT). */
+#define GB25_TRACERS_MAX 8
+typedef struct gb25_tracers gb25_tracers;   /* opaque; owned by the model it was begun on */
+typedef struct {
+  double source;            /* added per second of model time */
+  double surface_value;     /* the value of the top level after every update ... */
+  int32_t surface_reset;    /* ... when this is not 0 */
+  int32_t clip_negative;    /* 0 | 1: c = max(c, 0) after every update (not conservative) */
+} gb25_tracer_spec;
+int32_t     gb25_tracer_spec_bytes(void);   /* sizeof the struct as THIS library was built */
+gb25_status gb25_tracers_begin(gb25_model *m, int32_t count, const gb25_tracer_spec *specs, gb25_tracers **out);
+gb25_status gb25_tracers_set(gb25_model *m, gb25_tracers *set, int32_t n, const void *host, int include_halos);
+gb25_status gb25_tracers_get(gb25_model *m, gb25_tracers *set, int32_t n, int32_t which, void *host, int include_halos);
+gb25_status gb25_tracers_advance(gb25_model *m, gb25_tracers *set);
+gb25_status gb25_tracers_stats(gb25_model *m, gb25_tracers *set, int32_t n, gb25_field_stats *out);
+gb25_status gb25_tracers_clock(gb25_model *m, gb25_tracers *set, double *time, int64_t *iteration);
+gb25_status gb25_tracers_end(gb25_model *m, gb25_tracers *set);
+
 /* ---- checkpoint and bit-for-bit restart ("Checkpoint and restart").  Single domains and ranks of a decomposition: each
  *      rank writes and reads its own file, the exchange context exists before the restore, another decomposition is refused.
  *      gb25_checkpoint_snapshot copies the restart set -- every parent array a step reads and a step wrote, halos included, bits as

@@ -24,7 +24,9 @@ export Config, Model, create, destroy!, first_time_step!, time_step!, loop!, ini
        STABILITY, stability_dims, compute_stability, get_stability, stability_stats,
        Blocks, BlockInfo, block_dims, block_sums, compute_block_sums, derived_block_sums,
        AVG_MEANS, AVG_SQUARES, AVG_FLUXES, AVERAGE, AveragesInfo, averages_begin, averages_accumulate, averages_info, average_dims,
-       get_average, averages_end
+       get_average, averages_end,
+       TracerSpec, TracerSet, tracers_begin, tracers_set!, tracers_get, tracers_advance!, tracers_stats, tracers_clock, tracers_end!,
+       run_with_tracers!
 
 # One library per Oceananigans float type (src/arg_parsing.jl:12-16): Float32 -> libgb25hip.so, Float64 ->
 # libgb25hip_f64.so; same symbols, gb25_real_bytes() tells them apart.
@@ -650,5 +652,64 @@ function restore!(m::Model, directory::AbstractString, label::AbstractString = "
 end
 set_clock!(m::Model, time::Real, iteration::Integer, last_Δt::Real) =
     check(m, ccall((:gb25_set_clock, m.lib), Cint, (Ptr{Cvoid}, Float64, Int64, Float64), m.ptr, time, iteration, last_Δt), "gb25_set_clock")
+
+# ---- passive tracers carried beside a run (include/gb25.h, "passive tracers carried beside a run"): dyes and ideal age, advanced by
+# calls of their own between the model's steps; single domains, closure = nothing
+struct TracerSpec      # gb25_tracer_spec, field for field
+    source::Float64; surface_value::Float64; surface_reset::Int32; clip_negative::Int32
+end
+dye(; clip_negative::Bool = false) = TracerSpec(0.0, 0.0, 0, clip_negative ? 1 : 0)
+ideal_age() = TracerSpec(1.0, 0.0, 1, 0)
+mutable struct TracerSet
+    ptr::Ptr{Cvoid}
+    count::Int
+end
+const FIELD_T_ID = 3    # GB25_T: a tracer has the shapes of T
+function tracers_begin(m::Model, specs::Vector{TracerSpec})
+    sizeof(TracerSpec) == ccall((:gb25_tracer_spec_bytes, m.lib), Int32, ()) || error("gb25_tracer_spec: different versions")
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    check(m, ccall((:gb25_tracers_begin, m.lib), Cint, (Ptr{Cvoid}, Int32, Ptr{TracerSpec}, Ptr{Ptr{Cvoid}}), m.ptr, length(specs), specs, out),
+          "gb25_tracers_begin")
+    return TracerSet(out[], length(specs))
+end
+"tracer n (0-based) from an array shaped like interior(T) (or parent(T)); the next advance is an Euler step"
+function tracers_set!(m::Model{FT}, s::TracerSet, n::Integer, a::AbstractArray; include_halos::Bool = false) where {FT}
+    b = Array{FT}(reshape(a, field_dims(m, FIELD_T_ID, include_halos)))
+    check(m, ccall((:gb25_tracers_set, m.lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Cint), m.ptr, s.ptr, n, b, include_halos),
+          "gb25_tracers_set")
+end
+"which = 0: c, 1: the tendency of the last advance, 2: the one before"
+function tracers_get(m::Model{FT}, s::TracerSet, n::Integer; which::Integer = 0, include_halos::Bool = false) where {FT}
+    a = Array{FT}(undef, field_dims(m, FIELD_T_ID, include_halos)...)
+    check(m, ccall((:gb25_tracers_get, m.lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}, Cint), m.ptr, s.ptr, n, which, a,
+                   include_halos), "gb25_tracers_get")
+    return a
+end
+tracers_advance!(m::Model, s::TracerSet) =
+    check(m, ccall((:gb25_tracers_advance, m.lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), m.ptr, s.ptr), "gb25_tracers_advance")
+function tracers_stats(m::Model, s::TracerSet, n::Integer)
+    out = Ref{FieldStats}()
+    check(m, ccall((:gb25_tracers_stats, m.lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ref{FieldStats}), m.ptr, s.ptr, n, out), "gb25_tracers_stats")
+    return out[]
+end
+function tracers_clock(m::Model, s::TracerSet)
+    t = Ref{Float64}(0); it = Ref{Int64}(0)
+    check(m, ccall((:gb25_tracers_clock, m.lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Int64}), m.ptr, s.ptr, t, it), "gb25_tracers_clock")
+    return (time = t[], iteration = it[])
+end
+function tracers_end!(m::Model, s::TracerSet)
+    check(m, ccall((:gb25_tracers_end, m.lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), m.ptr, s.ptr), "gb25_tracers_end")
+    s.ptr = C_NULL
+end
+"advance, then the model's step, `steps` times; at iteration 0 initialize! and update_state! first make w and the halos of u, v"
+function run_with_tracers!(m::Model, s::TracerSet, steps::Integer)
+    for _ in 1:steps
+        if clock(m).iteration == 0
+            initialize!(m); update_state!(m); tracers_advance!(m, s); first_time_step!(m)
+        else
+            tracers_advance!(m, s); time_step!(m)
+        end
+    end
+end
 
 end # module

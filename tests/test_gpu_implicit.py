@@ -12,9 +12,9 @@ each flat and immersed (the made bottom of tests/test_implicit_spec.py: a dry co
 columns at i = 0 and Nx-1 and on the wall rows; the built-in island grids; the folded grid).  (70, 13, Nz): one ragged 64-wide
 tile, odd Ny, every row next to a wall.
 
-Not covered: the e slice of MODE 1 (kappa_e, -dt L^e on the diagonal, src_e).  Its right-hand side e* is internal to
-compute_diffusivities! and L^e > 0 breaks the diagonal dominance the bound rests on: it stays covered by
-tests/test_gpu_catke.py only.
+Not covered here: the e slice of MODE 1 (kappa_e, -dt L^e on the diagonal, src_e).  tests/test_gpu_catke_spec.py judges it cell by
+cell (tests/test_catke_spec.py on the oracle): e* is rebuilt from the total tendency k_catke_tke_step leaves in G^-.e, and
+L^e <= 0 by construction keeps the system diagonally dominant.
 
 Also here: the cache key (dt, K) of the host's factor table; T and S through one elimination (S does not change by a bit when
 T's input does); and the column integrals the solve kernels rewrite for the corrector -- phase by phase (the corrected column

@@ -4,8 +4,8 @@ lists -- handed a mutated input, the same oracle output fails.
 
 The solve is driven alone (drive): u, v, T, S through set, noise in every halo cell of theirs, zero tendencies, with CATKE the
 diffusivity fields set with their halos (independent noise there, NOT the periodic image), then ab2_step(dt, euler) -- no
-update_state in between, so no closure overwrites the kappa the test set.  The e slice of the CATKE solve is not covered here
-(its right-hand side cannot be read from outside): tests/test_gpu_catke.py and tests/test_oracle_catke.py.
+update_state in between, so no closure overwrites the kappa the test set.  The e slice of the CATKE solve is not covered here:
+tests/test_catke_spec.py and tests/test_gpu_catke_spec.py judge it (its right-hand side is rebuilt from G^-.e).
 
 set_bottom_height on simple_lat_lon does switch both implementations to their immersed paths (the oracle's is_immersed; the
 library's immersed kernel instances follow the same flag), so the made bottom (made_levels) is an immersed case of its own

@@ -16,6 +16,7 @@ from .model import (CATKEVerticalDiffusivity, default_ocean_closure, Field, Hydr
                     at_depths, isosurface_depth, layer_thickness, on_isosurface,
                     baroclinic_wave_speed, buoyancy_frequency, deformation_radius, eady_growth_rate, eddy_resolution, ertel_pv,
                     richardson_number, shear_squared,
+                    divergence, frontogenesis, gradient_magnitude, normal_strain, okubo_weiss, rossby_number, shear_strain,
                     coarsen, column_integral, depth_mean, heat_content, subgrid_variance,
                     eddy_part, filtered, subfilter_variance,
                     heat_transport, meridional_transport, overturning, section_transport,
@@ -36,6 +37,7 @@ from .spectra import (combine_spectra, cospectrum, dominant_wavenumber, host_tab
                       zonal_coefficients)
 from .surfaces import gather_surfaces, on_surfaces_host, surfaces_of_profiles
 from .stability import gather_stability, stability_host, stability_of_columns
+from .kinematics import gather_kinematics, kinematics_host, kinematics_pieces
 from .blocks import BlockSums, block_sums_host, depth_weights, gather_blocks, sums_of_blocks
 from .filters import FilterSums, filter_of_planes, filter_sums_host, kernel_weights, rows_for_length
 # (the submodule first, as for the averages: the name `particles` of the package is the function)

@@ -63,6 +63,7 @@ ABI_SYMBOLS = [
     "gb25_spectral_coefficient_bytes", "gb25_get_spectrum_table", "gb25_get_zonal_spectrum", "gb25_get_derived_zonal_spectrum",
     "gb25_compute_on_surfaces", "gb25_get_on_surfaces",
     "gb25_stability_dims", "gb25_compute_stability", "gb25_get_stability", "gb25_get_stability_stats",
+    "gb25_kinematics_dims", "gb25_compute_kinematics", "gb25_get_kinematics", "gb25_get_kinematics_stats",
     "gb25_block_info_bytes", "gb25_block_dims", "gb25_derived_block_dims", "gb25_get_block_sums", "gb25_compute_block_sums",
     "gb25_get_derived_block_sums",
     "gb25_filter_info_bytes", "gb25_filter_dims", "gb25_derived_filter_dims", "gb25_get_filter_sums", "gb25_compute_filter_sums",
@@ -93,6 +94,10 @@ SURFACE_MAX_VALUES = 64
 # gb25_stability (include/gb25.h); the floor each takes as param when none is given (the Richardson number's 1e-12 s^-2 is a convention)
 STABILITY_IDS = {"n2": 0, "shear2": 1, "richardson": 2, "eady_rate": 3, "ertel_pv": 4, "wave_speed": 5}
 STABILITY_DEFAULT_PARAM = {"richardson": 1e-12}
+# gb25_kinematics (include/gb25.h); the tracer the gradient and the frontogenesis function take as param
+KINEMATICS_IDS = {"divergence": 0, "normal_strain": 1, "shear_strain": 2, "okubo_weiss": 3, "rossby_number": 4, "gradient": 5,
+                  "frontogenesis": 6}
+KINEMATICS_TRACERS = {"T": 0, "S": 1, "potential_density": 2}
 AVERAGE_GROUPS = {"means": 1, "squares": 2, "fluxes": 4}              # gb25_average_group
 # gb25_average: name -> id; the first six are the MEANS, the next five the SQUARES, the last six the FLUXES
 AVERAGE_IDS = {n: q for q, n in enumerate(["u", "v", "w", "T", "S", "eta", "uu", "vv", "TT", "SS", "etaeta",
@@ -474,6 +479,10 @@ def load_library(float_type="Float32"):
     lib.gb25_compute_stability.argtypes = [P, C.c_int, C.c_double, C.c_int32, C.c_int32, C.POINTER(P), C.POINTER(C.c_int32)]
     lib.gb25_get_stability.argtypes = [P, C.c_int, C.c_double, C.c_int32, C.c_int32, P]
     lib.gb25_get_stability_stats.argtypes = [P, C.c_int, C.c_double, C.POINTER(FieldStats)]
+    lib.gb25_kinematics_dims.argtypes = [P, C.c_int, C.POINTER(C.c_int32)]
+    lib.gb25_compute_kinematics.argtypes = [P, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.POINTER(P), C.POINTER(C.c_int32)]
+    lib.gb25_get_kinematics.argtypes = [P, C.c_int, C.c_int32, C.c_int32, C.c_int32, P]
+    lib.gb25_get_kinematics_stats.argtypes = [P, C.c_int, C.c_int32, C.POINTER(FieldStats)]
     lib.gb25_block_dims.argtypes = [P, C.c_int, C.POINTER(Blocks), C.POINTER(C.c_int32)]
     lib.gb25_derived_block_dims.argtypes = [P, C.c_int, C.POINTER(Blocks), C.POINTER(C.c_int32)]
     lib.gb25_get_block_sums.argtypes = [P, C.c_int, C.POINTER(Blocks), P, P, P, P, C.POINTER(BlockInfo)]
@@ -853,6 +862,47 @@ class HipBackend:
         out = FieldStats()
         q, param, _, _ = self._stability_args(kind, param, None)
         self._call("gb25_get_stability_stats", q, param, C.byref(out))
+        return out
+
+    # ---- flow kinematics on the device (include/gb25.h: "flow kinematics"; gb-25_amd/kinematics.py).  kind: "divergence",
+    #      "normal_strain", "okubo_weiss", "gradient", "frontogenesis" at (c,c,c), "shear_strain", "rossby_number" at (f,f,c) (or the
+    #      ids of the header); param: the tracer of the gradient and of the frontogenesis function -- "T", "S",
+    #      "potential_density" or 0 .. 2 --, None or 0 for the others; levels = (k_first, k_count), 0-based, k_count = -1 or
+    #      levels = None: all
+    def kinematics_dims(self, kind):
+        d = (C.c_int32 * 3)()
+        self._call("gb25_kinematics_dims", int(KINEMATICS_IDS.get(kind, kind)), d)
+        return tuple(d)
+
+    @staticmethod
+    def _kinematics_args(kind, param, levels):
+        k_first, k_count = (0, -1) if levels is None else levels
+        param = 0 if param is None else KINEMATICS_TRACERS.get(param, param)
+        return int(KINEMATICS_IDS.get(kind, kind)), int(param), int(k_first), int(k_count)
+
+    def compute_kinematics(self, kind, param=None, levels=None):
+        """(device pointer, dims) of the packed result, elements of this backend's dtype, i fastest; read-only, valid until
+        the next diagnostics call on this model."""
+        p, d = C.c_void_p(), (C.c_int32 * 3)()
+        self._call("gb25_compute_kinematics", *self._kinematics_args(kind, param, levels), C.byref(p), d)
+        return p.value, tuple(d)
+
+    def get_kinematics(self, kind, param=None, levels=None):
+        """numpy array [i, j, k] of the requested levels; only those are computed and copied."""
+        q, param, k_first, k_count = self._kinematics_args(kind, param, levels)
+        d = (C.c_int32 * 3)()
+        if self.lib.gb25_kinematics_dims(self.h, q, d) != 0:          # (an unknown id: the call below says so by name)
+            d[0], d[1], d[2] = self.field_dims("T", False)
+        nk = d[2] - k_first if k_count == -1 else k_count
+        out = np.empty((max(nk, 0), d[1], d[0]), dtype=self.dtype)
+        self._call("gb25_get_kinematics", q, param, k_first, k_count, out.ctypes.data_as(C.c_void_p))
+        return out.transpose(2, 1, 0)
+
+    def kinematics_stats(self, kind, param=None):
+        """gb25_get_kinematics_stats: gb25_field_stats of the whole quantity."""
+        out = FieldStats()
+        q, param, _, _ = self._kinematics_args(kind, param, None)
+        self._call("gb25_get_kinematics_stats", q, param, C.byref(out))
         return out
 
     # ---- block sums on the device (include/gb25.h: "block sums"; gb-25_amd/blocks.py).  source: a field name or a derived name at

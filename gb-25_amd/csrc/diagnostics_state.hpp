@@ -1,5 +1,5 @@
 // diagnostics_state.hpp -- every piece of memory and bookkeeping the read-only diagnostics own (diagnostics_host.hpp,
-// averages_host.hpp, classes_host.hpp, particles_host.hpp, spectrum_host.hpp, surfaces_host.hpp, stability_host.hpp, blocks_host.hpp, filters_host.hpp), as ONE member of gb25_model.
+// averages_host.hpp, classes_host.hpp, particles_host.hpp, spectrum_host.hpp, surfaces_host.hpp, stability_host.hpp, kinematics_host.hpp, blocks_host.hpp, filters_host.hpp), as ONE member of gb25_model.
 // Host only; included by gb25_api.hip behind the kernel headers (PartState: particle_kernels.hpp; SURF_MAX: surface_kernels.hpp;
 // GB25_A_COUNT and the info structs: include/gb25.h); like Field it is local to that translation unit, so the libraries export
 // nothing of it.
@@ -53,6 +53,7 @@ struct DiagState {
   // derived fields (gb25_compute_derived, gb25_get_field_levels): the packed result array -- one 2-D plane (the mixed-layer depth)
   // followed by room for the largest interior a field of this model has --, made by the first call that needs it; the TEOS-10
   // table folded at Z = 0 is part of the allocation of build_eos_tables, rebuilt with it and NOT freed here
+  // (flow kinematics, gb25_compute_kinematics: their packed result lies in the 3-D part of the same array)
   gb25::real* derived = nullptr;
   size_t derived_plane = 0, derived_elems = 0;
   const double* eos0 = nullptr;

@@ -269,6 +269,11 @@ class LocalSlabEnsemble:
         from .stability import gather_stability
         return gather_stability(self, kind, param, levels)
 
+    # flow kinematics: every slab computes its own interior from the halos the step left, placed by global offset (gb-25_amd/kinematics.py)
+    def kinematics(self, kind, param=None, levels=None):
+        from .kinematics import gather_kinematics
+        return gather_kinematics(self, kind, param, levels)
+
     # block sums: every slab reduces its own blocks -- a block that does not divide a slab's extents is that slab's error --, the
     # planes are placed by global offset (gb-25_amd/blocks.py)
     def block_sums(self, source, block, levels=None, level_weights=None, param=None):

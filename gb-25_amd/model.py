@@ -85,6 +85,13 @@ class Field:
         (filtered of this module)."""
         return _filter_sums(self._b, self.name, radius, kernel, stride).mean()
 
+    def gradient_magnitude(self, levels=None):
+        """|grad_h| of this field (T or S) at (c,c,c), [i, j, k], on the device (gradient_magnitude of this module)."""
+        if self.name not in ("T", "S"):
+            raise ValueError(f"gradient_magnitude: T or S, not {self.name!r}")
+        from .kinematics import kinematics
+        return kinematics(self._b, "gradient", self.name, levels)
+
     def zonal_spectrum(self, wavenumbers=None, levels=None):
         """(X [level, row, m] complex128, nonfinite_lines): the zonal wavenumber coefficients of every interior line, computed
         where the field lives (zonal_spectrum of this module)."""
@@ -367,6 +374,51 @@ def eddy_resolution(model, **host):
     Host arithmetic like deformation_radius."""
     from .stability import cell_spacings
     return deformation_radius(model, **host) / cell_spacings(model.backend)
+
+
+def _kinematics(model, kind, param, levels, host):
+    from .kinematics import kinematics               # (the kernel, or the numpy restatement on a backend without it)
+    return kinematics(model.backend, kind, param, levels, **host)
+
+
+def divergence(model, levels=None, **host):
+    """The horizontal divergence du/dx + dv/dy [s^-1] at (c,c,c), [i, j, k], on the device (include/gb25.h,
+    GB25_KIN_DIVERGENCE): the flux of u, v through the four faces of a cell over its area; 0 in the immersed cells.  levels =
+    (k_first, k_count), 0-based (k_count = -1: all from k_first on); only those are computed and copied."""
+    return _kinematics(model, "divergence", None, levels, host)
+
+
+def normal_strain(model, levels=None, **host):
+    """The normal strain rate du/dx - dv/dy [s^-1] at (c,c,c)."""
+    return _kinematics(model, "normal_strain", None, levels, host)
+
+
+def shear_strain(model, levels=None, **host):
+    """The shear strain rate dv/dx + du/dy [s^-1] at (f,f,c), shaped like the vorticity: its stencil with the inner sign turned."""
+    return _kinematics(model, "shear_strain", None, levels, host)
+
+
+def okubo_weiss(model, levels=None, **host):
+    """The Okubo-Weiss parameter W = s_n^2 + s_s^2 - zeta^2 [s^-2] at (c,c,c), the corner quantities averaged as squares to the
+    cell: W < 0 in vortex cores, W > 0 in the strain-dominated filaments between them."""
+    return _kinematics(model, "okubo_weiss", None, levels, host)
+
+
+def rossby_number(model, levels=None, **host):
+    """The local Rossby number zeta / f at (f,f,c), shaped like the vorticity; 0 where f is 0."""
+    return _kinematics(model, "rossby_number", None, levels, host)
+
+
+def gradient_magnitude(model, of, levels=None, **host):
+    """|grad_h x| [x per m] at (c,c,c) of x = "T", "S" or "potential_density" (referenced to the surface, formed on the fly):
+    centred differences that count a face into land or a wall as 0.  host: sigma = ... for a backend without get_derived."""
+    return _kinematics(model, "gradient", of, levels, host)
+
+
+def frontogenesis(model, of="potential_density", levels=None, **host):
+    """The frontogenesis function F = -(gx^2 du/dx + gx gy (dv/dx + du/dy) + gy^2 dv/dy) at (c,c,c) of x = "T", "S" or
+    "potential_density": the rate at which the horizontal flow sharpens (F > 0) or weakens the gradient of x."""
+    return _kinematics(model, "frontogenesis", of, levels, host)
 
 
 def _block_sums(b, source, block, levels=None, level_weights=None, param=None):

@@ -876,6 +876,73 @@ gb25_status gb25_compute_stability(gb25_model *m, gb25_stability q, double param
 gb25_status gb25_get_stability(gb25_model *m, gb25_stability q, double param, int32_t k_first, int32_t k_count, void *host);
 gb25_status gb25_get_stability_stats(gb25_model *m, gb25_stability q, double param, gb25_field_stats *out);
 
+/* ---- flow kinematics on the device (csrc/kinematics_kernels.hpp, k_kinematics_centre / k_kinematics_corner): the horizontal
+ *      velocity gradient beyond zeta -- the divergence, the normal and the shear strain rate, the Okubo-Weiss parameter that
+ *      separates vortex cores (W < 0) from the strain-dominated filaments between them (W > 0), the local Rossby number zeta / f --
+ *      and the horizontal gradient of T, S or the potential density with the frontogenesis function, which says whether the flow
+ *      is sharpening that gradient -- without the parents of u, v, T and S crossing PCIe.  Same contract as the derived fields and
+ *      the stability diagnostics: the state gb25_get_field would return, READ-ONLY for the schedule (nothing pinned, every
+ *      look-ahead alive), LOCAL on a rank (a rank's interior, from the x and y halos a completed step leaves, as the vorticity;
+ *      gather by global_offset: gb-25_amd/kinematics.py gather_kinematics), bitwise repeatable, no atomics, ONE launch per request
+ *      under GB25_K_DIAGNOSTICS on the model's stream.  Every grid type, both float types, any closure.
+ *
+ *      DEFINITIONS.  Values are read from the parent arrays as gb25_get_field(f, host, 1) returns them at that moment, halo cells
+ *      included; metrics are the numbers gb25_get_metric / gb25_get_metric2 return.  Every operation in fp64 on (double) of the
+ *      stored values, in the written order with the written parentheses, IEEE divisions and square roots, NO fused multiply-adds,
+ *      the result rounded once to the float type -- gb-25_amd/kinematics.py restates them with numpy bit for bit.  Indices are
+ *      those of the interior; i-1, j-1, i+1, j+1 reach one halo column or row.  k is the level, the same on both sides.
+ *        Metrics, grids with 2-D metrics | LatitudeLongitudeGrid:
+ *            DYFC(i,j) | GB25_M_DY      DXCF(i,j) | GB25_M_DXF(j)      AZCC(i,j) | GB25_M_AZC(j)      (the cell's faces, its area)
+ *            DYCF(i,j) | GB25_M_DY      DXFC(i,j) | GB25_M_DXC(j)      AZFF(i,j) | GB25_M_AZF(j)      (the corner: those of zeta)
+ *            f(i,j) = GB25_M2_FFF(i,j) | GB25_M_FCOR(j), j the row of y faces
+ *        at a cell (c,c,c):
+ *            ax = DYFC(i+1,j) * u(i+1,j) - DYFC(i,j) * u(i,j)          ay = DXCF(i,j+1) * v(i,j+1) - DXCF(i,j) * v(i,j)
+ *            GB25_KIN_DIVERGENCE     delta = (ax + ay) / AZCC(i,j)
+ *            GB25_KIN_NORMAL_STRAIN  s_n   = (ax - ay) / AZCC(i,j)
+ *        at a corner (f,f,c), the metrics, operands and order of GB25_D_VORTICITY:
+ *            dv = DYCF(i,j) * v(i,j) - DYCF(i-1,j) * v(i-1,j)          du = DXFC(i,j) * u(i,j) - DXFC(i,j-1) * u(i,j-1)
+ *            GB25_KIN_SHEAR_STRAIN   s_s  = (dv + du) / AZFF(i,j)          (zeta = (dv - du) / AZFF(i,j): the bits of GB25_D_VORTICITY
+ *                                                                            before its rounding)
+ *            GB25_KIN_ROSSBY_NUMBER  Ro   = zeta / f(i,j)
+ *        the mean over the four corners of a cell, of the fp64 corner values before any rounding:
+ *            <a> = 0.25 * ((a(i,j) + a(i+1,j)) + (a(i,j+1) + a(i+1,j+1)))
+ *            GB25_KIN_OKUBO_WEISS    W = (s_n * s_n + <s_s * s_s>) - <zeta * zeta>        (every square formed before its mean)
+ *        the gradient of x at a cell; x by param: 0 = T, 1 = S, 2 = sigma, (double) of the value
+ *        gb25_get_derived(GB25_D_POTENTIAL_DENSITY) hands out in a wet cell (rounded to the float type first, the same bits; formed
+ *        in the kernel by the same device function, in the halo column and row too, never stored):
+ *            dx(i) = (x(i,j) - x(i-1,j)) / DXFC(i,j)        dy(j) = (x(i,j) - x(i,j-1)) / DYCF(i,j)
+ *            gx = 0.5 * (dx(i) + dx(i+1))                     gy = 0.5 * (dy(j) + dy(j+1))
+ *            GB25_KIN_GRADIENT       sqrt(gx * gx + gy * gy)
+ *            GB25_KIN_FRONTOGENESIS  F = -(((gx * gx) * (0.5 * (delta + s_n)) + (gx * gy) * <s_s>) + (gy * gy) * (0.5 * (delta - s_n)))
+ *                -- the rate of change of |grad x|^2 / 2 by the horizontal flow: F > 0 sharpens the front
+ *      A value that is not finite yields what this arithmetic yields: nothing is clamped or counted; there is no masking beyond
+ *      the following.
+ *
+ *      ZEROS.  Where AZCC is 0: delta, s_n, W and F are 0.  Where AZFF is 0: s_s, zeta and Ro of that corner are 0 (the rule of
+ *      GB25_D_VORTICITY), in the means too.  Where f is 0: Ro is 0.  A difference dx(i) or dy(j) across a face with an immersed side
+ *      (k < kbot of either cell, kbot of gb25_get_bottom_info) is 0 -- no gradient through land --, and so is dy across the southern
+ *      and the northern edge of the GLOBAL grid: a wall, or the fold, beyond which no bottom is tabulated.  The zero is SELECTED:
+ *      what the immersed cell holds does not enter.  The five quantities at cells are 0 in an immersed cell (k < kbot(i,j)).  The
+ *      two at corners are not masked, as the vorticity is not; in <.> a corner on a wall row enters with what memory holds.
+ *
+ *      LOCATIONS AND LEVELS.  Divergence, normal strain, W, gradient and F live at (Center, Center, Center): Nx x Ny x Nz.  The
+ *      shear strain and Ro live at (Face, Face, Center) and have the dims of GB25_D_VORTICITY (the rows of v).  k_first, k_count
+ *      select levels as in gb25_get_derived (k_count = -1: all from k_first on); only the requested levels are computed, written
+ *      and copied.  param: the tracer of GB25_KIN_GRADIENT and GB25_KIN_FRONTOGENESIS, 0 .. 2; 0 for the others.
+ *      gb25_compute_kinematics: into the derived fields' array (made by the first call that needs it, freed by gb25_destroy); *dev:
+ *      elements of the library's float type, PACKED, device_dims = the columns, the rows, the levels of the window, i fastest;
+ *      read-only, complete when the call returns, valid until the next diagnostics call on m.  gb25_get_kinematics: the same and
+ *      one device-to-host copy of exactly those elements.  gb25_get_kinematics_stats: gb25_field_stats of the whole quantity,
+ *      positions relative to its box.  Refused by name before anything is allocated or launched: an unknown q, a param out of
+ *      range, a window outside 0 .. Nz, a NULL pointer, a model without a device. */
+typedef enum { GB25_KIN_DIVERGENCE = 0, GB25_KIN_NORMAL_STRAIN, GB25_KIN_SHEAR_STRAIN, GB25_KIN_OKUBO_WEISS,
+               GB25_KIN_ROSSBY_NUMBER, GB25_KIN_GRADIENT, GB25_KIN_FRONTOGENESIS, GB25_KIN_COUNT } gb25_kinematics;
+gb25_status gb25_kinematics_dims(const gb25_model *m, gb25_kinematics q, int32_t dims[3]);   /* needs no device */
+gb25_status gb25_compute_kinematics(gb25_model *m, gb25_kinematics q, int32_t param, int32_t k_first, int32_t k_count,
+                                    const void **dev, int32_t device_dims[3]);
+gb25_status gb25_get_kinematics(gb25_model *m, gb25_kinematics q, int32_t param, int32_t k_first, int32_t k_count, void *host);
+gb25_status gb25_get_kinematics_stats(gb25_model *m, gb25_kinematics q, int32_t param, gb25_field_stats *out);
+
 /* ---- block sums on the device (csrc/block_kernels.hpp, k_block_sums): the one reduction of the family that gb25_integrate_field
  *      (rows, levels, the total) does not have -- a MAP.  The interior of a field, or of a derived field, is cut into boxes of
  *      bx x by x bz points and every box gets measure = sum mu', first = sum mu' x, second = sum mu' x^2 in fp64: block means on a

@@ -22,6 +22,7 @@ export Config, Model, create, destroy!, first_time_step!, time_step!, loop!, ini
        Transport, transport, overturning, ACROSS_Y, ACROSS_X, TR_LINES, TR_PROFILE, TR_STREAMFUNCTION,
        DERIVED, derived_dims, compute_derived, get_derived, derived_stats, field_levels,
        STABILITY, stability_dims, compute_stability, get_stability, stability_stats,
+       KINEMATICS, KIN_TRACER, kinematics_dims, compute_kinematics, get_kinematics, kinematics_stats,
        Blocks, BlockInfo, block_dims, block_sums, compute_block_sums, derived_block_sums,
        AVG_MEANS, AVG_SQUARES, AVG_FLUXES, AVERAGE, AveragesInfo, averages_begin, averages_accumulate, averages_info, average_dims,
        get_average, averages_end,
@@ -487,6 +488,40 @@ function stability_stats(m::Model, q::Integer; param::Real = (q == STABILITY.ric
     out = Ref{FieldStats}()
     check(m, ccall((:gb25_get_stability_stats, m.lib), Cint, (Ptr{Cvoid}, Cint, Float64, Ref{FieldStats}), m.ptr, q, param, out),
           "gb25_get_stability_stats")
+    return out[]
+end
+# ---- flow kinematics on the device (gb25_kinematics_dims / gb25_compute_kinematics / gb25_get_kinematics /
+#      gb25_get_kinematics_stats): definitions in include/gb25.h.  k_first counts levels, 0-based like the ABI; k_count = -1: all from
+#      k_first on.  param: the tracer of the gradient and of the frontogenesis function (KIN_TRACER), 0 for the others.
+const KINEMATICS = (divergence = Cint(0), normal_strain = Cint(1), shear_strain = Cint(2), okubo_weiss = Cint(3),
+                    rossby_number = Cint(4), gradient = Cint(5), frontogenesis = Cint(6))
+const KIN_TRACER = (T = Int32(0), S = Int32(1), potential_density = Int32(2))
+"extents of a kinematics quantity: (Nx, Ny, Nz) at the cells; the shear strain and the Rossby number have the rows of v"
+function kinematics_dims(m::Model, q::Integer)
+    out = zeros(Int32, 3)
+    check(m, ccall((:gb25_kinematics_dims, m.lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Int32}), m.ptr, q, out), "gb25_kinematics_dims")
+    return Tuple(Int.(out))
+end
+"(device pointer, dims) of the packed result; read-only, valid until the next diagnostics call on m"
+function compute_kinematics(m::Model{FT}, q::Integer; param::Integer = 0, k_first::Integer = 0, k_count::Integer = -1) where {FT}
+    p, dims = Ref{Ptr{Cvoid}}(C_NULL), zeros(Int32, 3)
+    check(m, ccall((:gb25_compute_kinematics, m.lib), Cint, (Ptr{Cvoid}, Cint, Int32, Int32, Int32, Ref{Ptr{Cvoid}}, Ptr{Int32}),
+                   m.ptr, q, param, k_first, k_count, p, dims), "gb25_compute_kinematics")
+    return Ptr{FT}(p[]), Tuple(Int.(dims))
+end
+"a kinematics quantity's requested levels as an Array{FT, 3}; only those levels are computed and copied"
+function get_kinematics(m::Model{FT}, q::Integer; param::Integer = 0, k_first::Integer = 0, k_count::Integer = -1) where {FT}
+    nx, ny, nz = kinematics_dims(m, q)
+    out = Array{FT}(undef, nx, ny, k_count == -1 ? nz - k_first : k_count)
+    check(m, ccall((:gb25_get_kinematics, m.lib), Cint, (Ptr{Cvoid}, Cint, Int32, Int32, Int32, Ptr{Cvoid}),
+                   m.ptr, q, param, k_first, k_count, out), "gb25_get_kinematics")
+    return out
+end
+function kinematics_stats(m::Model, q::Integer; param::Integer = 0)
+    check_diagnostic_structs(m)
+    out = Ref{FieldStats}()
+    check(m, ccall((:gb25_get_kinematics_stats, m.lib), Cint, (Ptr{Cvoid}, Cint, Int32, Ref{FieldStats}), m.ptr, q, param, out),
+          "gb25_get_kinematics_stats")
     return out[]
 end
 # ---- block sums on the device (gb25_block_dims / gb25_derived_block_dims / gb25_get_block_sums / gb25_compute_block_sums /

@@ -28,8 +28,9 @@ def stir(m, seed=5):
 @pytest.mark.parametrize("float_type,tol", [("Float64", 1e-12), ("Float32", 2e-6)])
 @pytest.mark.parametrize("grid_type", ["simple_lat_lon", "gaussian_islands"])
 def test_the_flux_solve_matches_the_oracle(grid_type, float_type, tol):
-    """compute_atmosphere_ocean_fluxes! alone: J^u, J^v, J^T, J^S from the same state (the solve runs in fp64 on both sides;
-    with a Float32 state the difference is the rounding of the fluxes themselves)."""
+    """compute_atmosphere_ocean_fluxes! alone: J^u, J^v, J^T, J^S from the same state.  The oracle solves in fp64 in both of its
+    builds; the Float64 library does too, the Float32 library runs the five iterations in fp32 (thermodynamics and the fluxes
+    themselves stay fp64), which is what its tolerance covers -- tests/test_gpu_forcing_spec.py bounds that cost cell by cell."""
     models = []
     for arch in (gb.GPU(float_type=float_type), CPU("f64" if float_type == "Float64" else "f32")):
         m = gb.baroclinic_instability_model(arch, 96, 48, 6, dt=30.0, grid_type=grid_type)

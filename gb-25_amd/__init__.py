@@ -38,6 +38,7 @@ from .spectra import (combine_spectra, cospectrum, dominant_wavenumber, host_tab
 from .surfaces import gather_surfaces, on_surfaces_host, surfaces_of_profiles
 from .stability import gather_stability, stability_host, stability_of_columns
 from .kinematics import gather_kinematics, kinematics_host, kinematics_pieces
+from .eddies import (ZonalEddy, combine_zonal_eddy, lorenz_cycle, lorenz_cycle_of_records, zonal_eddy, zonal_eddy_host)
 from .blocks import BlockSums, block_sums_host, depth_weights, gather_blocks, sums_of_blocks
 from .filters import FilterSums, filter_of_planes, filter_sums_host, kernel_weights, rows_for_length
 # (the submodule first, as for the averages: the name `particles` of the package is the function)

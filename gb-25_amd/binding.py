@@ -64,6 +64,7 @@ ABI_SYMBOLS = [
     "gb25_compute_on_surfaces", "gb25_get_on_surfaces",
     "gb25_stability_dims", "gb25_compute_stability", "gb25_get_stability", "gb25_get_stability_stats",
     "gb25_kinematics_dims", "gb25_compute_kinematics", "gb25_get_kinematics", "gb25_get_kinematics_stats",
+    "gb25_zonal_eddy_bytes", "gb25_zonal_eddy_dims", "gb25_get_zonal_eddy",
     "gb25_block_info_bytes", "gb25_block_dims", "gb25_derived_block_dims", "gb25_get_block_sums", "gb25_compute_block_sums",
     "gb25_get_derived_block_sums",
     "gb25_filter_info_bytes", "gb25_filter_dims", "gb25_derived_filter_dims", "gb25_get_filter_sums", "gb25_compute_filter_sums",
@@ -98,6 +99,8 @@ STABILITY_DEFAULT_PARAM = {"richardson": 1e-12}
 KINEMATICS_IDS = {"divergence": 0, "normal_strain": 1, "shear_strain": 2, "okubo_weiss": 3, "rossby_number": 4, "gradient": 5,
                   "frontogenesis": 6}
 KINEMATICS_TRACERS = {"T": 0, "S": 1, "potential_density": 2}
+# gb25_zonal_eddy_variable (include/gb25.h): the six centred variables of a line record, in the record's order
+ZONAL_EDDY_VARIABLES = {"U": 0, "V": 1, "W": 2, "T": 3, "S": 4, "SIGMA": 5}
 AVERAGE_GROUPS = {"means": 1, "squares": 2, "fluxes": 4}              # gb25_average_group
 # gb25_average: name -> id; the first six are the MEANS, the next five the SQUARES, the last six the FLUXES
 AVERAGE_IDS = {n: q for q, n in enumerate(["u", "v", "w", "T", "S", "eta", "uu", "vv", "TT", "SS", "etaeta",
@@ -213,6 +216,17 @@ class Moments(_Record):
 
 MOMENTS_DTYPE = np.dtype([("measure", np.float64), ("first", np.float64), ("second", np.float64),
                           ("points", np.int64), ("nonfinite", np.int64)])
+
+
+class ZonalEddyRow(_Record):
+    """gb25_zonal_eddy_row (include/gb25.h): of one line (row j, level k) the measure, the first moments and the means of the six
+    centred variables, the 21 comoments of their deviations (p <= q, row-major), the counted and the skipped cells."""
+    _fields_ = [("measure", C.c_double), ("first", C.c_double * 6), ("mean", C.c_double * 6), ("co", C.c_double * 21),
+                ("points", C.c_int64), ("nonfinite", C.c_int64)]
+
+
+ZONAL_EDDY_DTYPE = np.dtype([("measure", np.float64), ("first", np.float64, (6,)), ("mean", np.float64, (6,)),
+                             ("co", np.float64, (21,)), ("points", np.int64), ("nonfinite", np.int64)])
 
 
 class Blocks(C.Structure):
@@ -483,6 +497,8 @@ def load_library(float_type="Float32"):
     lib.gb25_compute_kinematics.argtypes = [P, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.POINTER(P), C.POINTER(C.c_int32)]
     lib.gb25_get_kinematics.argtypes = [P, C.c_int, C.c_int32, C.c_int32, C.c_int32, P]
     lib.gb25_get_kinematics_stats.argtypes = [P, C.c_int, C.c_int32, C.POINTER(FieldStats)]
+    lib.gb25_zonal_eddy_dims.argtypes = [P, C.POINTER(C.c_int32)]
+    lib.gb25_get_zonal_eddy.argtypes = [P, C.c_int32, C.c_int32, P, P]
     lib.gb25_block_dims.argtypes = [P, C.c_int, C.POINTER(Blocks), C.POINTER(C.c_int32)]
     lib.gb25_derived_block_dims.argtypes = [P, C.c_int, C.POINTER(Blocks), C.POINTER(C.c_int32)]
     lib.gb25_get_block_sums.argtypes = [P, C.c_int, C.POINTER(Blocks), P, P, P, P, C.POINTER(BlockInfo)]
@@ -542,7 +558,7 @@ def load_library(float_type="Float32"):
                        ("gb25_budget_bytes", Budget), ("gb25_transport_bytes", Transport),
                        ("gb25_class_sum_bytes", ClassSum), ("gb25_spectral_coefficient_bytes", SpectralCoefficient),
                        ("gb25_averages_info_bytes", AveragesInfo), ("gb25_particles_info_bytes", ParticlesInfo),
-                       ("gb25_tracer_spec_bytes", TracerSpec),
+                       ("gb25_tracer_spec_bytes", TracerSpec), ("gb25_zonal_eddy_bytes", ZonalEddyRow),
                        ("gb25_block_info_bytes", BlockInfo), ("gb25_filter_info_bytes", FilterInfo),
                        ("gb25_checkpoint_info_bytes", CheckpointInfo), ("gb25_restore_info_bytes", RestoreInfo)):
         getattr(lib, fn).restype = C.c_int32
@@ -904,6 +920,29 @@ class HipBackend:
         q, param, _, _ = self._kinematics_args(kind, param, None)
         self._call("gb25_get_kinematics_stats", q, param, C.byref(out))
         return out
+
+    # ---- zonal-mean and eddy statistics on the device (include/gb25.h: "zonal-mean and eddy statistics"; gb-25_amd/eddies.py)
+    def zonal_eddy_dims(self):
+        """gb25_zonal_eddy_dims: (rows, levels) of this rank's line records.  Needs no device."""
+        d = (C.c_int32 * 2)()
+        self._call("gb25_zonal_eddy_dims", d)
+        return tuple(d)
+
+    def zonal_eddy(self, levels=None, means=None):
+        """gb25_get_zonal_eddy: the line records of the levels (k_first, k_count) (None: all), numpy records of ZONAL_EDDY_DTYPE
+        [j, kk].  means: None, or float64 [j, kk, 6] -- the means the deviations are taken about (echoed in "mean")."""
+        Ny, Nz = self.zonal_eddy_dims()
+        k_first, k_count = (0, -1) if levels is None else (int(levels[0]), int(levels[1]))
+        nk = Nz - k_first if k_count == -1 else k_count
+        out = np.zeros((max(nk, 1), Ny), ZONAL_EDDY_DTYPE)      # (a window the library will refuse still gets a buffer)
+        mp = None
+        if means is not None:
+            mh = np.ascontiguousarray(np.asarray(means, np.float64).transpose(1, 0, 2))
+            if mh.shape != (nk, Ny, 6):
+                raise ValueError(f"means: expected shape {(Ny, nk, 6)}, got {np.shape(means)}")
+            mp = mh.ctypes.data_as(C.c_void_p)
+        self._call("gb25_get_zonal_eddy", k_first, k_count, mp, out.ctypes.data_as(C.c_void_p))
+        return out.T
 
     # ---- block sums on the device (include/gb25.h: "block sums"; gb-25_amd/blocks.py).  source: a field name or a derived name at
     #      (c,c) ("kinetic_energy", "density_anomaly", "potential_density", "mixed_layer_depth" with param = the threshold);

@@ -1,5 +1,5 @@
 // diagnostics_state.hpp -- every piece of memory and bookkeeping the read-only diagnostics own (diagnostics_host.hpp,
-// averages_host.hpp, classes_host.hpp, particles_host.hpp, spectrum_host.hpp, surfaces_host.hpp, stability_host.hpp, kinematics_host.hpp, blocks_host.hpp, filters_host.hpp), as ONE member of gb25_model.
+// averages_host.hpp, classes_host.hpp, particles_host.hpp, spectrum_host.hpp, surfaces_host.hpp, stability_host.hpp, kinematics_host.hpp, zonal_eddy_host.hpp, blocks_host.hpp, filters_host.hpp), as ONE member of gb25_model.
 // Host only; included by gb25_api.hip behind the kernel headers (PartState: particle_kernels.hpp; SURF_MAX: surface_kernels.hpp;
 // GB25_A_COUNT and the info structs: include/gb25.h); like Field it is local to that translation unit, so the libraries export
 // nothing of it.
@@ -78,6 +78,8 @@ struct DiagState {
   // stability diagnostics (gb25_compute_stability, gb25_get_stability): the packed result array, room for Nx x Ny x (Nz + 1)
   // values, made by the first call (ONE size per model, nothing grows: no result buffer)
   gb25::real* stability = nullptr;
+  // zonal-mean and eddy statistics (gb25_get_zonal_eddy): a result buffer -- the line records of one call, then the caller's means
+  DiagBuffer zonal_eddy;
   // block sums (gb25_get_block_sums, gb25_compute_block_sums, gb25_get_derived_block_sums): a result buffer -- the three counts of
   // the info record (BlockCounts, padded to 32 bytes), the level weights (Nz + 1 doubles), the planes measure | first | second
   // of one call, then the count slots of the waves of its launch.  The host copy of the weights the upload reads (a word of the
@@ -156,7 +158,7 @@ struct DiagState {
     drop(derived);
     drop(transport);
     drop(stability);
-    for (DiagBuffer* b : {&class_sums, &spectrum, &surfaces, &blocks, &filters}) b->drop();
+    for (DiagBuffer* b : {&class_sums, &spectrum, &surfaces, &zonal_eddy, &blocks, &filters}) b->drop();
     release_tables();
     release_averages();
     release_particles();

@@ -17,6 +17,7 @@
 #include "surface_kernels.hpp"
 #include "stability_kernels.hpp"
 #include "kinematics_kernels.hpp"
+#include "zonal_eddy_kernels.hpp"
 #include "block_kernels.hpp"
 #include "filter_kernels.hpp"
 #include "restart_kernels.hpp"
@@ -3483,5 +3484,6 @@ gb25_status gb25_profile_get(gb25_model* m, gb25_kernel k, int64_t* launches, do
 #include "surfaces_host.hpp"
 #include "stability_host.hpp"
 #include "kinematics_host.hpp"
+#include "zonal_eddy_host.hpp"
 #include "blocks_host.hpp"
 #include "filters_host.hpp"

@@ -943,6 +943,61 @@ gb25_status gb25_compute_kinematics(gb25_model *m, gb25_kinematics q, int32_t pa
 gb25_status gb25_get_kinematics(gb25_model *m, gb25_kinematics q, int32_t param, int32_t k_first, int32_t k_count, void *host);
 gb25_status gb25_get_kinematics_stats(gb25_model *m, gb25_kinematics q, int32_t param, gb25_field_stats *out);
 
+/* ---- zonal-mean and eddy statistics on the device (csrc/zonal_eddy_kernels.hpp, k_zonal_eddy): the split of the flow into the
+ *      mean along a line and the eddies about it -- the second moments about the ZONAL mean and the covariances of two different
+ *      variables along a row, which no other family here has: the eddy kinetic energy, the eddy heat and momentum fluxes [V*T*],
+ *      [U*V*] by latitude and depth, the terms of the Lorenz energy cycle (gb-25_amd/eddies.py, lorenz_cycle).  Same contract as
+ *      every diagnostic here: the state gb25_get_field would return (the corrected velocities and the stored w a returned call
+ *      leaves), READ-ONLY for the schedule (nothing pinned, every look-ahead alive), LOCAL on a rank, bitwise repeatable, no
+ *      atomics, launches under GB25_K_DIAGNOSTICS on the model's stream.
+ *
+ *      VARIABLES.  Six per interior cell (i, j, k), fp64 on (double) of the stored values with floating-point contraction OFF (no
+ *      fused multiply-adds: every product, sum and difference rounds by itself), all at the cell centre:
+ *        GB25_ZE_U      0.5 (u(i,j,k) + u(i+1,j,k))
+ *        GB25_ZE_V      0.5 (v(i,j,k) + v(i,j+1,k))
+ *        GB25_ZE_W      0.5 (w(i,j,k) + w(i,j,k+1))
+ *        GB25_ZE_T      T(i,j,k)
+ *        GB25_ZE_S      S(i,j,k)
+ *        GB25_ZE_SIGMA  the value gb25_get_derived(GB25_D_POTENTIAL_DENSITY) hands out for the cell, rounded to the float type first
+ *      u(i+1) and v(j+1) beyond the interior are the halo cells the step leaves filled: the periodic image, a neighbour's column
+ *      on a slab, the wall row, the fold's image.
+ *
+ *      WEIGHT.  mu(i,j,k) is THE MEASURE of gb25_integrate_field for a (c,c,c) field: area x thickness x 1/2 on the pivot row of
+ *      a folded grid x wet mask, from the same tables by the same expression.  A cell COUNTS iff mu > 0 and all six values are
+ *      finite; a cell with mu > 0 and any value not finite is skipped whole in both passes and counted once in `nonfinite`; an
+ *      immersed cell is invisible.
+ *
+ *      RECORD.  A line is interior row j, level k, along the grid's index i (a latitude circle on the LatitudeLongitudeGrid only,
+ *      as for the spectra; the sums are defined on every grid type).  Pass 1 over the line forms measure, first, points and
+ *      nonfinite; then mean[q] = first[q] / measure, ONE IEEE division (+0.0 if measure == 0), or the caller's means; pass 2 forms
+ *      d_q = x_q - mean[q] (one fp64 subtraction) and co[p, q] = sum (mu d_p) d_q for p <= q, row-major over (p, q): index
+ *      p (11 - p) / 2 + q.  The deviations are taken about the ROUNDED mean, hence the two passes.
+ *
+ *      ORDER, fixed: that of the ROWS of gb25_integrate_field.  One wave per line; the line is cut into chunks of four cells
+ *      aligned to four elements in MEMORY -- the first chunk holds the 4 - a first cells, a = (H + (Nx + 2H) ((j + H) + (Ny + 2H)
+ *      (k + H))) mod 4 the element offset of the line's first cell in the parent array of T, whose allocation is aligned --; lane
+ *      l takes the chunks l, l + 64, ... and adds its cells in ascending i; the 64 lanes are combined by lane l <- lane l + lane
+ *      (l + off), off = 1, 2, 4, 8, 16, 32, the answer in lane 0.  Every sum starts from +0.0, a cell that does not count adds
+ *      nothing.  measure and points of a line equal the ROWS record of gb25_integrate_field(GB25_T) bit for bit.
+ *
+ *      gb25_get_zonal_eddy: the records of the levels [k_first, k_first + k_count) (k_count = -1: all from k_first on), out[kk Ny +
+ *      j] for level k_first + kk and local row j.  means: NULL, or [k_count][Ny][6] doubles -- pass 1 still runs and reports measure
+ *      and first, the deviations are taken about the caller's numbers and mean echoes them: the ranks of a decomposition share one
+ *      mean this way (gb-25_amd/eddies.py, combine_zonal_eddy), and eddies about a time mean are taken this way.  Refused by name,
+ *      the model untouched: a NULL out, a window outside 0 .. Nz, a means entry that is not finite, a model without a device.
+ *      gb25_zonal_eddy_dims: the rows and the levels of the rank, from the configuration alone. */
+typedef enum { GB25_ZE_U = 0, GB25_ZE_V, GB25_ZE_W, GB25_ZE_T, GB25_ZE_S, GB25_ZE_SIGMA, GB25_ZE_COUNT } gb25_zonal_eddy_variable;
+typedef struct {
+  double measure;        /* sum mu over the counted cells                                                */
+  double first[6];       /* sum mu x_q                                                                   */
+  double mean[6];        /* first[q] / measure; +0.0 if measure == 0; or the caller's means, echoed      */
+  double co[21];         /* sum (mu d_p) d_q, p <= q, row-major over (p, q); d_q = x_q - mean[q]         */
+  int64_t points, nonfinite;
+} gb25_zonal_eddy_row;
+int32_t gb25_zonal_eddy_bytes(void);    /* sizeof the struct as THIS library was built */
+gb25_status gb25_zonal_eddy_dims(const gb25_model *m, int32_t dims[2]);   /* rows, levels; needs no device */
+gb25_status gb25_get_zonal_eddy(gb25_model *m, int32_t k_first, int32_t k_count, const double *means, gb25_zonal_eddy_row *out);
+
 /* ---- block sums on the device (csrc/block_kernels.hpp, k_block_sums): the one reduction of the family that gb25_integrate_field
  *      (rows, levels, the total) does not have -- a MAP.  The interior of a field, or of a derived field, is cut into boxes of
  *      bx x by x bz points and every box gets measure = sum mu', first = sum mu' x, second = sum mu' x^2 in fp64: block means on a

@@ -10,6 +10,7 @@ from .correctness import approx_equal, combine_diffs, combine_stats, compare_sta
 from .integrals import cell_measure, combine_budgets, combine_moments, fold_records, integrate_host
 # (the submodule first: the name `averages` of the package is the function of .model, imported after it)
 from .averages import (AveragesHost, average_terms, eddy_flux, eddy_kinetic_energy, gather_averages, tracer_variance)
+from .regions import Regions, label_host, region_records_host, regions_host, regions_of_arrays
 from .model import (CATKEVerticalDiffusivity, default_ocean_closure, Field, HydrostaticFreeSurfaceModel, VerticalScalarDiffusivity,
                     baroclinic_instability_model, budget, density_anomaly, first_time_step, initialize, kinetic_energy,
                     mixed_layer_depth, potential_density, vorticity,
@@ -19,6 +20,7 @@ from .model import (CATKEVerticalDiffusivity, default_ocean_closure, Field, Hydr
                     divergence, frontogenesis, gradient_magnitude, normal_strain, okubo_weiss, rossby_number, shear_strain,
                     coarsen, column_integral, depth_mean, heat_content, subgrid_variance,
                     eddy_part, filtered, subfilter_variance,
+                    eddy_census, regions,
                     heat_transport, meridional_transport, overturning, section_transport,
                     overturning_in_classes, water_mass_census, zonal_power_spectrum, zonal_spectrum,
                     Averages, averages, run_averaged,

@@ -69,6 +69,7 @@ ABI_SYMBOLS = [
     "gb25_get_derived_block_sums",
     "gb25_filter_info_bytes", "gb25_filter_dims", "gb25_derived_filter_dims", "gb25_get_filter_sums", "gb25_compute_filter_sums",
     "gb25_get_derived_filter_sums",
+    "gb25_region_bytes", "gb25_regions_info_bytes", "gb25_region_dims", "gb25_label_regions", "gb25_get_regions",
     "gb25_averages_info_bytes", "gb25_averages_begin", "gb25_averages_accumulate", "gb25_averages_get_info", "gb25_average_dims",
     "gb25_get_average", "gb25_average_device_ptr", "gb25_averages_end",
     "gb25_particles_info_bytes", "gb25_particles_begin", "gb25_particles_set", "gb25_particles_get", "gb25_particles_advance",
@@ -99,6 +100,12 @@ STABILITY_DEFAULT_PARAM = {"richardson": 1e-12}
 KINEMATICS_IDS = {"divergence": 0, "normal_strain": 1, "shear_strain": 2, "okubo_weiss": 3, "rossby_number": 4, "gradient": 5,
                   "frontogenesis": 6}
 KINEMATICS_TRACERS = {"T": 0, "S": 1, "potential_density": 2}
+# gb25_region_source, gb25_region_cmp (include/gb25.h): what the criterion of the coherent regions may be, by source
+REGION_SOURCES = {"field": 0, "derived": 1, "kinematics": 2}
+REGION_FIELDS = ("T", "S", "e")
+REGION_DERIVED = ("kinetic_energy", "density_anomaly", "potential_density")
+REGION_KINEMATICS = ("divergence", "normal_strain", "okubo_weiss", "gradient", "frontogenesis")
+REGION_CMP = {"below": 0, "above": 1}
 # gb25_zonal_eddy_variable (include/gb25.h): the six centred variables of a line record, in the record's order
 ZONAL_EDDY_VARIABLES = {"U": 0, "V": 1, "W": 2, "T": 3, "S": 4, "SIGMA": 5}
 AVERAGE_GROUPS = {"means": 1, "squares": 2, "fluxes": 4}              # gb25_average_group
@@ -253,6 +260,30 @@ class FilterInfo(_Record):
     outputs whose y window was cut, the global offset of the fine interior."""
     _fields_ = [("dims", C.c_int32 * 3), ("reserved", C.c_int32), ("nonfinite", C.c_int64), ("empty", C.c_int64),
                 ("clipped", C.c_int64), ("global_offset", C.c_int32 * 3), ("reserved2", C.c_int32)]
+
+
+class Region(_Record):
+    """gb25_region (include/gb25.h): one connected region of a thresholded level -- its cells, key, box, whether it crosses the
+    x seam, the sums weighted by the measure, the centroid sums about the key, the extreme value and its cell."""
+    _fields_ = [("cells", C.c_int32), ("key_i", C.c_int32), ("key_j", C.c_int32), ("i_min", C.c_int32), ("i_max", C.c_int32),
+                ("j_min", C.c_int32), ("j_max", C.c_int32), ("wraps", C.c_int32), ("extreme_i", C.c_int32), ("extreme_j", C.c_int32),
+                ("measure", C.c_double), ("first", C.c_double), ("second", C.c_double), ("carried", C.c_double),
+                ("sum_di", C.c_double), ("sum_dj", C.c_double), ("extreme", C.c_double)]
+
+
+REGION_DTYPE = np.dtype([("cells", np.int32), ("key_i", np.int32), ("key_j", np.int32), ("i_min", np.int32), ("i_max", np.int32),
+                         ("j_min", np.int32), ("j_max", np.int32), ("wraps", np.int32), ("extreme_i", np.int32), ("extreme_j", np.int32),
+                         ("measure", np.float64), ("first", np.float64), ("second", np.float64), ("carried", np.float64),
+                         ("sum_di", np.float64), ("sum_dj", np.float64), ("extreme", np.float64)])
+
+
+class RegionsInfo(_Record):
+    """gb25_regions_info (include/gb25.h), one per level: the true count of regions, how many records were stored, the foreground
+    cells and the wet cells whose criterion is not finite."""
+    _fields_ = [("regions", C.c_int32), ("stored", C.c_int32), ("foreground_cells", C.c_int64), ("nonfinite_cells", C.c_int64)]
+
+
+REGIONS_INFO_DTYPE = np.dtype([("regions", np.int32), ("stored", np.int32), ("foreground_cells", np.int64), ("nonfinite_cells", np.int64)])
 
 
 class Transport(_Record):
@@ -509,6 +540,10 @@ def load_library(float_type="Float32"):
     lib.gb25_get_filter_sums.argtypes = [P, C.c_int, C.POINTER(Filter), P, P, P, P, P, P, C.POINTER(FilterInfo)]
     lib.gb25_compute_filter_sums.argtypes = [P, C.c_int, C.POINTER(Filter), P, P, P, C.POINTER(FilterInfo), C.POINTER(P), C.POINTER(C.c_int32)]
     lib.gb25_get_derived_filter_sums.argtypes = [P, C.c_int, C.c_double, C.POINTER(Filter), P, P, P, P, P, P, C.POINTER(FilterInfo)]
+    lib.gb25_region_dims.argtypes = [P, C.POINTER(C.c_int32)]
+    lib.gb25_label_regions.argtypes = [P, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int, C.c_double, C.c_int32, C.c_int32, C.c_int32,
+                                       C.POINTER(P), C.POINTER(P), P]
+    lib.gb25_get_regions.argtypes = [P, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int, C.c_double, C.c_int32, C.c_int32, C.c_int32, P, P, P]
     lib.gb25_averages_begin.argtypes = [P, C.c_int32, C.c_int32, C.c_int32]
     lib.gb25_averages_accumulate.argtypes = [P, C.c_double]
     lib.gb25_averages_get_info.argtypes = [P, C.POINTER(AveragesInfo)]
@@ -560,6 +595,7 @@ def load_library(float_type="Float32"):
                        ("gb25_averages_info_bytes", AveragesInfo), ("gb25_particles_info_bytes", ParticlesInfo),
                        ("gb25_tracer_spec_bytes", TracerSpec), ("gb25_zonal_eddy_bytes", ZonalEddyRow),
                        ("gb25_block_info_bytes", BlockInfo), ("gb25_filter_info_bytes", FilterInfo),
+                       ("gb25_region_bytes", Region), ("gb25_regions_info_bytes", RegionsInfo),
                        ("gb25_checkpoint_info_bytes", CheckpointInfo), ("gb25_restore_info_bytes", RestoreInfo)):
         getattr(lib, fn).restype = C.c_int32
         if getattr(lib, fn)() != C.sizeof(struct):
@@ -1070,6 +1106,70 @@ class HipBackend:
         p, d, info = C.c_void_p(), (C.c_int32 * 3)(), FilterInfo()
         self._call("gb25_compute_filter_sums", FIELD_IDS[field], C.byref(flt), *w, C.byref(info), C.byref(p), d)
         return p.value, tuple(d), info
+
+    # ---- coherent regions on the device (include/gb25.h: "coherent regions"; gb-25_amd/regions.py).  source: "T", "S", "e"; a
+    #      derived name at (c,c,c) ("kinetic_energy", "density_anomaly", "potential_density"); a kinematics name at (c,c,c)
+    #      ("divergence", "normal_strain", "okubo_weiss", "gradient", "frontogenesis", the last two with param = their tracer) -- or
+    #      (kind, id) of the header's enumerations; cmp: "below" | "above"; levels = (k_first, k_count), k_count = -1 or None: all
+    def region_dims(self):
+        """gb25_region_dims: (Nx, Ny, levels).  Needs no device."""
+        d = (C.c_int32 * 3)()
+        self._call("gb25_region_dims", d)
+        return tuple(d)
+
+    @staticmethod
+    def _region_args(source, param, carry, cmp, threshold, levels, max_regions):
+        if isinstance(source, tuple):
+            kind, q = REGION_SOURCES.get(source[0], source[0]), source[1]
+        elif source in KINEMATICS_IDS:
+            kind, q = REGION_SOURCES["kinematics"], KINEMATICS_IDS[source]
+        elif source in DERIVED_IDS:
+            kind, q = REGION_SOURCES["derived"], DERIVED_IDS[source]
+        elif source in FIELD_IDS:
+            kind, q = REGION_SOURCES["field"], FIELD_IDS[source]
+        else:
+            raise GB25Error(f"regions: no field, derived field or kinematics quantity {source!r}")
+        if carry is not None and carry not in FIELD_IDS and not isinstance(carry, int):
+            raise GB25Error(f"regions: carried_field: no field {carry!r}")
+        k_first, k_count = (0, -1) if levels is None else levels
+        param = 0 if param is None else KINEMATICS_TRACERS.get(param, param)
+        return (int(kind), int(q), int(param), -1 if carry is None else int(FIELD_IDS.get(carry, carry)), int(REGION_CMP.get(cmp, cmp)),
+                float(threshold), int(k_first), int(k_count), int(max_regions))
+
+    def _region_buffers(self, args):
+        """(args with max_regions clamped, levels of the window, records per level) for the host buffers of a call.  A level holds
+        at most ceil(Nx Ny / 2) regions, so a larger max_regions is clamped to that: no record is lost.  What the library will
+        refuse -- a window outside the levels, max_regions < 1 -- gets the smallest buffers and is passed on for its named refusal."""
+        Nx, Ny, Nz = self.region_dims()
+        k_first, k_count, cap = args[6], args[7], args[8]
+        nk = Nz - k_first if k_count == -1 else k_count
+        if not (0 <= k_first < Nz and 1 <= nk <= Nz - k_first):
+            nk = 1
+        if cap >= 1:
+            cap = min(cap, (Nx * Ny + 1) // 2)
+        return args[:8] + (cap,), nk, max(cap, 1)
+
+    def get_regions(self, source, cmp, threshold, levels=None, carry=None, max_regions=4096, param=None, labels=True):
+        """gb25_get_regions: (labels int32 [i, j, kk] or None, records REGION_DTYPE [kk, max_regions], infos REGIONS_INFO_DTYPE
+        [kk]); the records of a level beyond its `stored` are zero.  labels=False: only records and infos cross PCIe.  max_regions
+        beyond ceil(Nx Ny / 2), the most a level can hold, is clamped to that."""
+        args, nk, cap = self._region_buffers(self._region_args(source, param, carry, cmp, threshold, levels, max_regions))
+        Nx, Ny, _ = self.region_dims()
+        lab = np.empty((nk, Ny, Nx), np.int32) if labels else None
+        rec = np.zeros((nk, cap), REGION_DTYPE)
+        info = np.zeros(nk, REGIONS_INFO_DTYPE)
+        self._call("gb25_get_regions", *args, None if lab is None else lab.ctypes.data_as(C.c_void_p), rec.ctypes.data_as(C.c_void_p),
+                   info.ctypes.data_as(C.c_void_p))
+        return (None if lab is None else lab.transpose(2, 1, 0)), rec, info
+
+    def label_regions(self, source, cmp, threshold, levels=None, carry=None, max_regions=4096, param=None):
+        """gb25_label_regions: (device pointer of the label planes, device pointer of the records, infos); read-only, valid until the
+        next call on this model.  max_regions is clamped as for get_regions: the records of level kk start at kk times that."""
+        args, nk, _ = self._region_buffers(self._region_args(source, param, carry, cmp, threshold, levels, max_regions))
+        info = np.zeros(nk, REGIONS_INFO_DTYPE)
+        pl, pr = C.c_void_p(), C.c_void_p()
+        self._call("gb25_label_regions", *args, C.byref(pl), C.byref(pr), info.ctypes.data_as(C.c_void_p))
+        return pl.value, pr.value, info
 
     # ---- time averages accumulated on the device (include/gb25.h: "time averages and eddy fluxes"); names: AVERAGE_IDS
     def averages_begin(self, groups=("means", "squares", "fluxes"), levels=None):

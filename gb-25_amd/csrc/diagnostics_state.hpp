@@ -1,5 +1,5 @@
 // diagnostics_state.hpp -- every piece of memory and bookkeeping the read-only diagnostics own (diagnostics_host.hpp,
-// averages_host.hpp, classes_host.hpp, particles_host.hpp, spectrum_host.hpp, surfaces_host.hpp, stability_host.hpp, kinematics_host.hpp, zonal_eddy_host.hpp, blocks_host.hpp, filters_host.hpp), as ONE member of gb25_model.
+// averages_host.hpp, classes_host.hpp, particles_host.hpp, spectrum_host.hpp, surfaces_host.hpp, stability_host.hpp, kinematics_host.hpp, region_host.hpp, zonal_eddy_host.hpp, blocks_host.hpp, filters_host.hpp), as ONE member of gb25_model.
 // Host only; included by gb25_api.hip behind the kernel headers (PartState: particle_kernels.hpp; SURF_MAX: surface_kernels.hpp;
 // GB25_A_COUNT and the info structs: include/gb25.h); like Field it is local to that translation unit, so the libraries export
 // nothing of it.
@@ -94,6 +94,9 @@ struct DiagState {
   DiagBuffer filters;
   std::vector<double> filter_wx, filter_wy;
   std::vector<int32_t> filter_rows;
+  // coherent regions (gb25_label_regions, gb25_get_regions): a result buffer -- the counts of the levels of one call, its label
+  // planes, its records, then the scratch of ONE level: the union-find forest, the numbers at the keys, the blocks' root counts
+  DiagBuffer regions;
   // time averages (gb25_averages_*): the accumulators of the active groups and the array a normalized read-out is divided into
   // -- ONE allocation (avg_acc[0] is its base: MEANS is always active), made by gb25_averages_begin, freed by gb25_averages_end
   // and gb25_destroy --, the window, the sample count and weight_sum (avg_info)
@@ -158,7 +161,7 @@ struct DiagState {
     drop(derived);
     drop(transport);
     drop(stability);
-    for (DiagBuffer* b : {&class_sums, &spectrum, &surfaces, &zonal_eddy, &blocks, &filters}) b->drop();
+    for (DiagBuffer* b : {&class_sums, &spectrum, &surfaces, &zonal_eddy, &blocks, &filters, &regions}) b->drop();
     release_tables();
     release_averages();
     release_particles();

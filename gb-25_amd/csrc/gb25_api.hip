@@ -20,6 +20,7 @@
 #include "zonal_eddy_kernels.hpp"
 #include "block_kernels.hpp"
 #include "filter_kernels.hpp"
+#include "region_kernels.hpp"
 #include "restart_kernels.hpp"
 #include "diagnostics_state.hpp"
 #include "validity.hpp"
@@ -3484,6 +3485,7 @@ gb25_status gb25_profile_get(gb25_model* m, gb25_kernel k, int64_t* launches, do
 #include "surfaces_host.hpp"
 #include "stability_host.hpp"
 #include "kinematics_host.hpp"
+#include "region_host.hpp"
 #include "zonal_eddy_host.hpp"
 #include "blocks_host.hpp"
 #include "filters_host.hpp"

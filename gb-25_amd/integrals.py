@@ -24,6 +24,7 @@ _FACES_Z = ("w", "kappa_u", "kappa_c", "kappa_e")
 _FLAT = ("eta", "U", "V", "eta_bar", "U_bar", "V_bar", "Gn.U", "Gn.V", "Jb")
 FOLDED_GRID_TYPES = (3, 4)      # gb25_grid_type: tripolar, tripolar with the Gaussian islands
 LAT_LON_GRID_TYPES = (0, 1)     # row tables; the others have 2-D metrics
+ISLAND_GRID_TYPES = (1, 4)      # the two with the Gaussian islands: a bottom table, land; on the others every cell is wet
 
 
 def location(name):

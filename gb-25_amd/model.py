@@ -92,6 +92,12 @@ class Field:
         from .kinematics import kinematics
         return kinematics(self._b, "gradient", self.name, levels)
 
+    def regions(self, below=None, above=None, levels=None, carry=None, max_regions=4096):
+        """The connected regions of every level where this field (T, S or e) lies below (or above) a threshold, labelled and
+        measured on the device (regions of this module)."""
+        from .regions import regions
+        return regions(self._b, self.name, below=below, above=above, levels=levels, carry=carry, max_regions=max_regions)
+
     def zonal_spectrum(self, wavenumbers=None, levels=None):
         """(X [level, row, m] complex128, nonfinite_lines): the zonal wavenumber coefficients of every interior line, computed
         where the field lives (zonal_spectrum of this module)."""
@@ -505,6 +511,29 @@ def eddy_part(model, source, radius, kernel="box", levels=None, length=None):
     x = np.asarray(source_values(b, source), np.float64)[:, :sums.dims[1], k0:k0 + sums.dims[2]]
     with np.errstate(invalid="ignore"):
         return np.where(own > 0, x - sums.mean(), np.nan)
+
+
+def regions(model, source, below=None, above=None, levels=None, carry=None, max_regions=4096, param=None, labels=False):
+    """The coherent regions of `source` -- "T", "S", "e"; "kinetic_energy", "density_anomaly", "potential_density"; "divergence",
+    "normal_strain", "okubo_weiss", "gradient", "frontogenesis" (param: their tracer) -- below (or above) a threshold, level by
+    level, labelled and measured on the device (include/gb25.h, gb25_get_regions): `regions(model, "okubo_weiss", below=-2e-11,
+    levels=(Nz - 1, 1), carry="T")` counts the vortex cores of the surface.  4-connectivity, the x seam joined on a periodic grid,
+    land and non-finite cells in the background.  Returns regions.Regions: .count, .records (one structured record per region:
+    cells, key, box, wraps, measure, first, second, carried, centroid sums, extreme), .labels() (int32 [i, j, kk], -1: background;
+    copied with the records only with labels=True, else when first asked for, which must be before the model is stepped again),
+    .volume() [m^3], .area() [m^2], .mean(), .centroid(), .centroid_lonlat().  At most max_regions records per level are stored;
+    .count is the true number."""
+    from .regions import regions as regions_of         # (the kernels, or the numpy restatement on a backend without them)
+    return regions_of(model.backend, source, below=below, above=above, levels=levels, carry=carry, max_regions=max_regions, param=param,
+                      labels=labels)
+
+
+def eddy_census(model, level=None, factor=0.2, carry=None, max_regions=4096, labels=False):
+    """The vortex cores of one level (default: the surface) by the usual Okubo-Weiss criterion W < -factor * sigma_W, sigma_W the
+    standard deviation of W over the wet cells of THAT level (regions.okubo_weiss_sigma: the level's plane of W is computed on
+    the device and reduced on the host): regions.Regions."""
+    from .regions import eddy_census as census
+    return census(model.backend, level, factor, carry, max_regions, labels)
 
 
 def _transport(model, faces, shape, window=None):

@@ -1136,6 +1136,93 @@ gb25_status gb25_get_derived_filter_sums(gb25_model *m, gb25_derived q, double p
                                          const double *wy, const int32_t *rx_of_row, double *measure, double *first, double *second,
                                          gb25_filter_info *info);
 
+/* ---- coherent regions on the device (csrc/region_kernels.hpp, k_region_*): every diagnostic above reduces along an index, a box,
+ *      a window or a class.  This one answers what a baroclinic-instability run is made for -- how many eddies are there, how big
+ *      are they, where are they, what do they carry: a plane of a centre-located quantity is thresholded, its connected regions
+ *      are labelled, and every region gets one record whose sums run in a fixed order, without the plane crossing PCIe.  Same
+ *      contract as every diagnostic here: the state gb25_get_field would return, READ-ONLY for the schedule (nothing pinned, every
+ *      look-ahead alive), bitwise repeatable, no floating-point atomics, launches under GB25_K_DIAGNOSTICS on the model's
+ *      stream.  NOT on a rank of a decomposition (below).
+ *
+ *      DEFINITIONS.
+ *      CRITERION.  x(i, j, k) at (Center, Center, Center) on the interior, Nx x Ny per level, from one of three sources:
+ *        GB25_REGION_FIELD       id = a gb25_field: GB25_T, GB25_S or GB25_E, read where it lies; param = 0
+ *        GB25_REGION_DERIVED     id = a gb25_derived: GB25_D_KINETIC_ENERGY, GB25_D_DENSITY_ANOMALY or GB25_D_POTENTIAL_DENSITY; param = 0
+ *        GB25_REGION_KINEMATICS  id = a gb25_kinematics: GB25_KIN_DIVERGENCE, GB25_KIN_NORMAL_STRAIN, GB25_KIN_OKUBO_WEISS,
+ *                                GB25_KIN_GRADIENT or GB25_KIN_FRONTOGENESIS with its param
+ *      The bits of x are the bits gb25_get_field, gb25_get_derived and gb25_get_kinematics hand out (the last two are computed by
+ *      their own launches into the model's packed array and read from there).  A quantity at the corners (GB25_D_VORTICITY,
+ *      GB25_KIN_SHEAR_STRAIN, GB25_KIN_ROSSBY_NUMBER), the 2-D GB25_D_MIXED_LAYER_DEPTH and every other field (the face fields
+ *      among them) are refused by name.
+ *      FOREGROUND.  cmp = GB25_REGION_BELOW or GB25_REGION_ABOVE.  A cell is foreground iff x < (real)threshold (ABOVE: >), compared
+ *      in the library's float type, AND x is finite AND mu(i, j, k) > 0 with mu THE MEASURE of gb25_integrate_field at (c,c,c): land
+ *      and the cells below the bottom are background.  nonfinite_cells counts the cells with mu > 0 whose x is not finite.
+ *      CONNECTIVITY.  Levels are labelled independently.  Within a level cells are neighbours across their four faces
+ *      (4-connectivity); column Nx - 1 is the neighbour of column 0 exactly where the grid is periodic in x (every single domain of
+ *      this library is).  There is NO connection across a wall (rows 0 and Ny - 1 have no neighbour beyond) and NONE across the
+ *      tripolar fold: on a folded grid the two halves of the last row meet physically, here they are joined only through the cells
+ *      between them.
+ *      LABELS.  A region's key is the smallest linear index i + Nx j among its cells; the regions of a level are numbered 0 .. n - 1
+ *      in ascending order of key.  The label plane is int32, Nx x Ny per level of the window (i fastest, then j, then the level):
+ *      the region's number in a foreground cell, -1 in a background cell.  This is unique: any correct algorithm gives these bits.
+ *      RECORD (gb25_region), one per region: cells; the key's (key_i, key_j); the box i_min .. i_max, j_min .. j_max of its cells
+ *      (columns as stored: a region across the seam has 0 and Nx - 1); wraps = 1 iff the grid is periodic in x and some row has
+ *      both its column 0 and its column Nx - 1 in the region; measure = sum mu, first = sum mu x, second = sum mu x^2, carried = sum
+ *      mu y for the optional second field y (carried_field = GB25_T, GB25_S or GB25_E; -1: none, carried = 0; y is not tested for
+ *      being finite); sum_di = sum mu di, sum_dj = sum mu dj with di = i - key_i, on a periodic grid wrapped into [-Nx/2, Nx/2)
+ *      (di - Nx where 2 di >= Nx, di + Nx where 2 di < -Nx), and dj = j - key_j: the centroid is (key_i + sum_di / measure, key_j +
+ *      sum_dj / measure); extreme = the smallest x of the region for BELOW, the largest for ABOVE, at (extreme_i, extreme_j): of
+ *      equal values the cell with the smallest linear index.
+ *      ARITHMETIC OF THE SUMS.  x, y = (double) of the stored values; the terms are mu, t = mu * x, q = t * x, mu * y, mu *
+ *      (double)di, mu * (double)dj: fp64 products that round by themselves, NO fused multiply-adds.  Every sum starts from +0.0 and
+ *      is sequential, acc = acc + term, over the region's cells in ascending linear index.  No floating-point atomics.
+ *      gb-25_amd/regions.py (label_host, region_records_host) restates labels and records with numpy bit for bit.
+ *      CAP.  max_regions >= 1 records per level.  gb25_regions_info, one per level: regions = the true count; stored =
+ *      min(regions, max_regions): the records of the regions 0 .. stored - 1, the others are dropped; foreground_cells;
+ *      nonfinite_cells.  The label plane is always complete.
+ *      gb25_label_regions: the device-pointer form.  *dev_labels: int32 [Nx Ny k_count]; *dev_records: gb25_region, level kk's at
+ *      kk max_regions, its first `stored` valid; in an array the model owns (made by the first call, made anew when a call needs
+ *      more, freed by gb25_destroy; its size is checked against the free device memory before it is allocated); read-only,
+ *      complete when the call returns, valid until the next call on m.  info: k_count records on the host.  Either pointer
+ *      argument may be NULL.
+ *      gb25_get_regions: the host form.  labels (may be NULL: then only the records and infos cross PCIe) [Nx Ny k_count];
+ *      records [max_regions k_count], level kk's at kk max_regions, those beyond `stored` zeroed; info [k_count].
+ *      k_first, k_count select levels as in gb25_get_kinematics (k_count = -1: all from k_first on).  The levels of a window are
+ *      processed one after another; each equals the call of that level alone.
+ *      STATIC BOUNDS.  Every device loop has one.  Should a union-find walk ever exhaust its Nx Ny hops the call returns
+ *      GB25_ERR_STATE and names the level.
+ *      RANKS OF A DECOMPOSITION.  A region reaches beyond the rank's columns and rows: on a rank (nranks > 1 or slab_mode = 1)
+ *      the two device entries return GB25_ERR_STATE and say so.  gb25_region_dims needs no device and answers there too.
+ *      ERRORS, each GB25_ERR_INVALID_ARGUMENT with a message that names the argument, refused before the device is touched, the
+ *      model stays usable and an earlier result readable: an unknown source_kind, id, param or cmp, a quantity that is not at
+ *      (c,c,c), a carried_field other than T, S, E or -1, a threshold that is NaN, a window outside the levels, max_regions < 1,
+ *      no output requested. */
+typedef enum { GB25_REGION_FIELD = 0, GB25_REGION_DERIVED = 1, GB25_REGION_KINEMATICS = 2 } gb25_region_source;
+typedef enum { GB25_REGION_BELOW = 0, GB25_REGION_ABOVE = 1 } gb25_region_cmp;
+typedef struct {
+  int32_t cells;
+  int32_t key_i, key_j;              /* 0-based local interior indices, here and below */
+  int32_t i_min, i_max, j_min, j_max;
+  int32_t wraps;
+  int32_t extreme_i, extreme_j;
+  double measure, first, second, carried;
+  double sum_di, sum_dj;
+  double extreme;
+} gb25_region;
+typedef struct {
+  int32_t regions, stored;
+  int64_t foreground_cells, nonfinite_cells;
+} gb25_regions_info;
+int32_t gb25_region_bytes(void);          /* sizeof the two structs as THIS library was built */
+int32_t gb25_regions_info_bytes(void);
+gb25_status gb25_region_dims(const gb25_model *m, int32_t dims[3]);   /* Nx, Ny, the levels; needs no device */
+gb25_status gb25_label_regions(gb25_model *m, gb25_region_source source_kind, int32_t id, int32_t param, int32_t carried_field,
+                               gb25_region_cmp cmp, double threshold, int32_t k_first, int32_t k_count, int32_t max_regions,
+                               const void **dev_labels, const void **dev_records, gb25_regions_info *info);
+gb25_status gb25_get_regions(gb25_model *m, gb25_region_source source_kind, int32_t id, int32_t param, int32_t carried_field,
+                             gb25_region_cmp cmp, double threshold, int32_t k_first, int32_t k_count, int32_t max_regions,
+                             int32_t *labels /* may be NULL */, gb25_region *records, gb25_regions_info *info);
+
 /* ---- time averages and eddy fluxes accumulated on the device (csrc/averages_kernels.hpp, k_averages_accumulate): what the other
  *      diagnostics cannot do -- remember something between two calls.  The time-mean state, eddy kinetic energy and tracer
  *      variance, the eddy heat and salt fluxes <v'T'>, <u'T'>, <w'T'>: Oceananigans' AveragedTimeInterval, without five parent arrays
